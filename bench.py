@@ -16,6 +16,11 @@ rank's pixels.  Workloads (`--workload`, BASELINE.json configs):
 With N > 1 the timed region ends with the RCCL (torch.distributed "nccl") sum-reduce of the
 radiance frame to rank 0, which assembles the image (pixels outside a rank's bands are zero, so
 the sum is exact).  Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for the fields).
+
+A plain run sets up, warms up (tuning steps included), times `--steps` steps and prints the line.
+`--full` adds the CPU baseline (the oracle on this job's CPUs and the SMT-yield probe: ten seconds
+or more of host work before the GPU phase).  `--dump-outputs DIR` writes the frame the timed path
+holds after its last step as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -387,6 +392,32 @@ def rccl_versions(group=None):
     return out
 
 
+DUMP_BYTES_MAX = 64 * 1000 * 1000    # --dump-outputs: all files together stay below this
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, col, cnt, px):
+    """--dump-outputs: what a caller of the timed path reads back after the last timed step, as
+    float32 .npy files, one row per pixel in frame order: colors (n, 3) the running-mean radiance
+    (read_radiance), counter (n,) the passes each pixel holds, pixels (n, 3) the 8-bit RGB of
+    read_pixels (its fourth byte is padding).  A frame that would exceed DUMP_BYTES_MAX is cut to a
+    fixed, seeded sample of its pixels, the same for every run of the same frame size; index.npy
+    (float64) then holds the sampled pixels' positions y * W + x in ascending order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = cnt.size
+    col, cnt, px = col.reshape(n, 3), cnt.reshape(n), px.reshape(n, 4)[:, :3]
+    per_pixel = 4 * (3 + 1 + 3)
+    if n * per_pixel > DUMP_BYTES_MAX - 4096:                 # 4 .npy headers of 128 B and slack
+        keep = (DUMP_BYTES_MAX - 4096) // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+        np.save(os.path.join(path, "index.npy"), idx.astype(np.float64))
+        col, cnt, px = col[idx], cnt[idx], px[idx]
+    np.save(os.path.join(path, "colors.npy"), np.ascontiguousarray(col, dtype=np.float32))
+    np.save(os.path.join(path, "counter.npy"), cnt.astype(np.float32))     # <= 30000: exact
+    np.save(os.path.join(path, "pixels.npy"), px.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
@@ -405,8 +436,14 @@ def main():
     ap.add_argument("--streams", type=int, default=0, help="pass streams per pixel (0 = auto: measured choice of one pass per lane or the fused kernel; -1 = one pass per lane; 1 = fused)")
     ap.add_argument("--specialize", type=int, default=1, choices=[0, 1],
                     help="scene-specialised kernels (run-time compiled; results identical)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (the oracle "
+                         "on this job's CPUs, the 1-core figure, the SMT-yield probe) and the speed-ups over it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame of the last timed step (colors, counter, "
+                         "pixels) as DIR/<name>.npy, float32, at most 64 MB (a seeded sample of a larger frame)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: length of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-smt-probe", action="store_true", help="skip the SMT-yield probe of the CPU baseline")
     ap.add_argument("--rehearse", action="store_true",
                     help="multi-rank dry run on fewer GPUs: gloo, ranks share devices (not a measurement)")
@@ -467,10 +504,10 @@ def main():
     untimed = tune + args.warmup + follow
     sid, vlp = sched.next(per_step * (untimed + args.steps))
 
-    # The CPU baseline (rank 0 at N = 1) runs first, before the GPU is touched: the GPU phase
-    # (tuning, warm-up, timed steps) then runs as one block.
+    # The CPU baseline (--full; rank 0 at N = 1) runs first, before the GPU is touched: the GPU
+    # phase (tuning, warm-up, timed steps) then runs as one block.
     cpu = None
-    if world == 1 and ndev == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and ndev == 1 and not args.no_cpu_baseline:
         rows = shd.owned_row_ranges(H, rank, nshards, band)
         region = (rows[0][0], rows[0][1]) if wl["fixed_bands"] else (0, H)
         cpu = cpu_baseline(sp, cam, W, H, region, sid, vlp, args.cpu_seconds)
@@ -621,11 +658,14 @@ def main():
         # last reset, the rest none
         if dist is not None:
             r.update_pixels()
+            col = t_col.cpu().numpy().reshape(H, W, 3) if args.dump_outputs else None
             cnt = t_cnt.cpu().numpy().reshape(H, W)
         else:
-            cnt = r.read_radiance()[1]
+            col, cnt = r.read_radiance()
         owned = (torch.arange(H).numpy() // band) % nshards < units
         assert (cnt[owned] == spp_total).all() and (cnt[~owned] == 0).all(), "frame counters wrong"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, col, cnt, r.read_pixels())
     if rank == 0:
         w = WORK.get(wl["scene"])
         avg_launch_s = kern_ms / 1e3 / max(launches, 1)

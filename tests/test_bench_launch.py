@@ -52,6 +52,36 @@ def test_gpus_2_without_gpus_refuses_cleanly():
     assert "GPU" in r.stderr, r.stderr[-800:]
 
 
+def test_dump_outputs_layout_and_seeded_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: a frame within the size budget is written whole, float32, one row per
+    pixel; a larger one is cut to a sample of its pixels that is the same on every call, named by
+    index.npy, and every file set stays below the budget."""
+    import numpy as np
+    H, W = 25, 33
+    rng = np.random.default_rng(1)
+    col = rng.random((H, W, 3), dtype=np.float32)
+    cnt = np.full((H, W), 52, np.uint32)
+    px = rng.integers(0, 256, (H, W, 4), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "whole"), col, cnt, px)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["colors.npy", "counter.npy", "pixels.npy"]
+    got = {n: np.load(tmp_path / "whole" / (n + ".npy")) for n in ("colors", "counter", "pixels")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["colors"], col.reshape(-1, 3)) and np.array_equal(got["counter"], cnt.reshape(-1))
+    assert np.array_equal(got["pixels"], px.reshape(-1, 4)[:, :3])
+
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 16384)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), col, cnt, px)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 16384
+    idx = np.load(tmp_path / "s1" / "index.npy")
+    assert idx.dtype == np.float64 and 300 < len(idx) < H * W and (np.diff(idx) > 0).all()
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "index.npy"))
+    k = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "s1" / "colors.npy"), col.reshape(-1, 3)[k])
+    assert np.array_equal(np.load(tmp_path / "s1" / "pixels.npy"), px.reshape(-1, 4)[k, :3])
+    assert np.array_equal(np.load(tmp_path / "s1" / "counter.npy"), cnt.reshape(-1)[k])
+
+
 def test_smt_topology_helpers():
     topo = bench.cpu_topology()
     assert topo and all(isinstance(v, tuple) and len(v) == 2 for v in topo.values())

@@ -34,3 +34,42 @@ def test_bench_crosses_counter_cap():
     assert cfg["samples_per_step"] == 97 * 65 * 128
     for k in ("metric", "unit", "ms_per_step", "higher_is_better", "scaling", "dtype", "roofline", "cpu_baseline"):
         assert k in d
+
+
+def test_dump_outputs_is_the_last_steps_frame(tmp_path):
+    """--dump-outputs writes the frame the timed path holds after its last timed step: float32
+    files that equal, bit for bit, the oracle's frame for every pass the run rendered (tuning,
+    warm-up and timed steps), and that a second run of the same workload writes again.  The plain
+    run carries no CPU baseline; the second run adds --full, which brings it back and changes
+    nothing about the frame."""
+    import numpy as np
+
+    import gpu_bidirectional_raytracer_amd as g
+    import oracle
+
+    args = ("--scene", "simple", "--width", "32", "--height", "24", "--passes", "4", "--steps", "2", "--warmup", "1")
+    a, b = tmp_path / "a", tmp_path / "b"
+    d = run_bench(*args, "--dump-outputs", str(a))
+    full = run_bench(*args, "--dump-outputs", str(b), "--full", "--cpu-seconds", "0.2", "--no-smt-probe")
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert d["cpu_baseline"] is None and "speedup_vs_cpu" not in d
+    assert full["cpu_baseline"]["value"] > 0 and full["speedup_vs_cpu"] > 0
+
+    W, H = 33, 25
+    npass = (d["tune_steps"] + 1 + 2) * 4
+    assert d["config"]["spp_total"] == npass
+    cam, sp = g.read_scene(os.path.join(REPO, "assets", "scenes", "simple.scn"))
+    g.update_camera(cam, W, H)
+    sched = g.PassScheduler()
+    sched.light()
+    sid, vlp = sched.next(npass)
+    rnd = oracle.mt607(0)
+    ocol, ocnt, opx = oracle.path_passes(sp, rnd, cam, W, H, oracle.light_pass(sp, rnd, 0), sid, vlp)
+    want = {"colors": ocol.reshape(-1, 3), "counter": ocnt.reshape(-1), "pixels": opx.reshape(-1, 4)[:, :3]}
+    assert sorted(os.listdir(a)) == sorted(os.listdir(b)) == ["colors.npy", "counter.npy", "pixels.npy"]
+    for name, ref in want.items():
+        got = np.load(a / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == ref.shape
+        assert np.array_equal(got, ref.astype(np.float32)), name
+        assert np.array_equal(got, np.load(b / (name + ".npy"))), name
+    assert (want["counter"] == npass).all() and want["colors"].any()
