@@ -2,6 +2,8 @@
 #   libbdpt.so  : HIP kernels (gfx950) + C-ABI + host utilities   (the product)
 #   smallpt     : headless C host program, drop-in for smallpt_cpu.c's main/IdleFunc loop
 #   oracle/liboracle.so : CPU restatement used by tests/bench only (never linked by the product)
+#   oracle/_ref/libref.so : the reference's own kernels compiled in place as host C++, where the
+#                           reference tree exists (tests only; see "The reference build" below)
 # Everything builds with -ffp-contract=off: results must match the oracle bit for bit.
 
 PKG      := gpu_bidirectional_raytracer_amd
@@ -70,6 +72,43 @@ $(GLHOST): $(CSRC)/smallpt_gl.c $(CSRC)/smallpt_app.h include/bdpt.h $(LIB)
 
 $(ORACLE): oracle/bdpt_oracle.c include/bdpt.h
 	$(CC) -O2 -std=gnu11 -fPIC -shared -fopenmp -ffp-contract=off -Wall -o $@ $< -lm
+
+# The reference build (test infrastructure; tests/test_ref_parity.py, tests/golden/make_ref_golden.py).
+# The reference's src/device.cu and src/MersenneTwister_kernel.cu compile, unmodified and in place,
+# as host C++ behind oracle/ref_shim.h; oracle/ref_driver.cpp replays the launches of
+# smallpt_cpu.c.  The four -D renames repair identifiers the reference left stale when it renamed
+# its locals (device.cu:260,279-300,670 use hitPoint/currentRay/inilight/pC; the declarations are
+# hit_point/current_ray/ini_light/rand_count); every other use of those names is a consistent local
+# or parameter, so the global rename is exact.  Nothing of the reference is copied: oracle/_ref/ is
+# ignored by git, and where BDPT_REFERENCE does not exist the step is skipped and whatever
+# oracle/_ref/ holds is left alone.
+#   libref.so      : cos/sin/pow of a float evaluated as (float)f((double)x) (the project's contract)
+#   libref_libm.so : the same calls resolved to the platform's float overloads (measured only)
+#   libref_host.so : the reference's src/display_func.c (ReadScene, UpdateCamera, KeyFunc,
+#                    SpecialFunc) as C, against the empty GL/CUDA stand-ins of oracle/ref_stubs/
+#                    and the callbacks of oracle/ref_host_driver.c
+BDPT_REFERENCE ?= /root/reference
+REFDIR     := oracle/_ref
+REF_SRCS   := $(BDPT_REFERENCE)/src/device.cu $(BDPT_REFERENCE)/src/MersenneTwister_kernel.cu
+REF_RENAME := -DhitPoint=hit_point -DcurrentRay=current_ray -Dinilight=ini_light -DpC=rand_count
+REF_FLAGS  := -O2 -ffp-contract=off -fPIC -shared -w -Wl,-Bsymbolic -include oracle/ref_shim.h \
+              -I$(BDPT_REFERENCE)/include $(REF_RENAME)
+ifneq ($(wildcard $(BDPT_REFERENCE)/src/device.cu),)
+all: $(REFDIR)/libref.so $(REFDIR)/libref_libm.so $(REFDIR)/libref_host.so
+
+$(REFDIR)/libref.so: $(REF_SRCS) oracle/ref_driver.cpp oracle/ref_shim.h
+	mkdir -p $(REFDIR)
+	g++ $(REF_FLAGS) -o $@ -x c++ $(REF_SRCS) oracle/ref_driver.cpp -lm
+
+$(REFDIR)/libref_libm.so: $(REF_SRCS) oracle/ref_driver.cpp oracle/ref_shim.h
+	mkdir -p $(REFDIR)
+	g++ $(REF_FLAGS) -DREF_PLATFORM_LIBM -o $@ -x c++ $(REF_SRCS) oracle/ref_driver.cpp -lm
+
+$(REFDIR)/libref_host.so: $(BDPT_REFERENCE)/src/display_func.c oracle/ref_host_driver.c $(wildcard oracle/ref_stubs/*.h oracle/ref_stubs/GL/*.h)
+	mkdir -p $(REFDIR)
+	gcc -O2 -std=gnu11 -ffp-contract=off -fPIC -shared -w -Wl,-Bsymbolic -Ioracle/ref_stubs \
+	    -I$(BDPT_REFERENCE)/include -o $@ $(BDPT_REFERENCE)/src/display_func.c oracle/ref_host_driver.c -lm
+endif
 
 # Sanitizer build (GPU sanitizers are not available on the pool): the C host, the host
 # utilities and the CPU backend under AddressSanitizer + UBSan through a HIP-free context layer,

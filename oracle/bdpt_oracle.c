@@ -7,10 +7,13 @@
  * `cpu_baseline` leg of bench.py.  Only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline may load it; the product never links it.
  *
- * Pinning (see DESIGN.md "Oracle"): the reference itself is unbuildable in this image (it needs
- * the CUDA toolkit/runtime and does not compile as shipped -- SURVEY.md 8(c)), so this
- * restatement is pinned by the known answers the survey recorded from the reference's own
- * kernels (MT607 table hashes and values, the cornell VLP dev_lp[1]) and by glibc rand().
+ * Pinning (see DESIGN.md "Oracle"): the reference does not compile as shipped (it wants the CUDA
+ * toolkit and has four stale identifiers -- SURVEY.md 8(c)), but its device.cu and
+ * MersenneTwister_kernel.cu compile in place as host C++ behind oracle/ref_shim.h
+ * (oracle/_ref/libref.so, built by `make` wherever the reference tree exists).  That build is
+ * the checker of record: tests/test_ref_parity.py holds this restatement to it bit for bit (MT607
+ * table, dev_lp, radiance, counters, pixels, camera and key functions).  The survey's known
+ * answers (table values, the cornell VLP dev_lp[1]) and glibc rand() remain as earlier pins.
  *
  * Floating-point contract (both here and in the HIP kernels): IEEE fp32 with no contraction
  * (-ffp-contract=off), correctly rounded division and sqrt, the two fp64 steps of the camera

@@ -1,0 +1,2 @@
+/* Empty stand-in: see ref_host_stub.h. */
+#include "ref_host_stub.h"
