@@ -381,6 +381,13 @@ class Renderer:
         self._chk(lib.bdpt_read_rand(self._h, _ptr(t)))
         return t
 
+    def read_sample_records(self) -> np.ndarray:
+        """The sample records of the current table, [RAND_N - 5, 8] = {A, B, C, u2, X, Y, Z, u0} per
+        position (include/bdpt.h bdpt_read_sample_records)."""
+        rec = np.empty((RAND_N - 5, 8), np.float32)
+        self._chk(lib.bdpt_read_sample_records(self._h, _ptr(rec)))
+        return rec
+
     def read_lightpaths(self) -> np.ndarray:
         lp = np.empty(LIGHT_POINTS, LIGHTPATH_DTYPE)
         self._chk(lib.bdpt_read_lightpaths(self._h, _ptr(lp)))

@@ -4,6 +4,12 @@
 //   d_rand    float[7,684,096]      MT607 table, lane-major (tid + k*4096)      30.7 MB
 //   d_rndp    float[29][307,364]    the same table in 29 planes (j mod 25)     35.6 MB
 //   d_scp     float2[29][307,364]   {sinf, cosf}(2 pi u) of every d_rndp entry 71.3 MB
+//             (filled before the first launch of a kernel that reads it: the pass-stream
+//             kernels without sample records)
+//   d_srec    float4[2][25][307,364] sample records (bdpt_sample_records_kernel): per table
+//             position j, at [j mod 25][j / 25], half 0 = {A, B, C, u2}, half 1 = {X, Y, Z, u0}
+//             (bdpt_math.h bdpt_sample_record); allocated and filled before the first launch
+//             of a kernel that reads it (specialised pass-stream kernels, BDPT_SREC) 245.9 MB
 //   d_lp      bdpt_dev_lightpath[4096]  VLPs {hp, rad, nl}, AoS 36 B            147 KB
 //   d_sph     bdpt_dev_sphere[n]    48 B/sphere {p, rad^2, e, rad, c, refl}
 //   d_colors  bdpt_dev_vec[W*H]     running-mean radiance, AoS 12 B (== dev_colors)
@@ -21,6 +27,9 @@
 // plane 25 + t holds d_Rand[25 (q + 1) + t]; PL = ceil(RAND_N / 25) entries per plane
 #define BDPT_DEV_RANDP_PL 307364u
 #define BDPT_DEV_RANDP_PLANES 29u
+// sample records: 25 planes (the offsets +0..+4 are folded into the record: no wrap planes), two
+// float4 halves BDPT_DEV_SREC_HALF entries apart; positions j >= RAND_N - 5 hold zeros
+#define BDPT_DEV_SREC_HALF (25u * BDPT_DEV_RANDP_PL)
 #define BDPT_DEV_N_PER_RNG 1876
 #define BDPT_DEV_LIGHT_POINTS 4096
 #define BDPT_DEV_COUNTER_CAP 30000u
@@ -65,7 +74,8 @@ struct bdpt_path_args {
     unsigned emis_mask;             // bit s = sphere s is emissive (sphere counts <= 32)
     const float* rnd;
     const float* rndp;              // the planar copy (BDPT_DEV_RANDP_*), pass-stream kernels
-    const float2* scp;              // per planar entry u: {sinf, cosf}(2 pi u) (bdpt_sincos_planar_kernel)
+    const float2* scp;              // per planar entry u: {sinf, cosf}(2 pi u) (bdpt_sincos_planar_kernel);
+                                    // for a BDPT_SREC kernel the sample records instead (d_srec, float4)
     const bdpt_dev_lightpath* lp;
     const unsigned* sid;            // per pass (nullptr: the pass table is sid_inl / vlp_inl)
     const int* vlp;                 // per pass

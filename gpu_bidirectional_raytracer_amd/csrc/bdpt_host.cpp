@@ -42,6 +42,7 @@ static_assert(sizeof(bdpt_dev_vec) == sizeof(bdpt_vec), "colour layout");
 extern "C" __global__ void bdpt_mt607_kernel(const uint4*, unsigned, float*);
 extern "C" __global__ void bdpt_rand_planar_kernel(const float*, float*);
 extern "C" __global__ void bdpt_sincos_planar_kernel(const float*, float2*);
+extern "C" __global__ void bdpt_sample_records_kernel(const float*, float4*);
 extern "C" __global__ void bdpt_light_kernel(const bdpt_dev_sphere*, unsigned, const float*, int,
                                              bdpt_dev_lightpath*);
 extern "C" const void* bdpt_path_kernel_table[36];   // [(S > 1) * 18 + (BVH ? 17 : n <= 16 ? n : 0)]
@@ -161,7 +162,13 @@ struct bdpt_ctx {
     uint4* d_params = nullptr;          // 4096 x {matrix_a, mask_b, mask_c, seed}
     float* d_rand = nullptr;
     float* d_rndp = nullptr;            // planar copy of d_rand (bdpt_rand_planar_kernel)
+    // Tables derived from d_rand that only some path kernels read: allocated on first need and
+    // filled before the first launch of a kernel that reads them (ensure_scp / ensure_srec); every
+    // table change (one_generate_rand: the light pass and a checkpoint load come through it) clears
+    // the ready flags.  Each device of a multi-device context owns its own.
     float2* d_scp = nullptr;            // {sinf, cosf}(2 pi u) per d_rndp entry (bdpt_sincos_planar_kernel)
+    float4* d_srec = nullptr;           // sample records (bdpt_sample_records_kernel, bdpt_device.h)
+    bool scp_ready = false, srec_ready = false;   // they hold the current table's values
     bdpt_dev_lightpath* d_lp = nullptr;
     bdpt_dev_sphere* d_sph = nullptr;
     unsigned sph_cap = 0;
@@ -336,7 +343,7 @@ static int upload_scene(bdpt_ctx* c) {
 }
 
 static void release(bdpt_ctx* c) {
-    void* bufs[] = {c->d_params, c->d_rand, c->d_rndp, c->d_scp, c->d_lp, c->d_sph, c->d_lights, c->d_geom, c->d_lightrec, c->d_colors,
+    void* bufs[] = {c->d_params, c->d_rand, c->d_rndp, c->d_scp, c->d_srec, c->d_lp, c->d_sph, c->d_lights, c->d_geom, c->d_lightrec, c->d_colors,
                     c->d_counter, c->d_pixels, c->d_thr, c->d_rbuf, c->d_rmask, c->d_poolctr, c->d_uflags, c->d_uerr, c->d_bvh_nodes,
                     c->d_bvh_geom, c->d_big_geom, c->d_mat, c->d_bvh_ids, c->d_big_ids,
                     c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc};
@@ -861,7 +868,6 @@ int bdpt_create(bdpt_ctx** out, const bdpt_sphere* spheres, unsigned n, int W, i
     CK(hipMalloc(&c->d_params, sizeof(c->h_params)));
     CK(hipMalloc(&c->d_rand, sizeof(float) * BDPT_RAND_N));
     CK(hipMalloc(&c->d_rndp, sizeof(float) * BDPT_DEV_RANDP_PLANES * BDPT_DEV_RANDP_PL));
-    CK(hipMalloc(&c->d_scp, sizeof(float2) * BDPT_DEV_RANDP_PLANES * BDPT_DEV_RANDP_PL));
     CK(hipMalloc(&c->d_lp, sizeof(bdpt_dev_lightpath) * BDPT_LIGHT_POINTS));
     CK(hipMalloc(&c->d_colors, sizeof(bdpt_dev_vec) * np));
     CK(hipMalloc(&c->d_counter, sizeof(unsigned) * np));
@@ -1050,13 +1056,56 @@ static int one_generate_rand(bdpt_ctx* c, unsigned seed) {
     hipLaunchKernelGGL(bdpt_rand_planar_kernel, dim3((BDPT_DEV_RANDP_PLANES * BDPT_DEV_RANDP_PL + 255) / 256),
                        dim3(256), 0, c->stream, (const float*)c->d_rand, c->d_rndp);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(bdpt_sincos_planar_kernel, dim3((BDPT_DEV_RANDP_PLANES * BDPT_DEV_RANDP_PL + 255) / 256),
-                       dim3(256), 0, c->stream, (const float*)c->d_rndp, c->d_scp);
-    HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->rand_ready = true;
+    c->scp_ready = c->srec_ready = false;              // rebuilt by the next launch that reads them
     c->rand_seed = seed;
     return BDPT_OK;
+}
+
+// The derived tables, built on the context's stream (the path kernels that read them run on it)
+// from the current d_rand / d_rndp; no-ops while they are current.
+static int ensure_scp(bdpt_ctx* c) {
+    if (c->scp_ready) return BDPT_OK;
+    const size_t n = (size_t)BDPT_DEV_RANDP_PLANES * BDPT_DEV_RANDP_PL;
+    if (!c->d_scp && hipMalloc(&c->d_scp, sizeof(float2) * n) != hipSuccess) {
+        (void)hipGetLastError();
+        c->d_scp = nullptr;
+        return fail(c, BDPT_ENOMEM, "sin/cos planes (%zu B)", sizeof(float2) * n);
+    }
+    hipLaunchKernelGGL(bdpt_sincos_planar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+                       (const float*)c->d_rndp, c->d_scp);
+    HIPCHK(c, hipGetLastError());
+    c->scp_ready = true;
+    return BDPT_OK;
+}
+
+static int ensure_srec(bdpt_ctx* c) {
+    if (c->srec_ready) return BDPT_OK;
+    const size_t n = 2 * (size_t)BDPT_DEV_SREC_HALF;
+    if (!c->d_srec && hipMalloc(&c->d_srec, sizeof(float4) * n) != hipSuccess) {
+        (void)hipGetLastError();
+        c->d_srec = nullptr;
+        return fail(c, BDPT_ENOMEM, "sample records (%zu B)", sizeof(float4) * n);
+    }
+    hipLaunchKernelGGL(bdpt_sample_records_kernel, dim3((BDPT_DEV_SREC_HALF + 255) / 256), dim3(256), 0, c->stream,
+                       (const float*)c->d_rand, c->d_srec);
+    HIPCHK(c, hipGetLastError());
+    c->srec_ready = true;
+    return BDPT_OK;
+}
+
+// Whether the specialised pass-stream kernels are built with sample records (bdpt_kernels.hip
+// BDPT_SREC, on by default in those builds): an experiment's -DBDPT_SREC=0 in BDPT_JIT_FLAGS turns
+// them off, and the host must then hand those kernels the sin/cos planes.
+static bool jit_srec_enabled() {
+    const char* f = getenv("BDPT_JIT_FLAGS");
+    bool on = true;
+    for (const char* q = f ? strstr(f, "-DBDPT_SREC") : nullptr; q; q = strstr(q + 1, "-DBDPT_SREC")) {
+        const char* v = q + strlen("-DBDPT_SREC");
+        on = *v == '=' ? atoi(v + 1) != 0 : true;
+    }
+    return on;
 }
 
 static int one_light_pass(bdpt_ctx* c, int current_sample) {
@@ -1130,7 +1179,6 @@ static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int
     a.emis_mask = c->emis_mask;
     a.rnd = c->d_rand;
     a.rndp = c->d_rndp;
-    a.scp = c->d_scp;
     a.lp = c->d_lp;
     a.colors = c->d_colors;
     a.counter = c->d_counter;
@@ -1323,11 +1371,12 @@ static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int
     }
     // resolve the specialised kernels (a compile on first use) before the timed region starts
     hipFunction_t jf_streams = nullptr, jf_fused = nullptr, jf_pool = nullptr, jf_units = nullptr;
-    bool any_fused = false, pool_ran = false, units_ran = false;
+    bool any_fused = false, any_streams = false, pool_ran = false, units_ran = false;
     for (int p0 = 0; grid_rows > 0 && p0 < npass; p0 += chunk) {
         const int np = npass - p0 < chunk ? npass - p0 : chunk;
         const bool st = (S < np ? S : np) > 1;
         any_fused |= !st;
+        any_streams |= st;
         if (bvh) continue;
         if (st && want_pool && !jf_pool) jf_pool = jit_path_kernel(c, true, true, true);
         if (st && want_units && !jf_units) jf_units = jit_path_kernel(c, true, true, false, true);
@@ -1339,6 +1388,16 @@ static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int
     // kernel more than the fold costs on its own -- caustic pools 4.10 -> 4.04-4.07 ms per call,
     // path kernel 3.93 -> 3.29-3.31 ms; two passes per lane keep the concurrent fold (cornell
     // S = 64 33.82 -> 33.92 ms serial), profiles/r05_s11_serial_fold.txt.
+    // the derived table this call's pass-stream kernels read (the pooled build reads neither):
+    // sample records for a specialised build that has them, else the sin/cos planes -- built here,
+    // before the call's timing starts, if the table changed since they were last built
+    const bool use_srec = any_streams && !jf_pool && (jf_units || jf_streams) && jit_srec_enabled();
+    const bool use_scp = any_streams && !jf_pool && !use_srec;
+    if (use_srec)
+        if (int rc = ensure_srec(c)) return rc;
+    if (use_scp)
+        if (int rc = ensure_scp(c)) return rc;
+    a.scp = use_srec ? (const float2*)c->d_srec : use_scp ? c->d_scp : nullptr;
     const bool serial_fold = jf_pool != nullptr;
     // Pooled launches overlap: each runs (with its fold) on pstream[half], so a launch's drain --
     // ~0.1 ms at its end, when all passes' pools run out together and the last paths finish at
@@ -1399,7 +1458,7 @@ static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int
         c->last_specialized = jf != nullptr;
         c->last_features = BDPT_FEAT_LAST_SKIP | (bvh ? BDPT_FEAT_BVH : 0) | (st ? BDPT_FEAT_STREAMS : 0) |
                            (pooled ? BDPT_FEAT_POOLS : 0) | (unitsl ? BDPT_FEAT_UNITS : 0) |
-                           (st && !pooled ? BDPT_FEAT_SCP : 0) |
+                           (st && !pooled ? BDPT_FEAT_SCP : 0) | (st && use_srec ? BDPT_FEAT_SREC : 0) |
                            (jf ? BDPT_FEAT_SPECIALIZED | BDPT_FEAT_DET_SKIP | (c->jit_zero_exit ? BDPT_FEAT_ZERO_EXIT : 0) : 0);
         void* kargs[] = {&a};
         grid.z = a.streams;
@@ -1648,6 +1707,24 @@ int bdpt_read_rand(bdpt_ctx* c, float* t) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpyAsync(t, c->d_rand, sizeof(float) * BDPT_RAND_N, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+int bdpt_read_sample_records(bdpt_ctx* c, float* rec) {
+    if (!c || !rec) return BDPT_EINVAL;
+    if (c->cpu) return fail(c, BDPT_EINVAL, "bdpt_read_sample_records: the CPU backend has no sample records");
+    if (!c->rand_ready) return fail(c, BDPT_ESTATE, "bdpt_read_sample_records: table not generated");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_srec(c)) return rc;
+    const size_t half = BDPT_DEV_SREC_HALF;
+    std::vector<float4> h(2 * half);
+    HIPCHK(c, hipMemcpyAsync(h.data(), c->d_srec, sizeof(float4) * h.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t j = 0; j < (size_t)BDPT_RAND_N - 5; j++) {     // table order: 8 floats per position
+        const size_t e = (j % 25) * BDPT_DEV_RANDP_PL + j / 25;
+        memcpy(rec + 8 * j, &h[e], sizeof(float4));
+        memcpy(rec + 8 * j + 4, &h[half + e], sizeof(float4));
+    }
     return BDPT_OK;
 }
 

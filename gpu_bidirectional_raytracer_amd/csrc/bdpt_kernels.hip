@@ -249,6 +249,23 @@ __device__ __forceinline__ f3 cosine_tail(f3 w, f3 u, float u_phi, float u_r2, f
 #ifndef BDPT_SCP_LATE
 #define BDPT_SCP_LATE 0
 #endif
+// Sample records (BDPT_SREC, where the sin/cos planes are used: pass streams without pixel
+// pools): everything a segment takes from d_Rand[j..j+4] that is a pure function of the table --
+// the cosine direction's coefficients cosf * sqrt(r2), sinf * sqrt(r2), sqrt(1 - r2) and the NEE
+// light sample uniform_sphere_sc(...) -- is computed once per table (bdpt_sample_records_kernel,
+// bdpt_math.h bdpt_sample_record) and loaded as one 32-B record per segment: two 16-B gathers and
+// the camera's d_Rand[j+1] instead of four 4-B and two 8-B gathers, and no per-vertex root,
+// products or sin/cos.  The record holds the same floats the per-segment code formed, so results
+// are unchanged bit for bit.  With it sqrt(cos2t) moves into the refraction branch (it shared an
+// instruction sequence with sqrt(r2)).  Scene-specialised builds only: the precompiled instances
+// keep the sin/cos planes.
+#ifndef BDPT_SREC
+#ifdef BDPT_JIT
+#define BDPT_SREC 1
+#else
+#define BDPT_SREC 0
+#endif
+#endif
 // Shadow rounds whose rays are all VLP rays (IntersectPVacuumDevice, device.cu:141-154, ignores
 // emitters) skip the emitters' sphere tests: the NEE rays fill the queue first, so a segment's
 // second round is usually VLP rays only.
@@ -379,6 +396,28 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_sincos_planar_kernel(cons
     float s, c;
     sincos_cr<true>(x, &s, &c, sct);
     scp[o] = make_float2(s, c);
+}
+
+// Sample records (BDPT_SREC): for every table position j < RAND_N - 5 the record of
+// d_Rand[j..j+4] (bdpt_math.h bdpt_sample_record), half 0 at srec[(j mod 25) * PL + j / 25] and
+// half 1 BDPT_DEV_SREC_HALF entries on; the other entries of the planes hold zeros.  One thread per
+// plane entry (coalesced stores); 7.7 M records per table.
+extern "C" __global__ __launch_bounds__(256) void bdpt_sample_records_kernel(const float* __restrict__ rnd,
+                                                                           float4* __restrict__ srec) {
+    __shared__ double sct[BDPT_SC_N];
+    for (int q = threadIdx.x; q < BDPT_SC_N; q += 256) sct[q] = bdpt_sincos_table_dev[q][0];
+    __syncthreads();
+    const unsigned o = blockIdx.x * 256u + threadIdx.x;
+    if (o >= BDPT_DEV_SREC_HALF) return;
+    const unsigned p = o / BDPT_DEV_RANDP_PL, qd = o - p * BDPT_DEV_RANDP_PL;
+    const unsigned j = 25u * qd + p;
+    float r[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (j < BDPT_DEV_RAND_N - 5u) {                            // j + 4 < RAND_N
+        const float u[5] = {rnd[j], rnd[j + 1], rnd[j + 2], rnd[j + 3], rnd[j + 4]};
+        bdpt_sample_record(u, sct, r);
+    }
+    srec[o] = make_float4(r[0], r[1], r[2], r[3]);
+    srec[BDPT_DEV_SREC_HALF + o] = make_float4(r[4], r[5], r[6], r[7]);
 }
 
 template <int... S>
@@ -582,6 +621,22 @@ __device__ __forceinline__ void load_sc(__amdgpu_buffer_rsrc_t rsc, unsigned j, 
     const u2v b = __builtin_amdgcn_raw_buffer_load_b64(rsc, vs, 4 * P8, 0);
     s0 = __uint_as_float(a.x); c0 = __uint_as_float(a.y);
     s4 = __uint_as_float(b.x); c4 = __uint_as_float(b.y);
+}
+
+// BDPT_SREC: the sample record of position j, {A, B, C, u2} and {X, Y, Z, u0} (two 16-B loads at
+// the same plane offset, the halves BDPT_DEV_SREC_HALF entries apart), and d_Rand[j + 1] (the
+// camera ray's second random) from the planar copy
+__device__ __forceinline__ void load_srec(__amdgpu_buffer_rsrc_t rs, __amdgpu_buffer_rsrc_t rsr, unsigned j,
+                                          float& A, float& B, float& C, float& u2, float& X, float& Y,
+                                          float& Z, float& u0, float& u1) {
+    typedef unsigned u4v __attribute__((ext_vector_type(4)));
+    const unsigned qd = j / 25u, r = j - qd * 25u;
+    const unsigned e = r * BDPT_DEV_RANDP_PL + qd;
+    const u4v a = __builtin_amdgcn_raw_buffer_load_b128(rsr, e * 16u, 0, 0);
+    const u4v b = __builtin_amdgcn_raw_buffer_load_b128(rsr, e * 16u, BDPT_DEV_SREC_HALF * 16u, 0);
+    u1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, e * 4u, BDPT_DEV_RANDP_PL * 4u, 0));
+    A = __uint_as_float(a.x); B = __uint_as_float(a.y); C = __uint_as_float(a.z); u2 = __uint_as_float(a.w);
+    X = __uint_as_float(b.x); Y = __uint_as_float(b.y); Z = __uint_as_float(b.z); u0 = __uint_as_float(b.w);
 }
 
 // f(S), f(S-1), ..., f(0) with compile-time indices while f returns true
@@ -864,10 +919,12 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
     // (not with BDPT_SCP: the pass-stream kernels load precomputed pairs -- except the pixel-pool
     // build, whose restarted lanes are bound by their random-table gathers: the two extra gathers
     // per segment cost caustic8 2.5 %, one-session A/B profiles/r06_s8_ab_scp_caustic8.txt)
-    constexpr bool kScp = STREAMS && BDPT_SCP && !BDPT_POOL;
+    // (nor with BDPT_SREC, which replaces the planes by the sample records in the same kernels)
+    constexpr bool kSrec = STREAMS && BDPT_SREC && !BDPT_POOL;
+    constexpr bool kScp = STREAMS && BDPT_SCP && !BDPT_POOL && !kSrec;
     constexpr int kSct = BDPT_SC_N >> BDPT_SC_COARSE;
     const double* SCT = nullptr;
-    if constexpr (!kScp) {
+    if constexpr (!kScp && !kSrec) {
         __shared__ double sct[kSct];
         static_assert(kSct % 256 == 0, "table fill");
 #pragma unroll
@@ -1074,12 +1131,16 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
         (void*)a.rndp, (short)0, (int)(BDPT_DEV_RANDP_PLANES * BDPT_DEV_RANDP_PL * 4u), 0x00020000);
     // BDPT_SCP: {sinf, cosf}(2 pi d_Rand[j]) and (2 pi d_Rand[j + 4]) (q4 is not loaded)
     float sn0 = 0.f, cs0 = 0.f, sn4 = 0.f, cs4 = 0.f;
+    // (BDPT_SREC: a.scp is the record table; q0 = u0, q2 = u2, sn0, cs0 = B, A, q3 = C and
+    // sn4, cs4, q4 = Y, X, Z of the record -- the registers of the values they replace)
     const __amdgpu_buffer_rsrc_t rss = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)a.scp, (short)0, (int)(BDPT_DEV_RANDP_PLANES * BDPT_DEV_RANDP_PL * 8u), 0x00020000);
+        (void*)a.scp, (short)0,
+        (int)(kSrec ? 2u * BDPT_DEV_SREC_HALF * 16u : BDPT_DEV_RANDP_PLANES * BDPT_DEV_RANDP_PL * 8u), 0x00020000);
     // BDPT_SCP_LATE (experiment): the pairs loaded at the top of their own segment instead of
     // one segment ahead with d_Rand[j..j+3] (shorter register lifetimes, less time to arrive)
     auto load_plan = [&](unsigned jj) {
-        if constexpr (kScp && BDPT_SCP_LATE) load_rand4p(rsp, jj, q0, q1, q2, q3);
+        if constexpr (kSrec) load_srec(rsp, rss, jj, cs0, sn0, q3, q2, cs4, sn4, q4, q0, q1);
+        else if constexpr (kScp && BDPT_SCP_LATE) load_rand4p(rsp, jj, q0, q1, q2, q3);
         else if constexpr (kScp) load_rand_scp(rsp, rss, jj, q0, q1, q2, q3, sn0, cs0, sn4, cs4);
         else load_rand5p(rsp, jj, q0, q1, q2, q3, q4);
     };
@@ -1290,12 +1351,15 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
                     }
                     if (isdiff || refr) {
                         // r2 = d_Rand value >= 2^-32; cos2t = 1 - X is 0 or >= 2^-24: core exact
-                        const float s1 = bdpt_sqrt_rn_core(isdiff ? q1 : cos2t);
+                        // (BDPT_SREC: sqrt(r2) is in the record; the root is the refraction's alone)
+                        float s1 = 0.f;
+                        if constexpr (!kSrec) s1 = bdpt_sqrt_rn_core(isdiff ? q1 : cos2t);
                         f3 V;
                         if (isdiff) {
                             const f3 ax = fabsf(nl.x) > .1f ? mk(0.f, 1.f, 0.f) : mk(1.f, 0.f, 0.f);
                             V = cross(ax, nl);                    // |V|^2 >= 0.01 by the choice
                         } else {
+                            if constexpr (kSrec) s1 = bdpt_sqrt_rn_core(cos2t);
                             const float kq = (float)(into ? 1 : -1) * (ddn * nnt + s1);
                             V = sub(smul(nnt, rd), smul(kq, normal));
                         }
@@ -1305,7 +1369,9 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
                             specular = false;
                             thr = mul(thr, cc);
                             diff = true;              // shadow rays: below, compacted over the wave
-                            if constexpr (kScp) rd = cosine_tail_sc(nl, U, sn0, cs0, q1, s1);
+                            // the record's {A, B, C}: cosine_tail_sc's sums on its own products
+                            if constexpr (kSrec) rd = add(add(smul(cs0, U), smul(sn0, cross(nl, U))), smul(q3, nl));
+                            else if constexpr (kScp) rd = cosine_tail_sc(nl, U, sn0, cs0, q1, s1);
                             else rd = cosine_tail<true>(nl, U, q0, q1, s1, SCT);
                         } else {
                             const float aa = nt - nc, bb = nt + nc;
@@ -1332,7 +1398,8 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
         if (__builtin_amdgcn_ballot_w64(diff) != 0) {
             f3 res = mk(0.f, 0.f, 0.f), usp = res, vsd = res, vcon = res;
             if (diff) {
-                if constexpr (kScp) usp = uniform_sphere_sc(q3, sn4, cs4);
+                if constexpr (kSrec) usp = mk(cs4, sn4, q4);
+                else if constexpr (kScp) usp = uniform_sphere_sc(q3, sn4, cs4);
                 else usp = uniform_sphere<true>(q3, q4, SCT);
             }
             const int nlights = (int)a.n_lights;
@@ -1584,7 +1651,8 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
         // same registers to wait for -- the compiler otherwise waits for every outstanding memory
         // operation there, the just-issued stores included (their loads completed long before:
         // the shading used them; the wait appeared on paths that skip the shading).
-        if constexpr (kScp) asm volatile("" ::"v"(q0), "v"(q1), "v"(q2), "v"(q3), "v"(sn0), "v"(cs0), "v"(sn4), "v"(cs4));
+        if constexpr (kSrec) asm volatile("" ::"v"(q0), "v"(q1), "v"(q2), "v"(q3), "v"(q4), "v"(sn0), "v"(cs0), "v"(sn4), "v"(cs4));
+        else if constexpr (kScp) asm volatile("" ::"v"(q0), "v"(q1), "v"(q2), "v"(q3), "v"(sn0), "v"(cs0), "v"(sn4), "v"(cs4));
         else if constexpr (STREAMS) asm volatile("" ::"v"(q0), "v"(q1), "v"(q2), "v"(q3), "v"(q4));
         if (alive) {
             if (!done && ++depth > 6) done = true;                       // :621 7-segment cap

@@ -129,4 +129,42 @@ __device__ __forceinline__ float bdpt_sqrt_rn(float x) {
 }
 #endif
 
+// One sample record: everything a path segment at table position j takes from u[0..4] =
+// d_Rand[j..j+4] that is a pure function of those entries (bdpt_kernels.hip BDPT_SREC):
+//   out[0..3] = {A, B, C, u2}: the cosine direction is (A*U + B*cross(nl, U)) + C*nl with
+//               A = cosf(2 pi u0) * sqrt(u1), B = sinf(2 pi u0) * sqrt(u1), C = sqrt(1 - u1)
+//               (cosine_tail_sc's coefficients); u2 is the Fresnel choice
+//   out[4..7] = {X, Y, Z, u0}: (X, Y, Z) = uniform_sphere_sc(u3, sinf, cosf(2 pi u4)), the NEE
+//               light sample; u0 is the camera ray's first random
+// The float operations and their order are those of cosine_tail_sc / uniform_sphere_sc on the
+// sincos_cr<true> pairs, and every root is the correctly rounded one (the device's bdpt_sqrt_rn
+// equals sqrtf for every input), so a record holds bit for bit what the path kernel computed per
+// segment before.  Host+device: tests/test_sample_records.py runs this code on the CPU (compile
+// with -ffp-contract=off, as everything here).  sintab = the 512-entry table (BDPT_SC_COARSE = 0).
+BDPT_HD void bdpt_sample_record(const float* u, const double* sintab, float* out) {
+    const float kTwoPi = 2.f * 3.14159265358979323846f;        // 2.f * kPi, formed first as in 2.f * kPi * u
+    double sd, cd;
+    bdpt_sincos_tab((double)(kTwoPi * u[0]), sintab, &sd, &cd);
+    const float s0 = (float)sd, c0 = (float)cd;
+    bdpt_sincos_tab((double)(kTwoPi * u[4]), sintab, &sd, &cd);
+    const float s4 = (float)sd, c4 = (float)cd;
+    const float zz = 1.f - 2.f * u[3];
+    const float q = 1.f - zz * zz;
+    const float qc = 0.f > q ? 0.f : q;
+    const float om = 1 - u[1];
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float r2s = bdpt_sqrt_rn(u[1]), C = bdpt_sqrt_rn(om), r = bdpt_sqrt_rn(qc);
+#else
+    const float r2s = sqrtf(u[1]), C = sqrtf(om), r = sqrtf(qc);
+#endif
+    out[0] = c0 * r2s;
+    out[1] = s0 * r2s;
+    out[2] = C;
+    out[3] = u[2];
+    out[4] = r * c4;
+    out[5] = r * s4;
+    out[6] = zz;
+    out[7] = u[0];
+}
+
 #endif

@@ -175,6 +175,11 @@ int  bdpt_last_traversal(const bdpt_ctx *ctx);
                                                new pixels of their pass, claimed in chunks)   */
 #define BDPT_FEAT_SCP       256             /* sin/cos planes: the angles' sinf/cosf loaded, not
                                                evaluated (pass streams / units, not pools)     */
+#define BDPT_FEAT_SREC      512             /* sample records: the cosine direction's coefficients
+                                               and the NEE light sample of every table position
+                                               loaded as one 32-B record, not computed per vertex
+                                               (specialised pass streams / units; set with
+                                               BDPT_FEAT_SCP, whose planes the records replace) */
 #define BDPT_FEAT_UNITS     128             /* pass streams with the ordered fold in the kernel:
                                                units of (tile, range of passes) in range order,
                                                running mean in registers, no radiance buffer   */
@@ -224,6 +229,10 @@ int  bdpt_read_radiance(bdpt_ctx *ctx, bdpt_vec *colors, unsigned *counter);
 int  bdpt_read_pixels(bdpt_ctx *ctx, unsigned char *rgba);
 int  bdpt_read_rand(bdpt_ctx *ctx, float *rand_table);          /* d_Rand, BDPT_RAND_N */
 int  bdpt_read_lightpaths(bdpt_ctx *ctx, bdpt_lightpath *lp);   /* dev_lp, 4096        */
+/* The sample records of the current table (BDPT_FEAT_SREC), built first if they are not current:
+ * 8 floats per table position j < BDPT_RAND_N - 5, {A, B, C, u2, X, Y, Z, u0} of d_Rand[j..j+4]
+ * (csrc/bdpt_math.h bdpt_sample_record), in table order -- 8 * (BDPT_RAND_N - 5) floats.  Tests. */
+int  bdpt_read_sample_records(bdpt_ctx *ctx, float *records);
 /* Upload all 4096 VLPs (the counterpart of bdpt_read_lightpaths; checkpoint restore). */
 int  bdpt_write_lightpaths(bdpt_ctx *ctx, const bdpt_lightpath *lp);
 /* The seed of the current MT607 table (current_sample * 5 of the last light pass, or the
