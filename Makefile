@@ -115,7 +115,7 @@ endif
 # plus the oracle driven against the same CPU backend.  Run by tests/test_asan.py.
 ASAN_FLAGS := -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -g -O1 -ffp-contract=off
 ASAN_DIR   := tests/native/_asan
-asan: $(ASAN_DIR)/smallpt_asan $(ASAN_DIR)/oracle_asan
+asan: $(ASAN_DIR)/smallpt_asan $(ASAN_DIR)/oracle_asan $(ASAN_DIR)/aov_asan
 
 $(ASAN_DIR):
 	mkdir -p $(ASAN_DIR)
@@ -138,6 +138,10 @@ $(ASAN_DIR)/smallpt_asan: $(ASAN_DIR)/smallpt.o $(ASAN_DIR)/bdpt_util.o $(ASAN_D
 $(ASAN_DIR)/oracle_asan: tests/native/oracle_asan.c $(ASAN_DIR)/bdpt_oracle.o $(ASAN_DIR)/bdpt_util.o $(ASAN_DIR)/bdpt_ckpt.o $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/asan_cpu_abi.o
 	g++ $(ASAN_FLAGS) -x c -std=gnu11 -c $< -o $(ASAN_DIR)/oracle_asan_main.o
 	g++ $(ASAN_FLAGS) -o $@ $(ASAN_DIR)/oracle_asan_main.o $(filter %.o,$^) -lm -pthread
+
+# the CPU backend's feature buffers (bdpt_cpu_render_aov) driven directly; tests/test_aov_asan.py
+$(ASAN_DIR)/aov_asan: tests/native/aov_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
+	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
 
 clean:
 	rm -rf $(BUILD) $(LIB) $(HOST) $(ORACLE) $(CHECKS) $(CSRC)/bdpt_jit_src.h $(ASAN_DIR)

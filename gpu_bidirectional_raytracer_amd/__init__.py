@@ -19,19 +19,22 @@ import numpy as np
 
 from ._lib import (BDPT_OK, CHOICES, COUNTER_CAP, DEFAULT_DAT, DIFF, FEATURES, KEY_DOWN, KEY_LEFT, KEY_PAGE_DOWN,
                    KEY_PAGE_UP, KEY_RIGHT, KEY_UP, LIGHT_POINTS, LITE, RAND_N, REFR, SCENE_DIR, SPEC,
-                   BdptError, Camera, LightPath, PassState, RandState, Sphere, Vec, lib)
+                   AovBuffers, BdptError, Camera, LightPath, PassState, RandState, Sphere, Vec, lib)
 
 __all__ = [
     "Vec", "Sphere", "Camera", "LightPath", "Renderer", "SmallPT", "PassScheduler", "read_scene",
     "default_scene", "update_camera", "camera_key", "sphere_key", "save_ppm", "ppm_name", "glibc_rand",
     "spheres_to_array", "RAND_N", "LIGHT_POINTS", "COUNTER_CAP", "DIFF", "SPEC", "REFR", "LITE",
-    "SCENE_DIR", "DEFAULT_DAT", "BdptError",
+    "SCENE_DIR", "DEFAULT_DAT", "BdptError", "AOV_PLANES",
 ]
 
 SPHERE_DTYPE = np.dtype([("rad", "<f4"), ("p", "<f4", 3), ("e", "<f4", 3), ("c", "<f4", 3),
                          ("refl", "<i4")])
 assert SPHERE_DTYPE.itemsize == ctypes.sizeof(Sphere)
 LIGHTPATH_DTYPE = np.dtype([("hp", "<f4", 3), ("rad", "<f4", 3), ("nl", "<f4", 3)])
+
+
+AOV_PLANES = ("id", "t", "dp", "position", "normal", "dir")     # bdpt_aov_buffers, in its order
 
 
 def _ptr(a: np.ndarray) -> ctypes.c_void_p:
@@ -416,6 +419,44 @@ class Renderer:
             lib.bdpt_get_scene(self._h, _sphere_ptr(arr), n)
         return arr
 
+    # -- first-hit feature buffers (no reference counterpart; include/bdpt.h bdpt_render_aov)
+    def render_aov(self, sid: Optional[int] = None, window: Optional[Tuple[int, int, int, int]] = None,
+                   planes: Sequence[str] = AOV_PLANES) -> dict:
+        """The first hit of every pixel's camera ray, in the path kernel's arithmetic: a dict of
+        id [h, w] int32 (-1 = miss), t, dp [h, w] float32 and position, normal, dir [h, w, 3]
+        float32.  sid=None: the unjittered pixel-centre rays (no random table needed); else the
+        jitter of a pass with that sid on the current table.  window=(x0, y0, w, h): only those
+        pixels (equal to that slice of the whole frame).  Changes nothing else of the context."""
+        x0, y0, w, h = (0, 0, self.width, self.height) if window is None else (int(v) for v in window)
+        shape = (max(h, 0), max(w, 0))
+        out = {k: np.empty(shape + ((3,) if k in ("position", "normal", "dir") else ()),
+                           np.int32 if k == "id" else np.float32) for k in AOV_PLANES if k in planes}
+        buf = AovBuffers(**{k: a.ctypes.data for k, a in out.items()})
+        self._chk(lib.bdpt_render_aov(self._h, x0, y0, w, h, int(sid is not None), int(sid or 0),
+                                      ctypes.byref(buf)))
+        return out
+
+    def pick(self, x: int, y: int, sid: Optional[int] = None) -> Tuple[int, float]:
+        """(sphere index or -1, hit distance) of the pixel (x, y): bdpt_pick, a 1x1 window."""
+        i, t = ctypes.c_int(), ctypes.c_float()
+        self._chk(lib.bdpt_pick(self._h, int(x), int(y), int(sid is not None), int(sid or 0),
+                                ctypes.byref(i), ctypes.byref(t)))
+        return i.value, t.value
+
+    @property
+    def last_aov_traversal(self) -> str:
+        """'brute' or 'bvh': what the last render_aov / pick call traversed."""
+        rc = int(lib.bdpt_last_aov_traversal(self._h))
+        if rc < 0:
+            raise BdptError(rc, "no feature buffers rendered yet")
+        return {1: "brute", 2: "bvh"}[rc]
+
+    def last_aov_ms(self) -> float:
+        """Device time (ms) of the last render_aov / pick kernel alone, without the read-back."""
+        ms = ctypes.c_float()
+        self._chk(lib.bdpt_last_aov_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
     def device_buffers(self) -> Tuple[int, int, int]:
         c, n, p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         self._chk(lib.bdpt_device_buffers(self._h, ctypes.byref(c), ctypes.byref(n), ctypes.byref(p)))
@@ -529,6 +570,17 @@ class SmallPT:
                 self.ReInitScene()
         elif camera_key(self.camera, key):
             self.ReInit(True)
+
+    def PickSphere(self, x: int, y: int) -> int:
+        """Select the sphere the pixel (x, y) shows (no reference counterpart: its only selection is
+        the '+'/'-' cycle, display_func.c:336-343).  On a hit current_sphere becomes that sphere and
+        the scene is re-initialised as the '+'/'-' handlers do; on a miss nothing changes.  Returns
+        the sphere index or -1."""
+        sphere, _ = self.renderer.pick(x, y)
+        if sphere >= 0:
+            self.current_sphere = sphere
+            self.ReInitScene()
+        return sphere
 
     def SpecialFunc(self, key: str) -> None:                 # display_func.c:384-437
         if camera_key(self.camera, key):

@@ -47,6 +47,12 @@ class Camera(ctypes.Structure):
     _fields_ = [("orig", Vec), ("target", Vec), ("dir", Vec), ("x", Vec), ("y", Vec)]
 
 
+class AovBuffers(ctypes.Structure):
+    """bdpt_aov_buffers: host pointers of the six first-hit planes, NULL = not wanted."""
+    _fields_ = [("id", ctypes.c_void_p), ("t", ctypes.c_void_p), ("dp", ctypes.c_void_p),
+                ("position", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("dir", ctypes.c_void_p)]
+
+
 class RandState(ctypes.Structure):
     _fields_ = [("state", ctypes.c_int * 31), ("f", ctypes.c_int), ("r", ctypes.c_int)]
 
@@ -114,6 +120,12 @@ _SIGS = [
     ("bdpt_get_scene", ctypes.c_int, [_P, ctypes.POINTER(Sphere), ctypes.c_uint]),
     ("bdpt_device_buffers", ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P)]),
     ("bdpt_update_pixels", ctypes.c_int, [_P]),
+    ("bdpt_render_aov", ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_uint, ctypes.POINTER(AovBuffers)]),
+    ("bdpt_pick", ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint,
+                                 ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float)]),
+    ("bdpt_last_aov_traversal", ctypes.c_int, [_P]),
+    ("bdpt_last_aov_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_gl_register_pbo", ctypes.c_int, [_P, ctypes.c_uint]),
     ("bdpt_gl_publish", ctypes.c_int, [_P]),
     ("bdpt_gl_unregister", ctypes.c_int, [_P]),

@@ -313,11 +313,10 @@ struct PathTracer {
         return 0.5f * res;
     }
 
-    V3 sample(int x, int y, int W, unsigned sid, int vlp) const {
-        const unsigned base = 26u + (unsigned)(y * W + x) * 25u;
-        const unsigned kk = (base + sid) % (kRandN - 5u);
-        const float kx = (float)(((double)((float)x * inv_w) - half_w) + (double)(rnd[kk] * inv_w));
-        const float ky = (float)(((double)((float)y * inv_h) - half_h) + (double)(rnd[kk + 1] * inv_h));
+    // the camera ray of device.cu:562-600 for pixel (x, y) with the jitter randoms u0, u1
+    void camera_ray(int x, int y, float u0, float u1, V3* o, V3* d) const {
+        const float kx = (float)(((double)((float)x * inv_w) - half_w) + (double)(u0 * inv_w));
+        const float ky = (float)(((double)((float)y * inv_h) - half_h) + (double)(u1 * inv_h));
         const float kz = 10.0f;
         V3 rdir = v3(0.f, 0.f, 0.f);
         rdir = rdir + kx * ux;
@@ -325,7 +324,15 @@ struct PathTracer {
         rdir = rdir + kz * ud;
         const float w = (tx * kx + ty * ky + tz * kz) + 1;
         rdir = (float)(1. / w) * rdir;
-        V3 o = rdir + orig, d = unit(rdir);
+        *o = rdir + orig;
+        *d = unit(rdir);
+    }
+
+    V3 sample(int x, int y, int W, unsigned sid, int vlp) const {
+        const unsigned base = 26u + (unsigned)(y * W + x) * 25u;
+        const unsigned kk = (base + sid) % (kRandN - 5u);
+        V3 o, d;
+        camera_ray(x, y, rnd[kk], rnd[kk + 1], &o, &d);
         V3 rad = v3(0.f, 0.f, 0.f), thr = v3(1.f, 1.f, 1.f);
         bool specular = true;
         const bdpt_lightpath& v = lp[vlp & (BDPT_LIGHT_POINTS - 1)];
@@ -417,6 +424,47 @@ void bdpt_cpu_path_passes(bdpt_cpu_ctx* c, const unsigned* sid, const int* vlp, 
             px[1] = (unsigned char)to_int8(col.y, c->thr);
             px[2] = (unsigned char)to_int8(col.z, c->thr);
             px[3] = 0;
+        }
+    });
+}
+
+// First-hit feature buffers (include/bdpt.h bdpt_render_aov): the first segment of the eye path of
+// sample() above on its own -- the camera ray (device.cu:562-600), IntersectDevice (:106-124) and
+// hitPoint / normal / dp (:635-643) -- for the window's pixels, packed [h][w].  The caller has
+// checked the window, the camera and (jitter) the table.
+void bdpt_cpu_render_aov(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid,
+                         const bdpt_aov_buffers* out) {
+    const PathTracer pt(c);
+    const int W = c->W;
+    parallel_rows(y0, y0 + h, c->threads, [&](int y) {
+        for (int x = x0; x < x0 + w; x++) {
+            float u0 = 0.f, u1 = 0.f;                              // no jitter: both randoms +0
+            if (jitter) {
+                const unsigned kk = (26u + (unsigned)(y * W + x) * 25u + sid) % (kRandN - 5u);   // :562
+                u0 = pt.rnd[kk];
+                u1 = pt.rnd[kk + 1];
+            }
+            V3 o, d;
+            pt.camera_ray(x, y, u0, u1, &o, &d);
+            float t = 0.f, dp = 0.f;
+            unsigned s = 0;
+            int id = -1;
+            V3 hp = v3(0.f, 0.f, 0.f), nrm = hp;
+            if (pt.sc.closest(o, d, &t, &s)) {
+                id = (int)s;
+                hp = o + t * d;
+                nrm = unit(hp - of(pt.sc.s[s].p));
+                dp = dot(nrm, d);
+            } else {
+                t = 0.f;
+            }
+            const size_t k = (size_t)(y - y0) * w + (x - x0);
+            if (out->id) out->id[k] = id;
+            if (out->t) out->t[k] = t;
+            if (out->dp) out->dp[k] = dp;
+            if (out->position) out->position[k] = {hp.x, hp.y, hp.z};
+            if (out->normal) out->normal[k] = {nrm.x, nrm.y, nrm.z};
+            if (out->dir) out->dir[k] = {d.x, d.y, d.z};
         }
     });
 }

@@ -15,6 +15,8 @@
 //   d_colors  bdpt_dev_vec[W*H]     running-mean radiance, AoS 12 B (== dev_colors)
 //   d_counter unsigned[W*H]         samples per pixel (== dev_counter)
 //   d_pixels  uchar4[W*H]           gamma-2.2 8-bit RGBA (== pixels_buf)
+//   d_aov     float[12][cap]        first-hit feature buffers (bdpt_aov_kernel): planes id, t, dp,
+//             position, normal, dir of the largest window asked for; made on first use  48 B/pixel
 #ifndef BDPT_DEVICE_H
 #define BDPT_DEVICE_H
 
@@ -129,6 +131,30 @@ struct bdpt_path_args {
     unsigned* unit_ctr;             // per XCD queue: units claimed (8 counters, 128 B apart, zeroed per launch)
     int unit_taper;                 // 1: the launch's last unit_passes passes in halving ranges
 };
+
+// First-hit feature buffers (bdpt_aov_kernel; include/bdpt.h bdpt_render_aov): the window, the
+// jitter and the output planes, packed [h][w].  The scene, the camera constants, the random table
+// and the BVH come from the bdpt_path_args the kernel also receives.
+struct bdpt_aov_args {
+    int x0, y0, w, h;               // the window inside the W x H frame (checked by the host)
+    int jitter;                     // 0: both camera randoms are +0.0f (a.rnd is not read)
+    unsigned sid;                   // kk = (26 + 25 i + sid) mod (RAND_N - 5), device.cu:562
+    int bvh;                        // 1: walls brute force + BVH (a.bvh_*), 0: the n-sphere scan
+    int rows;                       // 1: a wave covers 64 x 1 pixels, 0: 8 x 8 (below)
+    int* id;                       // sphere index, -1 = miss
+    float* t;
+    float* dp;
+    bdpt_dev_vec* position;
+    bdpt_dev_vec* normal;
+    bdpt_dev_vec* dir;
+};
+// Wave tiles of the feature-buffer kernel: 8 x 8 pixels when the BVH is traversed (coherent rays,
+// as in the path kernel), 64 x 1 for the brute scan (no divergence to contain; row-contiguous
+// stores).  A 256-thread workgroup covers 32 x 8 or 64 x 4 pixels.
+#define BDPT_AOV_BVH_BTW 32
+#define BDPT_AOV_BVH_BTH 8
+#define BDPT_AOV_ROW_BTW 64
+#define BDPT_AOV_ROW_BTH 4
 
 // Units' pass ranges: unit_passes (P) passes each, except (taper) the launch's last <= P passes,
 // which are split in halves -- P = 8: ..., 8, 4, 2, 1, 1 -- so that the launch drains over short

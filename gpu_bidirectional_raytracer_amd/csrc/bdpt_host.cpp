@@ -51,6 +51,7 @@ extern "C" __global__ void bdpt_accum_kernel(bdpt_path_args);
 extern "C" __global__ void bdpt_accum_serial_kernel(bdpt_path_args);
 
 extern "C" __global__ void bdpt_frame_add_kernel(float*, const float*, unsigned*, const unsigned*, int);
+extern "C" __global__ void bdpt_aov_kernel(bdpt_path_args, bdpt_aov_args);
 
 // gamma thresholds (host, once): see bdpt_util.c
 extern "C" void bdpt_gamma_thresholds(float thr[256]);
@@ -217,6 +218,13 @@ struct bdpt_ctx {
     char reduce_note[256] = {0};        // the RCCL version and communicator, or why RCCL is not used
     bdpt_cpu_ctx* cpu = nullptr;        // device == BDPT_DEVICE_CPU: the host backend (bdpt_cpu.cpp)
     hipGraphicsResource_t gl_res = nullptr;   // registered GL pixel-unpack buffer (bdpt_gl_register_pbo)
+    // first-hit feature buffers (bdpt_render_aov): six output planes of aov_cap pixels each in one
+    // allocation (12 words per pixel), made on the first call and grown when a window needs more
+    float* d_aov = nullptr;
+    size_t aov_cap = 0;
+    hipEvent_t aov_ev[2] = {nullptr, nullptr};   // around the kernel of the last call
+    int aov_traversal = 0;              // BDPT_TRAVERSE_* of the last call (0: none yet)
+    float aov_cpu_ms = 0.f;             // CPU backend: wall time of the last call's loop
     unsigned gl_pbo = 0;
 };
 enum { kReduceNone = 0, kReduceRccl = 1, kReducePeer = 2 };
@@ -346,9 +354,11 @@ static void release(bdpt_ctx* c) {
     void* bufs[] = {c->d_params, c->d_rand, c->d_rndp, c->d_scp, c->d_srec, c->d_lp, c->d_sph, c->d_lights, c->d_geom, c->d_lightrec, c->d_colors,
                     c->d_counter, c->d_pixels, c->d_thr, c->d_rbuf, c->d_rmask, c->d_poolctr, c->d_uflags, c->d_uerr, c->d_bvh_nodes,
                     c->d_bvh_geom, c->d_big_geom, c->d_mat, c->d_bvh_ids, c->d_big_ids,
-                    c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc};
+                    c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc, c->d_aov};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    for (hipEvent_t e : c->aov_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto& s : c->ring) {
         for (hipEvent_t e : s.kev) (void)hipEventDestroy(e);
         if (s.ev0) (void)hipEventDestroy(s.ev0);
@@ -1137,6 +1147,29 @@ static void vnorm3(float v[3]) {
     v[0] = l * v[0]; v[1] = l * v[1]; v[2] = l * v[2];
 }
 
+// The frame and camera constants of a launch (the by-value Camera of device.cu:548, as the kernels
+// take it): shared by the path passes and the feature-buffer kernel.
+static void camera_args(const bdpt_ctx* c, bdpt_path_args& a) {
+    a.W = c->W; a.H = c->H;
+    a.inv_w = (float)(14. / c->W);                       // smallpt_cpu.c:411-412
+    a.inv_h = (float)(10.5 / c->H);
+    a.half_w = (double)(a.inv_w * (float)c->W) / 2.;      // device.cu:565 inv_width*width/2.
+    a.half_h = (double)(a.inv_h * (float)c->H) / 2.;
+    const bdpt_camera& cam = c->cam;
+    float ux[3] = {cam.x.x, cam.x.y, cam.x.z}, uy[3] = {cam.y.x, cam.y.y, cam.y.z};
+    float ud[3] = {cam.dir.x, cam.dir.y, cam.dir.z};
+    vnorm3(ux); vnorm3(uy); vnorm3(ud);
+    float nx[3] = {-1.f * cam.x.x, -1.f * cam.x.y, -1.f * cam.x.z};
+    float ny[3] = {-1.f * cam.y.x, -1.f * cam.y.y, -1.f * cam.y.z};
+    float nd[3] = {-1.f * cam.dir.x, -1.f * cam.dir.y, -1.f * cam.dir.z};
+    vnorm3(nx); vnorm3(ny);                               // :584-590 (no vnorm on -dir, :591)
+    a.tx = nx[0] * cam.orig.x + nx[1] * cam.orig.y + nx[2] * cam.orig.z;
+    a.ty = ny[0] * cam.orig.x + ny[1] * cam.orig.y + ny[2] * cam.orig.z;
+    a.tz = nd[0] * cam.orig.x + nd[1] * cam.orig.y + nd[2] * cam.orig.z;
+    memcpy(a.ux, ux, sizeof(ux)); memcpy(a.uy, uy, sizeof(uy)); memcpy(a.ud, ud, sizeof(ud));
+    a.orig[0] = cam.orig.x; a.orig[1] = cam.orig.y; a.orig[2] = cam.orig.z;
+}
+
 static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int npass) {
     if (!c) return BDPT_EINVAL;
     if (npass < 0 || (npass > 0 && (!sid || !vlp))) return fail(c, BDPT_EINVAL, "bdpt_path_passes: bad pass list");
@@ -1184,24 +1217,7 @@ static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int
     a.counter = c->d_counter;
     a.pixels = c->d_pixels;
     a.gamma_thr = c->d_thr;
-    a.W = c->W; a.H = c->H;
-    a.inv_w = (float)(14. / c->W);                       // smallpt_cpu.c:411-412
-    a.inv_h = (float)(10.5 / c->H);
-    a.half_w = (double)(a.inv_w * (float)c->W) / 2.;      // device.cu:565 inv_width*width/2.
-    a.half_h = (double)(a.inv_h * (float)c->H) / 2.;
-    const bdpt_camera& cam = c->cam;
-    float ux[3] = {cam.x.x, cam.x.y, cam.x.z}, uy[3] = {cam.y.x, cam.y.y, cam.y.z};
-    float ud[3] = {cam.dir.x, cam.dir.y, cam.dir.z};
-    vnorm3(ux); vnorm3(uy); vnorm3(ud);
-    float nx[3] = {-1.f * cam.x.x, -1.f * cam.x.y, -1.f * cam.x.z};
-    float ny[3] = {-1.f * cam.y.x, -1.f * cam.y.y, -1.f * cam.y.z};
-    float nd[3] = {-1.f * cam.dir.x, -1.f * cam.dir.y, -1.f * cam.dir.z};
-    vnorm3(nx); vnorm3(ny);                               // :584-590 (no vnorm on -dir, :591)
-    a.tx = nx[0] * cam.orig.x + nx[1] * cam.orig.y + nx[2] * cam.orig.z;
-    a.ty = ny[0] * cam.orig.x + ny[1] * cam.orig.y + ny[2] * cam.orig.z;
-    a.tz = nd[0] * cam.orig.x + nd[1] * cam.orig.y + nd[2] * cam.orig.z;
-    memcpy(a.ux, ux, sizeof(ux)); memcpy(a.uy, uy, sizeof(uy)); memcpy(a.ud, ud, sizeof(ud));
-    a.orig[0] = cam.orig.x; a.orig[1] = cam.orig.y; a.orig[2] = cam.orig.z;
+    camera_args(c, a);
     a.shard = c->shard; a.nshards = c->nshards; a.band_rows = c->band_rows;
     if (!c->d_prof && getenv("BDPT_PROF")) {
         HIPCHK(c, hipMalloc(&c->d_prof, 24 * sizeof(unsigned long long)));
@@ -2226,6 +2242,122 @@ int bdpt_update_pixels(bdpt_ctx* c) {
     if (!c) return BDPT_EINVAL;
     if (!c->multi) return one_update_pixels(c);
     return assemble(c);
+}
+
+// ---- first-hit feature buffers (include/bdpt.h bdpt_render_aov) -----------------------------
+// One launch of bdpt_aov_kernel over the window on the context's stream (so it runs after the
+// table generation, light pass and scene upload queued there; it reads nothing the path passes
+// write), then the wanted planes are read back through the same stream.  Nothing of the path
+// passes' state is touched: not the accumulation, not the timing ring, not the stream choice.
+int bdpt_render_aov(bdpt_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid,
+                    const bdpt_aov_buffers* out) {
+    if (!c) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_render_aov: multi-device contexts render no feature buffers");
+    if (!out) return fail(c, BDPT_EINVAL, "bdpt_render_aov: no output buffers");
+    if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 > c->W - w || y0 > c->H - h)
+        return fail(c, BDPT_EINVAL, "bdpt_render_aov: window %d,%d %dx%d is empty or outside the %dx%d frame", x0, y0,
+                    w, h, c->W, c->H);
+    if (sid >= (unsigned)BDPT_RAND_N) return fail(c, BDPT_EINVAL, "bdpt_render_aov: sid %u >= RAND_N", sid);
+    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_render_aov: camera not set");
+    if (jitter && !c->rand_ready)
+        return fail(c, BDPT_ESTATE, "bdpt_render_aov: jitter needs a random table (run the light pass first)");
+    if (c->cpu) {
+        const auto t0 = std::chrono::steady_clock::now();
+        bdpt_cpu_render_aov(c->cpu, x0, y0, w, h, jitter, sid, out);
+        c->aov_cpu_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        c->aov_traversal = BDPT_TRAVERSE_BRUTE;
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t np = (size_t)w * (size_t)h;
+    if (np > c->aov_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));           // an earlier call's copies are done anyway
+        if (c->d_aov) HIPCHK(c, hipFree(c->d_aov));
+        c->d_aov = nullptr;
+        c->aov_cap = 0;
+        if (hipMalloc(&c->d_aov, 12 * sizeof(float) * np) != hipSuccess)
+            return fail(c, BDPT_ENOMEM, "bdpt_render_aov: output planes (%zu B)", 12 * sizeof(float) * np);
+        c->aov_cap = np;
+    }
+    for (hipEvent_t& e : c->aov_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    bdpt_path_args a;
+    memset(&a, 0, sizeof(a));
+    a.n = (unsigned)c->spheres.size();
+    a.geom = c->d_geom;
+    a.rnd = c->d_rand;
+    camera_args(c, a);
+    const bool bvh = c->has_bvh && c->traversal != BDPT_TRAVERSE_BRUTE;
+    if (bvh) {
+        a.bvh_nodes = c->d_bvh_nodes; a.bvh_geom = c->d_bvh_geom; a.bvh_ids = c->d_bvh_ids;
+        a.big_geom = c->d_big_geom; a.big_ids = c->d_big_ids;
+        a.bvh_nn = c->bvh_nn; a.bvh_ns = c->bvh_ns; a.big_n = c->big_n;
+        for (int k = 0; k < 3; k++) a.bvh_c[k] = c->bvh_c[k];
+        a.bvh_r = c->bvh_r;
+        a.bvh_q = c->bvh_q;
+    }
+    bdpt_aov_args v;
+    memset(&v, 0, sizeof(v));
+    v.x0 = x0; v.y0 = y0; v.w = w; v.h = h;
+    v.jitter = jitter != 0;
+    v.sid = sid;
+    v.bvh = bvh;
+    v.rows = !bvh;
+    if (const char* e = getenv("BDPT_AOV_TILE")) {            // experiments: 8 = 8x8 wave tiles, 64 = rows
+        if (atoi(e) == 8) v.rows = 0;
+        if (atoi(e) == 64) v.rows = 1;
+    }
+    float* base = c->d_aov;
+    v.id = (int*)base;
+    v.t = base + c->aov_cap;
+    v.dp = base + 2 * c->aov_cap;
+    v.position = (bdpt_dev_vec*)(base + 3 * c->aov_cap);
+    v.normal = (bdpt_dev_vec*)(base + 6 * c->aov_cap);
+    v.dir = (bdpt_dev_vec*)(base + 9 * c->aov_cap);
+    const int btw = v.rows ? BDPT_AOV_ROW_BTW : BDPT_AOV_BVH_BTW, bth = v.rows ? BDPT_AOV_ROW_BTH : BDPT_AOV_BVH_BTH;
+    const dim3 grid((unsigned)((w + btw - 1) / btw), (unsigned)((h + bth - 1) / bth), 1), block(256);
+    HIPCHK(c, hipEventRecord(c->aov_ev[0], c->stream));
+    hipLaunchKernelGGL(bdpt_aov_kernel, grid, block, 0, c->stream, a, v);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->aov_ev[1], c->stream));
+    c->aov_traversal = bvh ? BDPT_TRAVERSE_BVH : BDPT_TRAVERSE_BRUTE;
+    auto back = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIPCHK(c, back(out->id, v.id, sizeof(int) * np));
+    HIPCHK(c, back(out->t, v.t, sizeof(float) * np));
+    HIPCHK(c, back(out->dp, v.dp, sizeof(float) * np));
+    HIPCHK(c, back(out->position, v.position, sizeof(bdpt_vec) * np));
+    HIPCHK(c, back(out->normal, v.normal, sizeof(bdpt_vec) * np));
+    HIPCHK(c, back(out->dir, v.dir, sizeof(bdpt_vec) * np));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+int bdpt_pick(bdpt_ctx* c, int x, int y, int jitter, unsigned sid, int* id, float* t) {
+    bdpt_aov_buffers out;
+    memset(&out, 0, sizeof(out));
+    out.id = id;
+    out.t = t;
+    return bdpt_render_aov(c, x, y, 1, 1, jitter, sid, &out);
+}
+
+int bdpt_last_aov_traversal(const bdpt_ctx* c) {
+    if (!c) return BDPT_EINVAL;
+    return c->aov_traversal ? c->aov_traversal : BDPT_ESTATE;
+}
+
+int bdpt_last_aov_ms(bdpt_ctx* c, float* ms) {
+    if (!c || !ms) return BDPT_EINVAL;
+    if (!c->aov_traversal) return fail(c, BDPT_ESTATE, "bdpt_last_aov_ms: no feature buffers rendered");
+    if (c->cpu) {
+        *ms = c->aov_cpu_ms;
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(c->aov_ev[1]));
+    HIPCHK(c, hipEventElapsedTime(ms, c->aov_ev[0], c->aov_ev[1]));
+    return BDPT_OK;
 }
 
 // ---- checkpoint / resume of the accumulation ----------------------------------

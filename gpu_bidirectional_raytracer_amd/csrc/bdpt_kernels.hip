@@ -1956,4 +1956,108 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_pixels_kernel(const bdpt_
     const bdpt_dev_vec c = colors[i];
     pixels[i] = bdpt_dev_to_rgba(c.x, c.y, c.z, thr);
 }
+
+// First-hit feature buffers (include/bdpt.h bdpt_render_aov; no reference counterpart): the first
+// segment of the eye path on its own, one lane per pixel of the window -- the camera ray
+// (device.cu:562-600), the closest hit (:106-124) and hitPoint / normal / dp (:635-643), with the
+// float operations of bdpt_path_kernel_t in its order, so the planes equal what the path kernel
+// forms inside.  Nothing but the six output planes is written.
+//  * Sphere data is wave-uniform: the brute scan and the walls of a BVH scene read {p, rad^2}
+//    through the constant address space at a uniform index (scalar loads, ld_const); only the hit
+//    sphere's centre is a per-lane load.  The tree is read through L1/L2 as in the path kernel.
+//  * Wave tiles (v.rows, bdpt_device.h): 8 x 8 pixels when the BVH is traversed, so that a wave's
+//    rays walk the same nodes; 64 x 1 for the brute scan, whose loop is branch-free and the same
+//    for every lane -- there a wave's stores are whole contiguous rows of each plane (256 B of a
+//    scalar plane, 768 B of a float3 plane, instead of 8 runs of 32 / 96 B).
+//  * Tiles are anchored at the window's corner; a pixel's values depend on its frame index alone.
+extern "C" __global__ __launch_bounds__(256) void bdpt_aov_kernel(bdpt_path_args a, bdpt_aov_args v) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lx = v.rows ? (int)blockIdx.x * BDPT_AOV_ROW_BTW + lane
+                          : (int)blockIdx.x * BDPT_AOV_BVH_BTW + wave * 8 + (lane & 7);
+    const int ly = v.rows ? (int)blockIdx.y * BDPT_AOV_ROW_BTH + wave
+                          : (int)blockIdx.y * BDPT_AOV_BVH_BTH + (lane >> 3);
+    if (lx >= v.w || ly >= v.h) return;                  // (no cross-lane operation below)
+    const int x = v.x0 + lx, y = v.y0 + ly;
+    const unsigned i = (unsigned)(y * a.W + x);
+    float u0 = 0.f, u1 = 0.f;
+    if (v.jitter) {
+        const unsigned kk = (26u + i * 25u + v.sid) % (kRandN - 5u);     // kk + 1 <= RAND_N - 5
+        u0 = a.rnd[kk];
+        u1 = a.rnd[kk + 1];
+    }
+    // camera ray (:562-600), as the `fresh` branch of the path kernel forms it
+    const float kx = (float)(((double)((float)x * a.inv_w) - a.half_w) + (double)(u0 * a.inv_w));
+    const float ky = (float)(((double)((float)y * a.inv_h) - a.half_h) + (double)(u1 * a.inv_h));
+    f3 rdir = mk(0.f, 0.f, 0.f);
+    rdir = add(rdir, smul(kx, mk(a.ux[0], a.ux[1], a.ux[2])));
+    rdir = add(rdir, smul(ky, mk(a.uy[0], a.uy[1], a.uy[2])));
+    rdir = add(rdir, mk(10.0f * a.ud[0], 10.0f * a.ud[1], 10.0f * a.ud[2]));     // kz * ud
+    const float w = (a.tx * kx + a.ty * ky + a.tz * 10.0f) + 1;
+    rdir = smul(rcp_rn(w), rdir);
+    const f3 ro = add(rdir, mk(a.orig[0], a.orig[1], a.orig[2]));
+    const f3 rd = norm(rdir);
+
+    // closest hit, scanning from the last sphere down (:106-124)
+    float t = 1e20f;
+    int id = -1;
+    if (v.bvh) {
+        // walls by brute force, then the BVH; equal distances go to the higher index, which is
+        // what the reference's downward scan with `d < t` yields
+        for (int q = a.big_n - 1; q >= 0; --q) {
+            const troots h = sphere_roots(ld_const(a.big_geom, q), ro, rd);
+            const float d = h.t1 > kEps ? h.t1 : h.t2;
+            const int s = a.big_ids[q] & kBvhIdMask;
+            if (h.t2 > kEps && (d < t || (d == t && s > id))) { t = d; id = s; }
+        }
+        const bvh_ray br = bvh_setup(a, ro, rd);
+        int node = 0;
+        while (true) {                                   // while-while, as in the path kernel
+            int info = -1;
+            while (node < a.bvh_nn) {
+                const float4 lo = a.bvh_nodes[2 * node], hi = a.bvh_nodes[2 * node + 1];
+                const int inf = __float_as_int(hi.w);
+                const bool in = bvh_box(lo, hi, br, t);
+                node = (in && inf < 0) ? node + 1 : __float_as_int(lo.w);
+                if (in && inf >= 0) { info = inf; break; }
+            }
+            if (info < 0) break;
+            const int first = info & 0xffffff, end = first + (info >> 24);
+            for (int k = first; k < end; k++) {
+                const troots h = sphere_roots(a.bvh_geom[k], ro, rd);
+                const float d = h.t1 > kEps ? h.t1 : h.t2;
+                const int s = a.bvh_ids[k] & kBvhIdMask;
+                if (h.t2 > kEps && (d < t || (d == t && s > id))) { t = d; id = s; }
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int s = (int)a.n - 1; s >= 0; --s) {
+            const troots q = sphere_roots(ld_const(a.geom, s), ro, rd);
+            const float r = q.t1 > kEps ? q.t1 : q.t2;
+            if (q.t2 > kEps && r < t) { t = r; id = s; }
+        }
+    }
+
+    f3 hit = mk(0.f, 0.f, 0.f), normal = hit;            // a miss: +0 everywhere but dir
+    float dp = 0.f;
+    if (id >= 0) {
+        const float4 pc = a.geom[id];
+        hit = add(ro, smul(t, rd));                      // :635-637
+        normal = norm(sub(hit, mk(pc.x, pc.y, pc.z)));   // :639-641
+        dp = dot(normal, rd);                            // :643
+    } else {
+        t = 0.f;
+    }
+    const size_t o = (size_t)ly * (size_t)v.w + (size_t)lx;
+    v.id[o] = id;
+    v.t[o] = t;
+    v.dp[o] = dp;
+    bdpt_dev_vec ov;
+    ov.x = hit.x; ov.y = hit.y; ov.z = hit.z;
+    v.position[o] = ov;
+    ov.x = normal.x; ov.y = normal.y; ov.z = normal.z;
+    v.normal[o] = ov;
+    ov.x = rd.x; ov.y = rd.y; ov.z = rd.z;
+    v.dir[o] = ov;
+}
 #endif  // BDPT_JIT

@@ -251,6 +251,42 @@ int  bdpt_device_buffers(bdpt_ctx *ctx, void **colors, void **counter, void **pi
 /* Recompute pixels (toInt gamma) from colors on the device, e.g. after a cross-GPU reduce. */
 int  bdpt_update_pixels(bdpt_ctx *ctx);
 
+/* ---- first-hit feature buffers (AOVs) and sphere picking (no reference counterpart: the
+ * reference selects a sphere only by cycling '+'/'-', display_func.c:336-343) ----
+ * The first segment of the eye path on its own, in the path kernel's arithmetic, for the pixels
+ * (x, y) of the window [x0, x0+w) x [y0, y0+h) of the context's frame; outputs are packed [h][w].
+ *   ray    the camera ray of device.cu:562-600 with the jitter randoms d_Rand[kk], d_Rand[kk+1],
+ *          kk = (26 + 25*i + sid) % (RAND_N-5) (:562, 32-bit unsigned arithmetic), i = y*W + x the
+ *          full-frame pixel index of bdpt_read_radiance -- so a window equals the same slice of
+ *          the whole frame; jitter == 0: both randoms are +0.0f (no random table needed)
+ *   hit    IntersectDevice device.cu:106-124 (downward scan, strict `<`, EPSILON rule of :80-104);
+ *          the material plays no part: glass, mirrors and emitters are hits like any other
+ *   id     sphere index, -1 on a miss
+ *   t      hit distance along the normalised direction
+ *   position  hitPoint, device.cu:635-637
+ *   normal    the geometric normal of :639-641 (not flipped towards the ray)
+ *   dp        vdot(normal, ray.d) of :643, signed: negative = the sphere is seen from outside
+ *   dir       the normalised ray direction (also on a miss)
+ * On a miss t, dp, position and normal are +0.0f.  Pointers are host memory; NULL = not wanted.
+ * Synchronous, ordered after whatever the context has in flight, and without side effects: the
+ * accumulation, counters, pixels, random tables, VLPs, path timing, stream and kernel choices and
+ * shards are untouched, so passes rendered after the call equal passes rendered without it.
+ * bdpt_set_traversal is honoured -- BDPT_TRAVERSE_AUTO here means the BVH whenever the scene has
+ * one -- with the same result either way (on the BVH equal distances go to the higher index).
+ * BDPT_ESTATE: no camera set, or jitter != 0 before a random table exists.  BDPT_EINVAL: NULL
+ * `out`, an empty window or one outside the frame, sid >= BDPT_RAND_N, or a multi-device context
+ * (bdpt_create_multi): feature buffers are rendered by one-device contexts only. */
+typedef struct { int *id; float *t; float *dp; bdpt_vec *position, *normal, *dir; } bdpt_aov_buffers;
+int  bdpt_render_aov(bdpt_ctx *ctx, int x0, int y0, int w, int h, int jitter, unsigned sid,
+                     const bdpt_aov_buffers *out);
+/* The 1x1 window at (x, y): which sphere the pixel shows (-1: none) and how far away it is. */
+int  bdpt_pick(bdpt_ctx *ctx, int x, int y, int jitter, unsigned sid, int *id, float *t);
+/* Of the last bdpt_render_aov / bdpt_pick call: BDPT_TRAVERSE_BVH or BDPT_TRAVERSE_BRUTE, and the
+ * device time of its kernel alone (ms, HIP events around the launch, no read-back; wall time of
+ * the loop on the CPU backend).  BDPT_ESTATE before the first call. */
+int  bdpt_last_aov_traversal(const bdpt_ctx *ctx);
+int  bdpt_last_aov_ms(bdpt_ctx *ctx, float *ms);
+
 /* ---- optional display: HIP-GL interop ----
  * The caller owns the window, its OpenGL context (current on the calling thread) and a
  * pixel-unpack buffer of at least 4*W*H bytes (glGenBuffers + glBufferData(GL_PIXEL_UNPACK_BUFFER,
