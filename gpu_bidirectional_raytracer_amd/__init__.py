@@ -19,7 +19,7 @@ import numpy as np
 
 from ._lib import (BDPT_OK, CHOICES, COUNTER_CAP, DEFAULT_DAT, DIFF, FEATURES, KEY_DOWN, KEY_LEFT, KEY_PAGE_DOWN,
                    KEY_PAGE_UP, KEY_RIGHT, KEY_UP, LIGHT_POINTS, LITE, RAND_N, REFR, SCENE_DIR, SPEC,
-                   AovBuffers, BdptError, Camera, LightPath, PassState, RandState, Sphere, Vec, lib)
+                   DENOISE_MATERIALS, AovBuffers, BdptError, Camera, DenoiseParams, LightPath, PassState, RandState, Sphere, Vec, lib)
 
 __all__ = [
     "Vec", "Sphere", "Camera", "LightPath", "Renderer", "SmallPT", "PassScheduler", "read_scene",
@@ -457,6 +457,28 @@ class Renderer:
         self._chk(lib.bdpt_last_aov_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
+    # -- denoiser (no reference counterpart; include/bdpt.h bdpt_denoise)
+    def denoise(self, levels: int = 4, normal_power: int = 5, sigma_color: float = 0.5,
+                materials: str = "diffuse", pixels: bool = False):
+        """The accumulated radiance as it stands, through an edge-avoiding wavelet filter guided by
+        the unjittered first hit's sphere id and normal: `levels` a-trous levels (1..8, steps 1, 2,
+        4, ...), the normals' cosine squared `normal_power` times (0..6), colour stopping
+        1 / (1 + |dc|^2 4^k / sigma_color^2) (sigma_color > 0; inf: none).  materials="diffuse"
+        filters only pixels that show a DIFF sphere, "all" every hit; the others are copied through.
+        Returns the [H, W, 3] float32 frame, or (frame, rgba [H, W, 4] uint8 through read_pixels'
+        thresholds) with pixels=True.  Changes nothing else of the context."""
+        prm = DenoiseParams(int(levels), int(normal_power), float(sigma_color), DENOISE_MATERIALS[materials])
+        col = np.empty((self.height, self.width, 3), np.float32)
+        px = np.empty((self.height, self.width, 4), np.uint8) if pixels else None
+        self._chk(lib.bdpt_denoise(self._h, ctypes.byref(prm), _ptr(col), _ptr(px) if pixels else None))
+        return (col, px) if pixels else col
+
+    def last_denoise_ms(self) -> float:
+        """Device time (ms) of the last denoise call's kernels alone, without the read-back."""
+        ms = ctypes.c_float()
+        self._chk(lib.bdpt_last_denoise_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
     def device_buffers(self) -> Tuple[int, int, int]:
         c, n, p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         self._chk(lib.bdpt_device_buffers(self._h, ctypes.byref(c), ctypes.byref(n), ctypes.byref(p)))
@@ -624,4 +646,13 @@ class SmallPT:
         if path is None:
             path = ppm_name(self.total_time, self.current_sample)
         save_ppm(path, self.pixels(), binary)
+        return path
+
+    def SaveDenoisedPPM(self, path: Optional[str] = None, binary: bool = False, **params) -> str:
+        """SavePPM of the denoised frame (Renderer.denoise(**params)); without a path, SavePPM's
+        file name with `_denoised` before `.ppm`."""
+        if path is None:
+            path = ppm_name(self.total_time, self.current_sample)[:-len(".ppm")] + "_denoised.ppm"
+        _, px = self.renderer.denoise(pixels=True, **params)
+        save_ppm(path, px, binary)
         return path

@@ -53,6 +53,15 @@ class AovBuffers(ctypes.Structure):
                 ("position", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("dir", ctypes.c_void_p)]
 
 
+class DenoiseParams(ctypes.Structure):
+    """bdpt_denoise_params."""
+    _fields_ = [("levels", ctypes.c_int), ("normal_power", ctypes.c_int), ("sigma_color", ctypes.c_float),
+                ("materials", ctypes.c_int)]
+
+
+DENOISE_MATERIALS = {"diffuse": 0, "all": 1}               # BDPT_DENOISE_DIFFUSE / BDPT_DENOISE_ALL
+
+
 class RandState(ctypes.Structure):
     _fields_ = [("state", ctypes.c_int * 31), ("f", ctypes.c_int), ("r", ctypes.c_int)]
 
@@ -126,6 +135,8 @@ _SIGS = [
                                  ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_last_aov_traversal", ctypes.c_int, [_P]),
     ("bdpt_last_aov_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
+    ("bdpt_denoise", ctypes.c_int, [_P, ctypes.POINTER(DenoiseParams), _P, _P]),
+    ("bdpt_last_denoise_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_gl_register_pbo", ctypes.c_int, [_P, ctypes.c_uint]),
     ("bdpt_gl_publish", ctypes.c_int, [_P]),
     ("bdpt_gl_unregister", ctypes.c_int, [_P]),

@@ -469,6 +469,82 @@ void bdpt_cpu_render_aov(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, in
     });
 }
 
+// Edge-avoiding wavelet denoiser (include/bdpt.h bdpt_denoise): a plain restatement
+// of the definition there.  Guides: id and normal of the unjittered first hit (the loop above with
+// jitter = 0).  Level k filters with the 5x5 B3-spline taps at step 2^k; a tap counts when it is
+// inside the frame and shows the centre's sphere, weighted by the normals' cosine (squared
+// normal_power times) and by 1 / (1 + |dc|^2 * isc_k); ineligible pixels are copied through.
+// fp32, no contraction, in exactly this order -- the HIP kernel (bdpt_denoise_level_kernel) forms
+// the same bits.  Threaded over rows per level.  The caller has checked the parameters and the
+// camera; the context's own state is only read.
+void bdpt_cpu_denoise(const bdpt_cpu_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out,
+                      unsigned char* rgba_out) {
+    const int W = c->W, H = c->H;
+    const size_t np = (size_t)W * H;
+    std::vector<int> id(np);
+    std::vector<bdpt_vec> nrm(np);
+    bdpt_aov_buffers g;
+    memset(&g, 0, sizeof g);
+    g.id = id.data();
+    g.normal = nrm.data();
+    bdpt_cpu_render_aov(c, 0, 0, W, H, 0, 0u, &g);
+    for (size_t i = 0; i < np; i++)                       // an ineligible pixel: id -1
+        if (id[i] >= 0 && p->materials == BDPT_DENOISE_DIFFUSE && c->scene.s[id[i]].refl != BDPT_DIFF) id[i] = -1;
+    static const float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
+    const float isc0 = 1.0f / (p->sigma_color * p->sigma_color);
+    std::vector<bdpt_vec> ping(c->colors), pong(np);
+    for (int k = 0; k < p->levels; k++) {
+        const int s = 1 << k;
+        const float isc = isc0 * (float)(1 << (2 * k));
+        const bdpt_vec* cur = ping.data();
+        bdpt_vec* out = pong.data();
+        parallel_rows(0, H, c->threads, [&](int y) {
+            for (int x = 0; x < W; x++) {
+                const size_t i = (size_t)y * W + x;
+                const bdpt_vec cp = cur[i];
+                if (id[i] < 0) {
+                    out[i] = cp;
+                    continue;
+                }
+                const V3 n_p = of(nrm[i]);
+                float sw = 0.f;
+                V3 sc = v3(0.f, 0.f, 0.f);
+                for (int j = 0; j < 5; j++) {
+                    const int qy = y + (j - 2) * s;
+                    if (qy < 0 || qy >= H) continue;
+                    for (int t = 0; t < 5; t++) {
+                        const int qx = x + (t - 2) * s;
+                        if (qx < 0 || qx >= W) continue;
+                        const size_t q = (size_t)qy * W + qx;
+                        if (id[q] != id[i]) continue;
+                        const float d = dot(n_p, of(nrm[q]));
+                        float wn = d > 0.f ? d : 0.f;
+                        for (int r = 0; r < p->normal_power; r++) wn = wn * wn;
+                        const V3 cq = of(cur[q]);
+                        const V3 dc = cq - of(cp);
+                        const float e2 = dot(dc, dc);
+                        const float wc = 1.f / (1.f + e2 * isc);
+                        const float w = ((hk[j] * hk[t]) * wn) * wc;
+                        sw = sw + w;
+                        sc = sc + w * cq;
+                    }
+                }
+                const float r = 1.f / sw;
+                out[i] = {sc.x * r, sc.y * r, sc.z * r};
+            }
+        });
+        ping.swap(pong);
+    }
+    if (colors_out) memcpy(colors_out, ping.data(), sizeof(bdpt_vec) * np);
+    if (rgba_out)
+        for (size_t i = 0; i < np; i++) {
+            rgba_out[4 * i] = (unsigned char)to_int8(ping[i].x, c->thr);
+            rgba_out[4 * i + 1] = (unsigned char)to_int8(ping[i].y, c->thr);
+            rgba_out[4 * i + 2] = (unsigned char)to_int8(ping[i].z, c->thr);
+            rgba_out[4 * i + 3] = 0;
+        }
+}
+
 bool bdpt_cpu_rand_ready(const bdpt_cpu_ctx* c) { return c->rand_ready; }
 bool bdpt_cpu_camera_set(const bdpt_cpu_ctx* c) { return c->cam_set; }
 

@@ -21,6 +21,8 @@ void bdpt_cpu_light_pass(bdpt_cpu_ctx* c, int current_sample);
 void bdpt_cpu_path_passes(bdpt_cpu_ctx* c, const unsigned* sid, const int* vlp, int npass);
 void bdpt_cpu_render_aov(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid,
                          const bdpt_aov_buffers* out);
+void bdpt_cpu_denoise(const bdpt_cpu_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out,
+                      unsigned char* rgba_out);
 bool bdpt_cpu_rand_ready(const bdpt_cpu_ctx* c);
 bool bdpt_cpu_camera_set(const bdpt_cpu_ctx* c);
 void bdpt_cpu_read_radiance(const bdpt_cpu_ctx* c, bdpt_vec* colors, unsigned* counter);

@@ -17,6 +17,8 @@
 //   d_pixels  uchar4[W*H]           gamma-2.2 8-bit RGBA (== pixels_buf)
 //   d_aov     float[12][cap]        first-hit feature buffers (bdpt_aov_kernel): planes id, t, dp,
 //             position, normal, dir of the largest window asked for; made on first use  48 B/pixel
+//   d_dn      float4[3][W*H]        denoiser (bdpt_denoise): guide records {normal, id or -1}, ping and
+//             pong colours; made on the first call                                  48 B/pixel
 #ifndef BDPT_DEVICE_H
 #define BDPT_DEVICE_H
 
@@ -155,6 +157,35 @@ struct bdpt_aov_args {
 #define BDPT_AOV_BVH_BTH 8
 #define BDPT_AOV_ROW_BTW 64
 #define BDPT_AOV_ROW_BTH 4
+
+// Edge-avoiding wavelet denoiser (bdpt_denoise_pack_kernel / bdpt_denoise_level_kernel;
+// include/bdpt.h bdpt_denoise).  Context-owned, 48 B per pixel, made on the first call:
+//   guide  float4[W*H]  {normal, bits: the first hit's sphere id, or -1 for an ineligible pixel}
+//   ping / pong  float4[W*H]  the level's input / output colour in xyz (w unused)
+// One level launch reads `cur` and `guide` and writes `nxt`; the last one may write the packed
+// results instead (out3: bdpt_dev_vec[W*H], rgba: uchar4[W*H]; either may be nullptr).
+struct bdpt_denoise_args {
+    int W, H;
+    int step;                       // 2^k
+    float isc;                      // isc_0 * 4^k
+    int normal_power;               // squarings of the normal weight, 0..6
+    int rows;                       // 1: a wave covers 64 x 1 pixels, 0: 8 x 8
+    const float4* guide;
+    const float4* cur;
+    float4* nxt;                    // nullptr on a last level that only writes out3 / rgba
+    bdpt_dev_vec* out3;
+    uchar4* rgba;
+    const float* gamma_thr;
+};
+// Workgroup tiles of the level kernel, as for the feature buffers: 32 x 8 (four 8 x 8 waves) or
+// 64 x 4 (four rows).  The LDS variant stages a 32 x 8 tile plus a halo of 2 * step <= 4 pixels.
+#define BDPT_DN_BTW 32
+#define BDPT_DN_BTH 8
+#define BDPT_DN_ROW_BTW 64
+#define BDPT_DN_ROW_BTH 4
+#define BDPT_DN_LDS_MAX_STEP 2
+#define BDPT_DN_LDS_W (BDPT_DN_BTW + 4 * BDPT_DN_LDS_MAX_STEP)
+#define BDPT_DN_LDS_H (BDPT_DN_BTH + 4 * BDPT_DN_LDS_MAX_STEP)
 
 // Units' pass ranges: unit_passes (P) passes each, except (taper) the launch's last <= P passes,
 // which are split in halves -- P = 8: ..., 8, 4, 2, 1, 1 -- so that the launch drains over short

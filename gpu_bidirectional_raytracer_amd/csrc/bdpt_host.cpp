@@ -52,6 +52,9 @@ extern "C" __global__ void bdpt_accum_serial_kernel(bdpt_path_args);
 
 extern "C" __global__ void bdpt_frame_add_kernel(float*, const float*, unsigned*, const unsigned*, int);
 extern "C" __global__ void bdpt_aov_kernel(bdpt_path_args, bdpt_aov_args);
+extern "C" __global__ void bdpt_denoise_pack_kernel(const int*, const bdpt_dev_vec*, const bdpt_dev_vec*,
+                                                    const bdpt_dev_sphere*, int, float4*, float4*, int);
+extern "C" const void* bdpt_denoise_level_table[2][7];   // [LDS staging][normal_power]
 
 // gamma thresholds (host, once): see bdpt_util.c
 extern "C" void bdpt_gamma_thresholds(float thr[256]);
@@ -225,6 +228,12 @@ struct bdpt_ctx {
     hipEvent_t aov_ev[2] = {nullptr, nullptr};   // around the kernel of the last call
     int aov_traversal = 0;              // BDPT_TRAVERSE_* of the last call (0: none yet)
     float aov_cpu_ms = 0.f;             // CPU backend: wall time of the last call's loop
+    // denoiser (bdpt_denoise): guide, ping and pong records of the whole frame in one allocation
+    // (3 x 16 B per pixel), made on the first call -- the frame size never changes
+    float4* d_dn = nullptr;
+    hipEvent_t dn_ev[2] = {nullptr, nullptr};    // around the kernels of the last call
+    bool dn_ran = false;
+    float dn_cpu_ms = 0.f;              // CPU backend: wall time of the last call
     unsigned gl_pbo = 0;
 };
 enum { kReduceNone = 0, kReduceRccl = 1, kReducePeer = 2 };
@@ -354,10 +363,12 @@ static void release(bdpt_ctx* c) {
     void* bufs[] = {c->d_params, c->d_rand, c->d_rndp, c->d_scp, c->d_srec, c->d_lp, c->d_sph, c->d_lights, c->d_geom, c->d_lightrec, c->d_colors,
                     c->d_counter, c->d_pixels, c->d_thr, c->d_rbuf, c->d_rmask, c->d_poolctr, c->d_uflags, c->d_uerr, c->d_bvh_nodes,
                     c->d_bvh_geom, c->d_big_geom, c->d_mat, c->d_bvh_ids, c->d_big_ids,
-                    c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc, c->d_aov};
+                    c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc, c->d_aov, c->d_dn};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : c->aov_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->dn_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& s : c->ring) {
         for (hipEvent_t e : s.kev) (void)hipEventDestroy(e);
@@ -2249,26 +2260,11 @@ int bdpt_update_pixels(bdpt_ctx* c) {
 // table generation, light pass and scene upload queued there; it reads nothing the path passes
 // write), then the wanted planes are read back through the same stream.  Nothing of the path
 // passes' state is touched: not the accumulation, not the timing ring, not the stream choice.
-int bdpt_render_aov(bdpt_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid,
-                    const bdpt_aov_buffers* out) {
-    if (!c) return BDPT_EINVAL;
-    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_render_aov: multi-device contexts render no feature buffers");
-    if (!out) return fail(c, BDPT_EINVAL, "bdpt_render_aov: no output buffers");
-    if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 > c->W - w || y0 > c->H - h)
-        return fail(c, BDPT_EINVAL, "bdpt_render_aov: window %d,%d %dx%d is empty or outside the %dx%d frame", x0, y0,
-                    w, h, c->W, c->H);
-    if (sid >= (unsigned)BDPT_RAND_N) return fail(c, BDPT_EINVAL, "bdpt_render_aov: sid %u >= RAND_N", sid);
-    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_render_aov: camera not set");
-    if (jitter && !c->rand_ready)
-        return fail(c, BDPT_ESTATE, "bdpt_render_aov: jitter needs a random table (run the light pass first)");
-    if (c->cpu) {
-        const auto t0 = std::chrono::steady_clock::now();
-        bdpt_cpu_render_aov(c->cpu, x0, y0, w, h, jitter, sid, out);
-        c->aov_cpu_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        c->aov_traversal = BDPT_TRAVERSE_BRUTE;
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
+// Capacity of d_aov, the kernel's arguments and its launch on the context's stream (between the
+// two events, if given); the caller has checked the window, the camera and the table.  *v holds
+// the output planes on return.  Shared with bdpt_denoise, whose guides are these planes.
+static int aov_launch(bdpt_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid, bdpt_aov_args* vout,
+                      bool* bvh_out, hipEvent_t ev0, hipEvent_t ev1) {
     const size_t np = (size_t)w * (size_t)h;
     if (np > c->aov_cap) {
         HIPCHK(c, hipStreamSynchronize(c->stream));           // an earlier call's copies are done anyway
@@ -2279,8 +2275,6 @@ int bdpt_render_aov(bdpt_ctx* c, int x0, int y0, int w, int h, int jitter, unsig
             return fail(c, BDPT_ENOMEM, "bdpt_render_aov: output planes (%zu B)", 12 * sizeof(float) * np);
         c->aov_cap = np;
     }
-    for (hipEvent_t& e : c->aov_ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
     bdpt_path_args a;
     memset(&a, 0, sizeof(a));
     a.n = (unsigned)c->spheres.size();
@@ -2316,10 +2310,41 @@ int bdpt_render_aov(bdpt_ctx* c, int x0, int y0, int w, int h, int jitter, unsig
     v.dir = (bdpt_dev_vec*)(base + 9 * c->aov_cap);
     const int btw = v.rows ? BDPT_AOV_ROW_BTW : BDPT_AOV_BVH_BTW, bth = v.rows ? BDPT_AOV_ROW_BTH : BDPT_AOV_BVH_BTH;
     const dim3 grid((unsigned)((w + btw - 1) / btw), (unsigned)((h + bth - 1) / bth), 1), block(256);
-    HIPCHK(c, hipEventRecord(c->aov_ev[0], c->stream));
+    if (ev0) HIPCHK(c, hipEventRecord(ev0, c->stream));
     hipLaunchKernelGGL(bdpt_aov_kernel, grid, block, 0, c->stream, a, v);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->aov_ev[1], c->stream));
+    if (ev1) HIPCHK(c, hipEventRecord(ev1, c->stream));
+    *vout = v;
+    *bvh_out = bvh;
+    return BDPT_OK;
+}
+
+int bdpt_render_aov(bdpt_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid,
+                    const bdpt_aov_buffers* out) {
+    if (!c) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_render_aov: multi-device contexts render no feature buffers");
+    if (!out) return fail(c, BDPT_EINVAL, "bdpt_render_aov: no output buffers");
+    if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 > c->W - w || y0 > c->H - h)
+        return fail(c, BDPT_EINVAL, "bdpt_render_aov: window %d,%d %dx%d is empty or outside the %dx%d frame", x0, y0,
+                    w, h, c->W, c->H);
+    if (sid >= (unsigned)BDPT_RAND_N) return fail(c, BDPT_EINVAL, "bdpt_render_aov: sid %u >= RAND_N", sid);
+    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_render_aov: camera not set");
+    if (jitter && !c->rand_ready)
+        return fail(c, BDPT_ESTATE, "bdpt_render_aov: jitter needs a random table (run the light pass first)");
+    if (c->cpu) {
+        const auto t0 = std::chrono::steady_clock::now();
+        bdpt_cpu_render_aov(c->cpu, x0, y0, w, h, jitter, sid, out);
+        c->aov_cpu_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        c->aov_traversal = BDPT_TRAVERSE_BRUTE;
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t np = (size_t)w * (size_t)h;
+    for (hipEvent_t& e : c->aov_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    bdpt_aov_args v;
+    bool bvh = false;
+    if (int rc = aov_launch(c, x0, y0, w, h, jitter, sid, &v, &bvh, c->aov_ev[0], c->aov_ev[1])) return rc;
     c->aov_traversal = bvh ? BDPT_TRAVERSE_BVH : BDPT_TRAVERSE_BRUTE;
     auto back = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
         return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
@@ -2357,6 +2382,103 @@ int bdpt_last_aov_ms(bdpt_ctx* c, float* ms) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipEventSynchronize(c->aov_ev[1]));
     HIPCHK(c, hipEventElapsedTime(ms, c->aov_ev[0], c->aov_ev[1]));
+    return BDPT_OK;
+}
+
+// ---- edge-avoiding wavelet denoiser (include/bdpt.h bdpt_denoise) --------------
+// On the context's stream, after the last fold (the colours are the folds' output): the unjittered
+// whole-frame bdpt_aov_kernel, bdpt_denoise_pack_kernel (guide records + the first ping buffer),
+// one level kernel per level (ping-pong), the last of which writes the packed results, then the
+// read-back.  The packed results go where the feature planes were: the pack kernel has consumed
+// them, and 16 B of a pixel's 48 B there hold its float3 and its RGBA.  Only d_aov and d_dn are
+// written; nothing of the path passes' state is touched.
+int bdpt_denoise(bdpt_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out, unsigned char* rgba_out) {
+    if (!c) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_denoise: multi-device contexts are not denoised (upload the assembled frame to a one-device context)");
+    if (!p) return fail(c, BDPT_EINVAL, "bdpt_denoise: no parameters");
+    if (!colors_out && !rgba_out) return fail(c, BDPT_EINVAL, "bdpt_denoise: no output buffer");
+    if (p->levels < 1 || p->levels > 8) return fail(c, BDPT_EINVAL, "bdpt_denoise: levels %d outside 1..8", p->levels);
+    if (p->normal_power < 0 || p->normal_power > 6)
+        return fail(c, BDPT_EINVAL, "bdpt_denoise: normal_power %d outside 0..6", p->normal_power);
+    if (!(p->sigma_color > 0.f)) return fail(c, BDPT_EINVAL, "bdpt_denoise: sigma_color must be > 0");
+    if (p->materials != BDPT_DENOISE_DIFFUSE && p->materials != BDPT_DENOISE_ALL)
+        return fail(c, BDPT_EINVAL, "bdpt_denoise: materials %d", p->materials);
+    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_denoise: camera not set");
+    if (c->cpu) {
+        const auto t0 = std::chrono::steady_clock::now();
+        bdpt_cpu_denoise(c->cpu, p, colors_out, rgba_out);
+        c->dn_cpu_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        c->dn_ran = true;
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t np = (size_t)c->W * c->H;
+    if (!c->d_dn && hipMalloc(&c->d_dn, 3 * sizeof(float4) * np) != hipSuccess) {
+        c->d_dn = nullptr;
+        return fail(c, BDPT_ENOMEM, "bdpt_denoise: guide, ping and pong buffers (%zu B)", 3 * sizeof(float4) * np);
+    }
+    for (hipEvent_t& e : c->dn_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    if (int rc = join_fold(c)) return rc;
+    HIPCHK(c, hipEventRecord(c->dn_ev[0], c->stream));
+    bdpt_aov_args av;
+    bool bvh = false;
+    if (int rc = aov_launch(c, 0, 0, c->W, c->H, 0, 0u, &av, &bvh, nullptr, nullptr)) return rc;
+    float4 *guide = c->d_dn, *ping = c->d_dn + np, *pong = c->d_dn + 2 * np;
+    const dim3 block(256);
+    hipLaunchKernelGGL(bdpt_denoise_pack_kernel, dim3((unsigned)((np + 255) / 256)), block, 0, c->stream,
+                       (const int*)av.id, (const bdpt_dev_vec*)av.normal, (const bdpt_dev_vec*)c->d_colors,
+                       (const bdpt_dev_sphere*)c->d_sph, (int)(p->materials == BDPT_DENOISE_ALL), guide, ping, (int)np);
+    HIPCHK(c, hipGetLastError());
+    bdpt_dev_vec* d_out3 = (bdpt_dev_vec*)c->d_aov;           // 3 of a pixel's 12 words there
+    uchar4* d_rgba = (uchar4*)(c->d_aov + 3 * c->aov_cap);    // the 4th
+    bdpt_denoise_args v;
+    memset(&v, 0, sizeof(v));
+    v.W = c->W; v.H = c->H;
+    v.normal_power = p->normal_power;
+    v.guide = guide;
+    v.gamma_thr = c->d_thr;
+    // tile shape and LDS staging: the measured choice; the environment overrides
+    // it for experiments (BDPT_DENOISE_TILE = 8 / 64, BDPT_DENOISE_LDS = 0 / 1)
+    v.rows = 1;
+    bool lds = true;
+    if (const char* e = getenv("BDPT_DENOISE_TILE")) v.rows = atoi(e) == 64;
+    if (const char* e = getenv("BDPT_DENOISE_LDS")) lds = atoi(e) == 1;
+    const float isc0 = 1.0f / (p->sigma_color * p->sigma_color);
+    for (int k = 0; k < p->levels; k++) {
+        const bool last = k == p->levels - 1;
+        v.step = 1 << k;
+        v.isc = isc0 * (float)(1 << (2 * k));
+        v.cur = k % 2 ? pong : ping;
+        v.nxt = last ? nullptr : (k % 2 ? ping : pong);
+        v.out3 = last && colors_out ? d_out3 : nullptr;
+        v.rgba = last && rgba_out ? d_rgba : nullptr;
+        const bool staged = lds && v.step <= BDPT_DN_LDS_MAX_STEP;
+        const int btw = staged || !v.rows ? BDPT_DN_BTW : BDPT_DN_ROW_BTW;
+        const int bth = staged || !v.rows ? BDPT_DN_BTH : BDPT_DN_ROW_BTH;
+        const dim3 grid((unsigned)((c->W + btw - 1) / btw), (unsigned)((c->H + bth - 1) / bth), 1);
+        void* kargs[] = {&v};
+        HIPCHK(c, hipLaunchKernel(bdpt_denoise_level_table[staged][p->normal_power], grid, block, kargs, 0, c->stream));
+    }
+    HIPCHK(c, hipEventRecord(c->dn_ev[1], c->stream));
+    c->dn_ran = true;
+    if (colors_out)
+        HIPCHK(c, hipMemcpyAsync(colors_out, d_out3, sizeof(bdpt_vec) * np, hipMemcpyDeviceToHost, c->stream));
+    if (rgba_out) HIPCHK(c, hipMemcpyAsync(rgba_out, d_rgba, 4 * np, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return units_verdict(c);                                 // a frame known to be invalid is an error
+}
+
+int bdpt_last_denoise_ms(bdpt_ctx* c, float* ms) {
+    if (!c || !ms) return BDPT_EINVAL;
+    if (!c->dn_ran) return fail(c, BDPT_ESTATE, "bdpt_last_denoise_ms: no frame denoised");
+    if (c->cpu) {
+        *ms = c->dn_cpu_ms;
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(c->dn_ev[1]));
+    HIPCHK(c, hipEventElapsedTime(ms, c->dn_ev[0], c->dn_ev[1]));
     return BDPT_OK;
 }
 

@@ -2060,4 +2060,173 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_aov_kernel(bdpt_path_args
     ov.x = rd.x; ov.y = rd.y; ov.z = rd.z;
     v.dir[o] = ov;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Edge-avoiding wavelet denoiser (include/bdpt.h bdpt_denoise; no reference
+// counterpart).  Host sequence on the context's stream: bdpt_aov_kernel (unjittered, whole frame),
+// bdpt_denoise_pack_kernel, then one level kernel per level, ping-pong.
+//
+// Numerics: the definition in include/bdpt.h, operation for operation -- fp32, no contraction
+// (-ffp-contract=off), dot() in the order (x + y) + z, both divisions correctly rounded (rcp_rn:
+// v_rcp_f32 + one Newton step inside [2^-125, 2^125), the library division outside, e.g. for
+// 1 + e2 * isc = +inf).  Denormal intermediates are kept, not flushed: wn (a cosine squared up to
+// six times) and w underflow gradually, and the build keeps fp32 denormals (hipcc's default for
+// gfx9; the hipRTC flags of the specialised kernels say -fno-gpu-flush-denormals-to-zero
+// explicitly).  A tap that is not used adds nothing -- it is skipped, not weighted by zero.
+
+// Guide records and the first ping buffer.  gid: the first hit's sphere, or -1 where the pixel is
+// not to be filtered (a miss; with materials == DIFFUSE any sphere that is not DIFF).  Eligibility
+// is a function of the sphere, so "same sphere as an eligible centre" implies an eligible tap.
+extern "C" __global__ __launch_bounds__(256) void bdpt_denoise_pack_kernel(
+    const int* __restrict__ id, const bdpt_dev_vec* __restrict__ normal, const bdpt_dev_vec* __restrict__ colors,
+    const bdpt_dev_sphere* __restrict__ sph, int all_materials, float4* __restrict__ guide,
+    float4* __restrict__ ping, int count) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    int g = id[i];
+    if (g >= 0 && !all_materials && sph[g].refl != BDPT_DEV_DIFF) g = -1;
+    const bdpt_dev_vec n = normal[i], c = colors[i];
+    guide[i] = make_float4(n.x, n.y, n.z, __int_as_float(g));
+    ping[i] = make_float4(c.x, c.y, c.z, 0.f);
+}
+
+// 1.f / x, correctly rounded, for x >= 1 or NaN (1 + a product that is non-negative or NaN): one
+// compare decides between the in-range sequence and the library division (+inf, NaN, >= 2^125)
+__device__ __forceinline__ float rcp_rn_ge1(float x) {
+    if (__builtin_expect(!(x < 0x1p125f), 0)) return 1.f / x;
+    return rcp_rn_inrange(x);
+}
+
+// one used tap: hw = h[j] * h[i] (an exact constant), NP squarings of the normal weight
+template <int NP>
+__device__ __forceinline__ void dn_tap(float hw, float isc, f3 n_p, f3 c_p, float4 gq, float4 cq, float& sw, f3& sc) {
+    const float d = dot(n_p, mk(gq.x, gq.y, gq.z));
+    float wn = d > 0.f ? d : 0.f;
+#pragma unroll
+    for (int r = 0; r < NP; r++) wn = wn * wn;
+    const f3 q = mk(cq.x, cq.y, cq.z);
+    const f3 dc = sub(q, c_p);
+    const float e2 = dot(dc, dc);
+    const float wc = rcp_rn_ge1(1.f + e2 * isc);        // e2 >= 0 and isc >= 0, or their product is NaN
+    const float w = (hw * wn) * wc;
+    sw = sw + w;
+    sc = add(sc, smul(w, q));
+}
+
+__device__ __forceinline__ void dn_store(const bdpt_denoise_args& v, int i, f3 o) {
+    if (v.nxt) v.nxt[i] = make_float4(o.x, o.y, o.z, 0.f);
+    if (v.out3) {
+        bdpt_dev_vec ov;
+        ov.x = o.x; ov.y = o.y; ov.z = o.z;
+        v.out3[i] = ov;
+    }
+    if (v.rgba) v.rgba[i] = bdpt_dev_to_rgba(o.x, o.y, o.z, v.gamma_thr);
+}
+
+// One level, taps straight from L1 / L2: one lane per pixel, two 16-byte loads per tap (guide
+// record and colour), one 16-byte store.  Wave tiles 8 x 8 or 64 x 1
+// (v.rows), as in bdpt_aov_kernel.  The 25 taps are unrolled, j outer and i inner as defined.
+template <int NP>
+__global__ __launch_bounds__(256) void bdpt_denoise_level_t(bdpt_denoise_args v) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = v.rows ? (int)blockIdx.x * BDPT_DN_ROW_BTW + lane
+                         : (int)blockIdx.x * BDPT_DN_BTW + wave * 8 + (lane & 7);
+    const int y = v.rows ? (int)blockIdx.y * BDPT_DN_ROW_BTH + wave
+                         : (int)blockIdx.y * BDPT_DN_BTH + (lane >> 3);
+    if (x >= v.W || y >= v.H) return;                    // (no cross-lane operation below)
+    const int i = y * v.W + x;
+    const float4 gp = v.guide[i], cp4 = v.cur[i];
+    const f3 c_p = mk(cp4.x, cp4.y, cp4.z);
+    const int gid = __float_as_int(gp.w);
+    if (gid < 0) {                                       // copied through
+        dn_store(v, i, c_p);
+        return;
+    }
+    const f3 n_p = mk(gp.x, gp.y, gp.z);
+    constexpr float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
+    float sw = 0.f;
+    f3 sc = mk(0.f, 0.f, 0.f);
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        const int qy = y + (j - 2) * v.step;
+        if (qy < 0 || qy >= v.H) continue;
+        // the row's ten loads are issued together; a tap outside the frame reads the centre
+        // (always a valid address) and is not used
+        float4 gq[5], cq[5];
+        bool in[5];
+#pragma unroll
+        for (int t = 0; t < 5; t++) {
+            const int qx = x + (t - 2) * v.step;
+            in[t] = qx >= 0 && qx < v.W;
+            const int q = in[t] ? qy * v.W + qx : i;
+            gq[t] = v.guide[q];
+            cq[t] = v.cur[q];
+        }
+#pragma unroll
+        for (int t = 0; t < 5; t++)
+            if (in[t] && __float_as_int(gq[t].w) == gid)
+                dn_tap<NP>(hk[j] * hk[t], v.isc, n_p, c_p, gq[t], cq[t], sw, sc);
+    }
+    dn_store(v, i, smul(rcp_rn(sw), sc));
+}
+
+// The same level with the 32 x 8 tile and its halo of 2 * step <= 4 pixels staged in LDS (steps 1
+// and 2, where neighbouring lanes share most taps): every record of the region is loaded from
+// memory once per workgroup, coalesced, and the 25 taps are ds reads.  Positions outside the
+// frame hold the id -2, which no eligible centre has.  Kept or not by measurement: DESIGN.md 4d.
+template <int NP>
+__global__ __launch_bounds__(256) void bdpt_denoise_level_lds_t(bdpt_denoise_args v) {
+    __shared__ float4 sg[BDPT_DN_LDS_W * BDPT_DN_LDS_H], scol[BDPT_DN_LDS_W * BDPT_DN_LDS_H];
+    const int halo = 2 * v.step;                         // <= 4 (the host launches steps 1 and 2 only)
+    const int rw = BDPT_DN_BTW + 2 * halo, rh = BDPT_DN_BTH + 2 * halo;
+    const int bx0 = (int)blockIdx.x * BDPT_DN_BTW - halo, by0 = (int)blockIdx.y * BDPT_DN_BTH - halo;
+    for (int k = threadIdx.x; k < rw * rh; k += 256) {   // rw * rh <= BDPT_DN_LDS_W * BDPT_DN_LDS_H
+        const int ry = k / rw, rx = k - ry * rw;
+        const int gx = bx0 + rx, gy = by0 + ry;
+        float4 g = make_float4(0.f, 0.f, 0.f, __int_as_float(-2)), c = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (gx >= 0 && gx < v.W && gy >= 0 && gy < v.H) {
+            g = v.guide[gy * v.W + gx];
+            c = v.cur[gy * v.W + gx];
+        }
+        sg[k] = g;
+        scol[k] = c;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lx = wave * 8 + (lane & 7), ly = lane >> 3;
+    const int x = (int)blockIdx.x * BDPT_DN_BTW + lx, y = (int)blockIdx.y * BDPT_DN_BTH + ly;
+    if (x >= v.W || y >= v.H) return;
+    const int i = y * v.W + x, li = (ly + halo) * rw + lx + halo;
+    const float4 gp = sg[li], cp4 = scol[li];
+    const f3 c_p = mk(cp4.x, cp4.y, cp4.z);
+    const int gid = __float_as_int(gp.w);
+    if (gid < 0) {
+        dn_store(v, i, c_p);
+        return;
+    }
+    const f3 n_p = mk(gp.x, gp.y, gp.z);
+    constexpr float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
+    float sw = 0.f;
+    f3 sc = mk(0.f, 0.f, 0.f);
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+#pragma unroll
+        for (int t = 0; t < 5; t++) {
+            const int q = li + (j - 2) * v.step * rw + (t - 2) * v.step;
+            const float4 gq = sg[q];
+            if (__float_as_int(gq.w) != gid) continue;
+            dn_tap<NP>(hk[j] * hk[t], v.isc, n_p, c_p, gq, scol[q], sw, sc);
+        }
+    }
+    dn_store(v, i, smul(rcp_rn(sw), sc));
+}
+
+// host-side launch table: [LDS staging][normal_power]
+#define BDPT_DN(NP) (const void*)&bdpt_denoise_level_t<NP>
+#define BDPT_DNL(NP) (const void*)&bdpt_denoise_level_lds_t<NP>
+extern "C" const void* bdpt_denoise_level_table[2][7] = {
+    {BDPT_DN(0), BDPT_DN(1), BDPT_DN(2), BDPT_DN(3), BDPT_DN(4), BDPT_DN(5), BDPT_DN(6)},
+    {BDPT_DNL(0), BDPT_DNL(1), BDPT_DNL(2), BDPT_DNL(3), BDPT_DNL(4), BDPT_DNL(5), BDPT_DNL(6)}};
+#undef BDPT_DN
+#undef BDPT_DNL
 #endif  // BDPT_JIT

@@ -5,6 +5,7 @@
  *
  *   smallpt [<width> <height> <scene.scn>] [--spp N] [--batch B] [--keys KEYS] [--out F.ppm]
  *           [--device D | --gpus N | --devices D0,D1,...] [--tile ROWS] [--seed S] [--dat PATH]
+ *           [--denoise [--denoise-levels N] [--denoise-sigma S] [--denoise-all]]
  *
  * Without positional arguments the built-in CornellSpheres scene is used (smallpt_cpu.c:400).
  * Like the reference, width/height get +1 (smallpt_cpu.c:409-410).  The first frame runs the
@@ -19,6 +20,9 @@
  * --checkpoint F saves the accumulation, the pass schedule and the render state (camera, scene,
  * MT table seed, VLPs: keys may have edited them) at the end; --resume F restores all of it after
  * the first light pass, so a run continues exactly where the saved one stopped.
+ * --denoise writes --out from the denoised frame (bdpt_denoise: 4 levels, sigma 0.5, diffuse
+ * surfaces only, unless --denoise-levels / --denoise-sigma / --denoise-all say otherwise) instead
+ * of the raw pixels; one device (or the CPU, --device -1) only.
  */
 #include "smallpt_app.h"
 
@@ -31,6 +35,8 @@ int main(int argc, char **argv)
     unsigned seed = 1;
     const char *pos[3] = {0, 0, 0}, *out = NULL, *keys = "", *dat = "assets/data/MersenneTwister.dat";
     const char *ckpt = NULL, *resume = NULL;
+    int denoise = 0;
+    bdpt_denoise_params dn = {4, 5, 0.5f, BDPT_DENOISE_DIFFUSE};
     for (int a = 1; a < argc; a++) {
         if (!strcmp(argv[a], "--spp") && a + 1 < argc) spp = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--batch") && a + 1 < argc) batch = atoi(argv[++a]);
@@ -49,6 +55,10 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[a], "--seed") && a + 1 < argc) seed = (unsigned)strtoul(argv[++a], NULL, 10);
         else if (!strcmp(argv[a], "--dat") && a + 1 < argc) dat = argv[++a];
         else if (!strcmp(argv[a], "--p6")) p6 = 1;
+        else if (!strcmp(argv[a], "--denoise")) denoise = 1;
+        else if (!strcmp(argv[a], "--denoise-levels") && a + 1 < argc) dn.levels = atoi(argv[++a]);
+        else if (!strcmp(argv[a], "--denoise-sigma") && a + 1 < argc) dn.sigma_color = strtof(argv[++a], NULL);
+        else if (!strcmp(argv[a], "--denoise-all")) dn.materials = BDPT_DENOISE_ALL;
         else if (!strcmp(argv[a], "--checkpoint") && a + 1 < argc) ckpt = argv[++a];
         else if (!strcmp(argv[a], "--resume") && a + 1 < argc) resume = argv[++a];
         else if (npos < 3) pos[npos++] = argv[a];
@@ -56,6 +66,10 @@ int main(int argc, char **argv)
     }
     fprintf(stderr, "Usage: %s\n", argv[0]);
     fprintf(stderr, "Usage: %s <window width> <window height> <scene file>\n", argv[0]);
+    if (denoise && ndev) {
+        fprintf(stderr, "--denoise needs one device (--device D, or -1 for the CPU)\n");
+        return 1;
+    }
     if (npos == 3) {
         h.width = atoi(pos[0]);
         h.height = atoi(pos[1]);
@@ -125,7 +139,7 @@ int main(int argc, char **argv)
         for (int done = 0; done < spp; done += batch)
             update_rendering(&h, spp - done < batch ? spp - done : batch);
     }
-    if (out) rc = save_ppm(&h, out, p6);
+    if (out) rc = denoise ? save_denoised_ppm(&h, out, p6, &dn) : save_ppm(&h, out, p6);
     if (ckpt) {
         host_state st;
         get_state(&h, &st);

@@ -104,6 +104,20 @@ static int save_ppm(host *h, const char *path, int binary)
     return rc;
 }
 
+/* --denoise: the same file from the denoised frame's pixels (bdpt_denoise) */
+__attribute__((unused)) static int save_denoised_ppm(host *h, const char *path, int binary,
+                                                     const bdpt_denoise_params *dn)
+{
+    unsigned char *rgba = malloc(4 * (size_t)h->width * h->height);
+    int rc = rgba ? bdpt_denoise(h->ctx, dn, NULL, rgba) : BDPT_ENOMEM;
+    if (rc == BDPT_OK)
+        rc = binary ? bdpt_save_ppm_binary(path, rgba, h->width, h->height)
+                    : bdpt_save_ppm(path, rgba, h->width, h->height);
+    report(h, rc, "Denoised SavePPM");
+    free(rgba);
+    return rc;
+}
+
 /* what a checkpoint carries besides the frame: the pass schedule and the host counters */
 typedef struct {
     bdpt_pass_state ps;

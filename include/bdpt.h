@@ -287,6 +287,44 @@ int  bdpt_pick(bdpt_ctx *ctx, int x, int y, int jitter, unsigned sid, int *id, f
 int  bdpt_last_aov_traversal(const bdpt_ctx *ctx);
 int  bdpt_last_aov_ms(bdpt_ctx *ctx, float *ms);
 
+/* ---- edge-avoiding wavelet denoiser guided by the first-hit buffers (no reference counterpart:
+ * the reference shows and saves only the raw running mean, smallpt_cpu.c:239-262) ----
+ * An a-trous filter over the context's accumulated radiance (what bdpt_read_radiance returns) as
+ * it stands when the call runs, after whatever is queued on the context.  Guides: id and normal of
+ * the unjittered first hit (bdpt_render_aov with jitter = 0, whole frame).  Pixel (x, y) is frame
+ * index y*W + x.  fp32, no contraction, in the order written; the GPU, the CPU backend and the
+ * tests' numpy statement form the same bits.
+ *   eligible   BDPT_DENOISE_DIFFUSE: id >= 0 and spheres[id].refl == BDPT_DIFF; BDPT_DENOISE_ALL:
+ *              id >= 0.  Ineligible pixels (misses; by default mirrors, glass, LITE emitters, whose
+ *              first hit says nothing about what they show) are copied through at every level.
+ *   level k    = 0 .. levels-1, step s = 2^k, h = (1/16, 1/4, 3/8, 1/4, 1/16),
+ *              isc_k = (1.0f / (sigma_color * sigma_color)) * (float)4^k.  For an eligible centre p:
+ *              sw = +0, sc = (+0, +0, +0); for j = 0..4 (dy = (j-2) s), for i = 0..4 (dx = (i-2) s),
+ *              a tap q inside the frame with id[q] == id[p] adds
+ *                d  = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z
+ *                wn = max(d, 0), then wn = wn*wn normal_power times
+ *                dc = cur[q] - cur[p];  e2 = (dc.x*dc.x + dc.y*dc.y) + dc.z*dc.z
+ *                wc = 1 / (1 + e2*isc_k);  w = ((h[j]*h[i]) * wn) * wc
+ *                sw = sw + w;  sc = sc + w*cur[q]
+ *              and out = sc * (1/sw) (both divisions correctly rounded).  Level k+1 reads level k.
+ *              Denormal intermediates are kept, not flushed; non-finite radiance is not special.
+ *   levels 1..8, normal_power 0..6, sigma_color > 0 (+inf: no colour stopping).
+ * colors_out: W*H denoised colours; rgba_out: 4*W*H bytes, the denoised frame through the toInt
+ * thresholds and alpha of bdpt_read_pixels.  Either may be NULL, not both.  Synchronous; writes
+ * nothing but its own buffers: accumulation, counters, pixels, tables, VLPs, path timing, the auto
+ * stream mode's measurements and shards are untouched.  It filters the frame buffer as it stands:
+ * a sharded caller uploads the assembled frame with bdpt_write_radiance first.
+ * BDPT_EINVAL: NULL or out-of-range parameters, both outputs NULL, or a multi-device context
+ * (bdpt_create_multi).  BDPT_ESTATE: no camera set. */
+#define BDPT_DENOISE_DIFFUSE 0
+#define BDPT_DENOISE_ALL     1
+typedef struct { int levels; int normal_power; float sigma_color; int materials; } bdpt_denoise_params;
+int  bdpt_denoise(bdpt_ctx *ctx, const bdpt_denoise_params *params, bdpt_vec *colors_out,
+                  unsigned char *rgba_out);
+/* Device time (ms) of the last bdpt_denoise call's kernels alone (HIP events around the guide, pack
+ * and level launches, no read-back; wall time on the CPU backend).  BDPT_ESTATE before any call. */
+int  bdpt_last_denoise_ms(bdpt_ctx *ctx, float *ms);
+
 /* ---- optional display: HIP-GL interop ----
  * The caller owns the window, its OpenGL context (current on the calling thread) and a
  * pixel-unpack buffer of at least 4*W*H bytes (glGenBuffers + glBufferData(GL_PIXEL_UNPACK_BUFFER,
