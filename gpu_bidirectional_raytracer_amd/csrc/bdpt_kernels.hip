@@ -1157,8 +1157,12 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
     if constexpr (kPair) load_next(j);
     if constexpr (kParkPf) load_cam(j);
     f3 ro = mk(0.f, 0.f, 0.f), rd = ro, thr = ro, rad = ro, nl = ro;
-    bool specular = true, fresh = true, parked = false, want = kPool && !active;
+    bool specular = true, fresh = true, parked = false;
     bool alive = active && nslot > 0 && cnt0 + (unsigned)(kUnits ? k : s0 + k * S) < BDPT_DEV_COUNTER_CAP;
+    // a pool lane draws again when its first pixel gives it nothing to render: no pixel there, or
+    // one already at the counter cap for this pass.  (It must: a wave whose 64 first pixels are all
+    // at the cap still owns the rest of its chunk, and nobody else renders those pixels.)
+    bool want = kPool && !alive;
 
     // (a pool lane without a pixel yet keeps the loop going: it draws one at the iteration's end)
     BDPT_CNTN(14, 1);
