@@ -670,7 +670,7 @@ static hipFunction_t jit_path_kernel_build(bdpt_ctx* c, bool streams, bool pair,
     const std::string name = "&bdpt_path_kernel_t<" + std::to_string(n) + (streams ? ", true>" : ", false>");
     const char* jflags = getenv("BDPT_JIT_FLAGS");
     const bool user_coarse = jflags && strstr(jflags, "BDPT_SC_COARSE");   // experiments decide
-    bool coarse = false;
+    bool coarse = false, pf_off = false;
     for (;; waves--) {
         const std::vector<std::string> opts = {
             "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
@@ -691,6 +691,13 @@ static hipFunction_t jit_path_kernel_build(bdpt_ctx* c, bool streams, bool pair,
         for (unsigned k = 1; k <= 3; k++)
             if ((1u << k) <= c->n_vac && (c->n_vac + (1u << k) - 1) >> k < (n + (1u << k) - 1) >> k) vac_list = true;
         if (!vac_list) all.push_back("-DBDPT_VAC_LIST=0");
+        // Part-full shadow rounds as straight-line code (bdpt_kernels.hip BDPT_PF_UNROLL, on by
+        // default in these builds; BDPT_JIT_FLAGS below sets it either way): not in the pixel-pool
+        // build, which has not been measured with it, and not where the build with it spills at
+        // more than 5 waves/SIMD (pf_off, below: the bodies change the register allocation of the
+        // whole loop, and the in-kernel fold build of synthetic64 then needs scratch at 6)
+        const bool pf_user = jflags && strstr(jflags, "BDPT_PF_UNROLL");
+        if (!pf_user && ((streams && pool) || pf_off)) all.push_back("-DBDPT_PF_UNROLL=0");
         if (const char* extra = getenv("BDPT_JIT_FLAGS")) {    // experiments: extra -D options
             std::string tok;
             for (const char* q = extra;; q++) {
@@ -727,6 +734,13 @@ static hipFunction_t jit_path_kernel_build(bdpt_ctx* c, bool streams, bool pair,
         if (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, fn) != hipSuccess) {
             (void)hipGetLastError();
             scratch = 0;
+        }
+        // a build that spills above the floor is tried once more at the same wave count with the
+        // lane-group loop in place of the straight-line part-full rounds
+        if (scratch != 0 && waves > 5 && !pf_off && !pf_user && !(streams && pool) && !getenv("BDPT_JIT_SCRATCH_OK")) {
+            pf_off = true;
+            waves++;
+            continue;
         }
         // spill-free, or the 5-wave floor (BDPT_JIT_SCRATCH_OK: keep a spilling build; experiments)
         if (scratch == 0 || waves <= 5 || getenv("BDPT_JIT_SCRATCH_OK")) {

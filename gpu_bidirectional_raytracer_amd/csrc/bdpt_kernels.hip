@@ -290,6 +290,24 @@ __device__ __forceinline__ f3 cosine_tail(f3 w, f3 u, float u_phi, float u_r2, f
 #define BDPT_VAC_LIST 0
 #endif
 #endif
+// Part-full rounds as straight-line code (scene-specialised builds; pf_round below): one body per
+// group count and list, unrolled over its ceil(nl / 2^lg) iterations, instead of the per-lane
+// loop.  A (list, lg) pair that would take more than BDPT_PF_MAX_IT iterations keeps the loop
+// (synthetic64 at lg <= 2: 16 and 32 iterations, 0.5 and 1 KB of code each for rounds that its
+// 64-ray steps rarely leave).
+#ifndef BDPT_PF_UNROLL
+#ifdef BDPT_JIT
+#define BDPT_PF_UNROLL 1
+#else
+#define BDPT_PF_UNROLL 0
+#endif
+#endif
+#ifndef BDPT_PF_MAX_IT
+#define BDPT_PF_MAX_IT 8
+#endif
+#ifdef BDPT_JIT
+constexpr int kJitNLights = __builtin_popcountll(kJitEmis);      // bdpt_host.cpp upload_scene lights
+#endif
 
 // Fused S = 1 kernel: a lane whose path ends parks until at least BDPT_REGEN_K lanes of its wave
 // (or all of its live lanes) are parked; then they start their next passes together, so the
@@ -646,6 +664,76 @@ __device__ __forceinline__ void unroll_down(F& f) {
         if (f(S)) unroll_down<S - 1>(f);
     }
 }
+
+#if defined(BDPT_JIT) && BDPT_PF_UNROLL
+// A part-full shadow round of c <= 64 >> LG rays (queue entries q0[r] = {o, maxt}, q1[r] = {d,
+// vacuum}) against the list GL[0..NL) as straight-line code: ray r is traced by the lanes r,
+// r + (64 >> LG), ... (groups g = 0 .. 2^LG - 1), and group g tests the spheres g, g + 2^LG, ...
+// in ceil(NL / 2^LG) iterations, through one LDS base per lane and immediate offsets (the groups
+// split the list as in the lane-group loop, counted from its other end so that the base is
+// &GL[g]).  Only the last iteration can pass the list's end; its read then stays inside the
+// workgroup's tables (at most 31 entries on, and the 1024-entry shadow queues follow them) and its
+// result is masked.  Occlusion is accumulated without a per-lane exit: each test is the loop's
+// float sequence (sphere_roots, the key test), and an OR does not depend on the order or on how
+// far a lane went.  EMIS: the list holds the emitters (every sphere; mixed rounds), which a vacuum
+// ray (VLP) ignores: the emitter mask of the lane's spheres is kJitEmis >> g, and an iteration
+// whose 2^LG candidate spheres hold no emitter has no test for it.  Returns the rays' occlusion
+// bits.
+constexpr int pf_iters(int nl, int lg) { return (nl + (1 << lg) - 1) >> lg; }
+// lists that reach lg under BDPT_LG_RULE's reduction (2^(lg - 1) < nl; with the older rule every
+// such list too) and fit the bound
+constexpr bool pf_fits(int nl, int lg) { return (1 << (lg - 1)) < nl && pf_iters(nl, lg) <= BDPT_PF_MAX_IT; }
+constexpr int kJitNVac = BDPT_JIT_N - kJitNLights;                // bdpt_host.cpp upload_scene n_vac
+template <int LG, int NL, bool EMIS>
+__device__ __forceinline__ unsigned long long pf_round(const float4* GL, const float4* q0, const float4* q1,
+                                                       int lane, int c) {
+    constexpr int kStep = 1 << LG, kIt = pf_iters(NL, LG), kRpg = 64 >> LG;
+    static_assert(NL >= 1 && NL <= 64 && kIt >= 1, "list");
+    // the lane's ray and group are formed here, every round: left visible as functions of the
+    // lane alone, every body's indices and LDS addresses are hoisted out of the path loop and
+    // held in registers throughout (23 VGPRs spilled at 6 waves)
+    asm volatile("" : "+v"(lane));
+    const int r = lane & (kRpg - 1), g = lane >> (6 - LG);
+    bool occ = false;
+    if (r < c) {
+        const float4 r0 = q0[r], r1 = q1[r];
+        const f3 o = mk(r0.x, r0.y, r0.z), d = mk(r1.x, r1.y, r1.z);
+        const float4* gp = GL + g;
+        // the emitters among the lane's spheres, for a vacuum ray (bit i * kStep: iteration i)
+        unsigned long long em = 0;
+        if constexpr (EMIS) {
+            if constexpr (NL <= 32) em = r1.w != 0.f ? (unsigned)kJitEmis >> g : 0u;
+            else em = r1.w != 0.f ? kJitEmis >> g : 0ull;
+        }
+#if BDPT_IKEY
+        const unsigned km = maxt_key(r0.w);
+#endif
+#pragma unroll
+        for (int i = 0; i < kIt; i++) {
+            // one sphere in flight at a time (left free, the scheduler issues every iteration's
+            // read up front: 4 registers each through the round, 16 VGPRs spilled at 6 waves)
+            const float4 gc = gp[i * kStep];
+            __builtin_amdgcn_sched_barrier(0);
+            const troots q = sphere_roots(gc, o, d);
+#if BDPT_IKEY
+            bool h = umin2(key_of(q.t1), key_of(q.t2)) < km;
+#else
+            const float rr = q.t1 > kEps ? q.t1 : q.t2;
+            bool h = q.t2 > kEps && rr < r0.w;
+#endif
+            // the iteration's candidates are the spheres i * kStep .. i * kStep + kStep - 1
+            if (EMIS && ((kJitEmis >> (i * kStep)) & ((1ull << kStep) - 1ull)) != 0ull)
+                h = h && !((em >> (i * kStep)) & 1ull);
+            if (i == kIt - 1 && kIt * kStep > NL) h = h && g < NL - (kIt - 1) * kStep;
+            occ |= h;
+        }
+    }
+    unsigned long long m = __builtin_amdgcn_ballot_w64(occ);
+#pragma unroll
+    for (int w = 32; w >= kRpg; w >>= 1) m |= m >> w;
+    return m;
+}
+#endif
 
 // Handover between the units of a tile (BDPT_UNITS): agent-scope relaxed atomics are coherent
 // across XCDs (sc1 loads / stores on gfx950, no L2 invalidation); the producer waits for its data
@@ -1410,6 +1498,8 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
             // the emitters' NEE records {p, rad}, {e, (4*pi*rad)*rad} (bdpt_host.cpp upload_scene)
             // through the constant address space (folding them into the specialised build freed
             // 8 VGPRs but issued 2.5 % more VALU instructions: cornell -1 to -2 % at 5..8 waves)
+            // (loaded once before the path loop instead, 8 SGPRs for cornell's one emitter, the
+            // specialised pass-stream build spills 4 VGPRs at 6 waves)
             auto lrec = [&](int k) -> float4 { return ld_const(a.lightrec, k); };
             const int nsteps = nlights > 0 ? nlights : 1;
             for (int li = 0; li < nsteps; li++) {                         // uniform
@@ -1521,6 +1611,34 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
 #endif
                         if (lg > 0) {
                             BDPT_CNTN(8, 1);
+                            unsigned long long m;
+#if defined(BDPT_JIT) && BDPT_PF_UNROLL
+                            // straight-line bodies (pf_round), one per group count the list can
+                            // have (BDPT_LG_RULE: 2^(lg - 1) < nl) and at most BDPT_PF_MAX_IT
+                            // iterations long, picked by the uniform lg; other rounds: the loop
+                            bool unrolled = false;
+                            if constexpr (N == BDPT_JIT_N) {
+#define BDPT_PF_CASE(L)                                                                                   \
+    case L:                                                                                               \
+        if (allvac) {                                                                                     \
+            if constexpr (BDPT_VAC_LIST && !kPool && pf_fits(kJitNVac, L)) {                              \
+                m = pf_round<L, kJitNVac, false>(GV, SQ + base, SQ + kQueue + base, lane, c);             \
+                unrolled = true;                                                                          \
+            }                                                                                             \
+        } else if constexpr (pf_fits(N, L)) {                                                             \
+            BDPT_CNTN(16, pf_iters(N, L));                                                                \
+            m = pf_round<L, N, true>(G, SQ + base, SQ + kQueue + base, lane, c);                          \
+            unrolled = true;                                                                              \
+        }                                                                                                 \
+        break;
+                                switch (lg) {
+                                    BDPT_PF_CASE(1) BDPT_PF_CASE(2) BDPT_PF_CASE(3) BDPT_PF_CASE(4) BDPT_PF_CASE(5)
+                                }
+#undef BDPT_PF_CASE
+                            }
+                            if (!unrolled)
+#endif
+                            {
                             const int rpg = 64 >> lg;
                             const int r = lane & (rpg - 1), g = lane >> (6 - lg);
                             unsigned occ = 0;
@@ -1553,8 +1671,9 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
 #endif
                                 }
                             }
-                            unsigned long long m = __builtin_amdgcn_ballot_w64(occ != 0);
+                            m = __builtin_amdgcn_ballot_w64(occ != 0);
                             for (int w = 32; w >= rpg; w >>= 1) m |= m >> w;   // uniform
+                            }
                             if (lane < c) SQ[base + lane].w = __uint_as_float((unsigned)(m >> lane) & 1u);
                             continue;
                         }
@@ -1809,15 +1928,20 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
 #endif
     if constexpr (kUnits) {
         // the unit's result, then this wave tile's flag: the next range's unit may start
+        // (the pixel index is formed again from the packed coordinates, as for the pass-stream
+        // store above: kept from the prologue it is the value that spills at the 80-VGPR bound)
+        unsigned xyv = xy;
+        asm volatile("" : "+v"(xyv));
+        const int iu = active ? (int)(xyv >> 16) * a.W + (int)(xyv & 0xffffu) : 0;
         if (active && k > 0) {
-            st_coherent(&a.colors[i].x, col.x);
-            st_coherent(&a.colors[i].y, col.y);
-            st_coherent(&a.colors[i].z, col.z);
-            __hip_atomic_store(&a.counter[i], cnt0 + (unsigned)k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            st_coherent(&a.colors[iu].x, col.x);
+            st_coherent(&a.colors[iu].y, col.y);
+            st_coherent(&a.colors[iu].z, col.z);
+            __hip_atomic_store(&a.counter[iu], cnt0 + (unsigned)k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         // pixels once, by the launch's last range: plain stores of several units (on several XCDs,
         // each with its own write-back L2) would reach memory in no defined order
-        if (active && s0 + nslot >= a.npass) a.pixels[i] = bdpt_dev_to_rgba(col.x, col.y, col.z, a.gamma_thr);
+        if (active && s0 + nslot >= a.npass) a.pixels[iu] = bdpt_dev_to_rgba(col.x, col.y, col.z, a.gamma_thr);
 #if BDPT_UNITS_FENCE
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
 #else
