@@ -115,7 +115,7 @@ endif
 # plus the oracle driven against the same CPU backend.  Run by tests/test_asan.py.
 ASAN_FLAGS := -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -g -O1 -ffp-contract=off
 ASAN_DIR   := tests/native/_asan
-asan: $(ASAN_DIR)/smallpt_asan $(ASAN_DIR)/oracle_asan $(ASAN_DIR)/aov_asan $(ASAN_DIR)/denoise_asan
+asan: $(ASAN_DIR)/smallpt_asan $(ASAN_DIR)/oracle_asan $(ASAN_DIR)/aov_asan $(ASAN_DIR)/denoise_asan $(ASAN_DIR)/reproject_asan
 
 $(ASAN_DIR):
 	mkdir -p $(ASAN_DIR)
@@ -126,8 +126,9 @@ $(ASAN_DIR)/%.o: $(CSRC)/%.c include/bdpt.h | $(ASAN_DIR)
 $(ASAN_DIR)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h | $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -std=c++17 -c $< -o $@
 
-# (asan_cpu_abi_denoise.cpp = asan_cpu_abi.cpp + the bdpt_denoise entry point smallpt --denoise calls)
-$(ASAN_DIR)/asan_cpu_abi.o: tests/native/asan_cpu_abi_denoise.cpp tests/native/asan_cpu_abi.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h | $(ASAN_DIR)
+# (asan_cpu_abi_denoise.cpp = asan_cpu_abi.cpp + the bdpt_denoise entry point smallpt --denoise calls;
+# asan_cpu_abi_reproject.cpp = that + the history entry points smallpt --reproject calls)
+$(ASAN_DIR)/asan_cpu_abi.o: tests/native/asan_cpu_abi_reproject.cpp tests/native/asan_cpu_abi_denoise.cpp tests/native/asan_cpu_abi.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h | $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -std=c++17 -c $< -o $@
 
 $(ASAN_DIR)/bdpt_oracle.o: oracle/bdpt_oracle.c include/bdpt.h | $(ASAN_DIR)
@@ -146,6 +147,10 @@ $(ASAN_DIR)/aov_asan: tests/native/aov_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.
 
 # the CPU backend's denoiser (bdpt_cpu_denoise) driven directly; tests/test_denoise_asan.py
 $(ASAN_DIR)/denoise_asan: tests/native/denoise_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
+	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
+
+# the CPU backend's history and reprojection driven directly; tests/test_reproject_asan.py
+$(ASAN_DIR)/reproject_asan: tests/native/reproject_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
 	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
 
 clean:

@@ -19,7 +19,8 @@ import numpy as np
 
 from ._lib import (BDPT_OK, CHOICES, COUNTER_CAP, DEFAULT_DAT, DIFF, FEATURES, KEY_DOWN, KEY_LEFT, KEY_PAGE_DOWN,
                    KEY_PAGE_UP, KEY_RIGHT, KEY_UP, LIGHT_POINTS, LITE, RAND_N, REFR, SCENE_DIR, SPEC,
-                   DENOISE_MATERIALS, AovBuffers, BdptError, Camera, DenoiseParams, LightPath, PassState, RandState, Sphere, Vec, lib)
+                   DENOISE_MATERIALS, AovBuffers, BdptError, Camera, DenoiseParams, LightPath, PassState, RandState,
+                   ReprojectParams, Sphere, Vec, lib)
 
 __all__ = [
     "Vec", "Sphere", "Camera", "LightPath", "Renderer", "SmallPT", "PassScheduler", "read_scene",
@@ -479,6 +480,68 @@ class Renderer:
         self._chk(lib.bdpt_last_denoise_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
+    # -- temporal reprojection (no reference counterpart; include/bdpt.h bdpt_reproject)
+    @staticmethod
+    def _reproject_params(max_history: float = 64.0, plane_tol: float = 0.01, materials: str = "diffuse"):
+        return ReprojectParams(DENOISE_MATERIALS[materials], float(max_history), float(plane_tol))
+
+    def history_capture(self, **params) -> None:
+        """Take the frame as it stands (blended with the history present, if any, as reproject()
+        would) as the new history under the current camera and scene.  Call it before the camera
+        changes.  Parameters as for reproject()."""
+        prm = self._reproject_params(**params)
+        self._chk(lib.bdpt_history_capture(self._h, ctypes.byref(prm)))
+
+    def history_clear(self) -> None:
+        self._chk(lib.bdpt_history_clear(self._h))
+
+    def history_info(self) -> Tuple[bool, Optional[Camera]]:
+        """(present, camera): whether a history is stored and the scene is still the one it was
+        taken under, and the camera of the stored history (None if none was ever stored)."""
+        present, cam = ctypes.c_int(-1), Camera()
+        cam.orig.x = float("nan")
+        self._chk(lib.bdpt_history_info(self._h, ctypes.byref(present), ctypes.byref(cam)))
+        return bool(present.value), (None if cam.orig.x != cam.orig.x else cam)
+
+    def history_read(self) -> Tuple[np.ndarray, np.ndarray]:
+        """The stored history's colours [H, W, 3] float32 and weights [H, W] float32."""
+        col = np.empty((self.height, self.width, 3), np.float32)
+        w = np.empty((self.height, self.width), np.float32)
+        self._chk(lib.bdpt_history_read(self._h, _ptr(col), _ptr(w)))
+        return col, w
+
+    def history_write(self, camera: Camera, colors, weight) -> None:
+        """Upload a history: colours and per-pixel weights taken under `camera` and the current
+        scene (its guides are rendered here)."""
+        col = np.ascontiguousarray(colors, np.float32).reshape(self.height, self.width, 3)
+        w = np.ascontiguousarray(weight, np.float32).reshape(self.height, self.width)
+        self._chk(lib.bdpt_history_write(self._h, ctypes.byref(camera), _ptr(col), _ptr(w)))
+
+    def reproject(self, max_history: float = 64.0, plane_tol: float = 0.01, materials: str = "diffuse",
+                  weight: bool = False, pixels: bool = False):
+        """The preview after a camera move: the accumulated radiance as it stands, blended by sample
+        count with the history fetched where the old view showed the same surface (the pixel's first
+        hit projected into the history's camera, four bilinear taps validated by sphere id and a
+        plane test of plane_tol x hit distance, each tap's weight capped at max_history).
+        materials="diffuse" takes history only on DIFF spheres.  Returns the [H, W, 3] float32 frame,
+        followed by the [H, W] float32 blended sample count with weight=True and by the rgba
+        [H, W, 4] uint8 (read_pixels' thresholds) with pixels=True.  Changes nothing else of the
+        context; without a history it returns read_radiance()."""
+        prm = self._reproject_params(max_history, plane_tol, materials)
+        col = np.empty((self.height, self.width, 3), np.float32)
+        w = np.empty((self.height, self.width), np.float32) if weight else None
+        px = np.empty((self.height, self.width, 4), np.uint8) if pixels else None
+        self._chk(lib.bdpt_reproject(self._h, ctypes.byref(prm), _ptr(col), _ptr(w) if weight else None,
+                                     _ptr(px) if pixels else None))
+        out = (col,) + ((w,) if weight else ()) + ((px,) if pixels else ())
+        return out if len(out) > 1 else col
+
+    def last_reproject_ms(self) -> float:
+        """Device time (ms) of the last reproject / history_capture call's kernels alone."""
+        ms = ctypes.c_float()
+        self._chk(lib.bdpt_last_reproject_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
     def device_buffers(self) -> Tuple[int, int, int]:
         c, n, p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         self._chk(lib.bdpt_device_buffers(self._h, ctypes.byref(c), ctypes.byref(n), ctypes.byref(p)))
@@ -508,7 +571,11 @@ class SmallPT:
     """
 
     def __init__(self, width: Optional[int] = None, height: Optional[int] = None,
-                 scene: Optional[str] = None, device: int = 0, dat_path: str = DEFAULT_DAT):
+                 scene: Optional[str] = None, device: int = 0, dat_path: str = DEFAULT_DAT,
+                 reuse_history: bool = False):
+        # reuse_history: camera keys capture the frame before ReInit discards it, so that preview()
+        # can reproject it into the new view (Renderer.reproject); the render path is unchanged
+        self.reuse_history = bool(reuse_history)
         if scene is not None:
             self.camera, self.spheres = read_scene(scene)
             self.width, self.height = int(width), int(height)
@@ -577,6 +644,8 @@ class SmallPT:
         self.UpdateRendering(1)
 
     def ReInitScene(self) -> None:                           # smallpt_cpu.c:365-371
+        if self.reuse_history:                                # a moved sphere changes the lighting everywhere
+            self.renderer.history_clear()
         self.current_sample = 0
         self.sched.state.flag = 1
         self.AllocateBuffers()
@@ -591,6 +660,8 @@ class SmallPT:
             if sphere_key(self.spheres, self.current_sphere, key):
                 self.ReInitScene()
         elif camera_key(self.camera, key):
+            if self.reuse_history:                            # the context still holds the old camera
+                self.renderer.history_capture()
             self.ReInit(True)
 
     def PickSphere(self, x: int, y: int) -> int:
@@ -606,6 +677,8 @@ class SmallPT:
 
     def SpecialFunc(self, key: str) -> None:                 # display_func.c:384-437
         if camera_key(self.camera, key):
+            if self.reuse_history:
+                self.renderer.history_capture()
             self.ReInit(True)
 
     def colors(self) -> Tuple[np.ndarray, np.ndarray]:
@@ -654,5 +727,19 @@ class SmallPT:
         if path is None:
             path = ppm_name(self.total_time, self.current_sample)[:-len(".ppm")] + "_denoised.ppm"
         _, px = self.renderer.denoise(pixels=True, **params)
+        save_ppm(path, px, binary)
+        return path
+
+    def preview(self, **params):
+        """The frame with the last view's history reprojected into it (Renderer.reproject(**params));
+        with reuse_history=False there is no history and this is the raw frame."""
+        return self.renderer.reproject(**params)
+
+    def SavePreviewPPM(self, path: Optional[str] = None, binary: bool = False, **params) -> str:
+        """SavePPM of the preview's pixels; without a path, SavePPM's file name with `_preview`
+        before `.ppm`."""
+        if path is None:
+            path = ppm_name(self.total_time, self.current_sample)[:-len(".ppm")] + "_preview.ppm"
+        px = self.renderer.reproject(pixels=True, **params)[-1]
         save_ppm(path, px, binary)
         return path

@@ -62,6 +62,11 @@ class DenoiseParams(ctypes.Structure):
 DENOISE_MATERIALS = {"diffuse": 0, "all": 1}               # BDPT_DENOISE_DIFFUSE / BDPT_DENOISE_ALL
 
 
+class ReprojectParams(ctypes.Structure):
+    """bdpt_reproject_params."""
+    _fields_ = [("materials", ctypes.c_int), ("max_history", ctypes.c_float), ("plane_tol", ctypes.c_float)]
+
+
 class RandState(ctypes.Structure):
     _fields_ = [("state", ctypes.c_int * 31), ("f", ctypes.c_int), ("r", ctypes.c_int)]
 
@@ -137,6 +142,13 @@ _SIGS = [
     ("bdpt_last_aov_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_denoise", ctypes.c_int, [_P, ctypes.POINTER(DenoiseParams), _P, _P]),
     ("bdpt_last_denoise_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
+    ("bdpt_history_capture", ctypes.c_int, [_P, ctypes.POINTER(ReprojectParams)]),
+    ("bdpt_history_clear", ctypes.c_int, [_P]),
+    ("bdpt_history_info", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(Camera)]),
+    ("bdpt_history_read", ctypes.c_int, [_P, _P, _P]),
+    ("bdpt_history_write", ctypes.c_int, [_P, ctypes.POINTER(Camera), _P, _P]),
+    ("bdpt_reproject", ctypes.c_int, [_P, ctypes.POINTER(ReprojectParams), _P, _P, _P]),
+    ("bdpt_last_reproject_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_gl_register_pbo", ctypes.c_int, [_P, ctypes.c_uint]),
     ("bdpt_gl_publish", ctypes.c_int, [_P]),
     ("bdpt_gl_unregister", ctypes.c_int, [_P]),

@@ -155,6 +155,14 @@ struct bdpt_cpu_ctx {
     float thr[256];
     int shard = 0, nshards = 1, band_rows = 8;
     int threads = 1;
+    // history of bdpt_reproject (include/bdpt.h): colour, weight and guides per pixel under hcam
+    // and the spheres hsph; has_hist says that one is stored
+    bool has_hist = false;
+    bdpt_camera hcam{};
+    std::vector<bdpt_sphere> hsph;
+    std::vector<bdpt_vec> hc, gpos;
+    std::vector<float> hm;
+    std::vector<int> gid;
 };
 
 extern "C" void bdpt_gamma_thresholds(float thr[256]);
@@ -269,8 +277,9 @@ struct PathTracer {
     float tx, ty, tz, inv_w, inv_h;
     double half_w, half_h;
 
-    PathTracer(const bdpt_cpu_ctx* c) : sc(c->scene), rnd(c->rnd.data()), lp(c->lp.data()) {
-        const bdpt_camera& cm = c->cam;
+    PathTracer(const bdpt_cpu_ctx* c) : PathTracer(c, c->cam) {}
+    // under a camera other than the context's (the history's, bdpt_cpu_history_write)
+    PathTracer(const bdpt_cpu_ctx* c, const bdpt_camera& cm) : sc(c->scene), rnd(c->rnd.data()), lp(c->lp.data()) {
         ux = unit(of(cm.x)); uy = unit(of(cm.y)); ud = unit(of(cm.dir)); orig = of(cm.orig);
         tx = dot(unit(-1.f * of(cm.x)), orig);
         ty = dot(unit(-1.f * of(cm.y)), orig);
@@ -432,9 +441,9 @@ void bdpt_cpu_path_passes(bdpt_cpu_ctx* c, const unsigned* sid, const int* vlp, 
 // sample() above on its own -- the camera ray (device.cu:562-600), IntersectDevice (:106-124) and
 // hitPoint / normal / dp (:635-643) -- for the window's pixels, packed [h][w].  The caller has
 // checked the window, the camera and (jitter) the table.
-void bdpt_cpu_render_aov(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid,
-                         const bdpt_aov_buffers* out) {
-    const PathTracer pt(c);
+static void render_aov_cam(const bdpt_cpu_ctx* c, const bdpt_camera& cam, int x0, int y0, int w, int h, int jitter,
+                           unsigned sid, const bdpt_aov_buffers* out) {
+    const PathTracer pt(c, cam);
     const int W = c->W;
     parallel_rows(y0, y0 + h, c->threads, [&](int y) {
         for (int x = x0; x < x0 + w; x++) {
@@ -467,6 +476,11 @@ void bdpt_cpu_render_aov(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, in
             if (out->dir) out->dir[k] = {d.x, d.y, d.z};
         }
     });
+}
+
+void bdpt_cpu_render_aov(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid,
+                         const bdpt_aov_buffers* out) {
+    render_aov_cam(c, c->cam, x0, y0, w, h, jitter, sid, out);
 }
 
 // Edge-avoiding wavelet denoiser (include/bdpt.h bdpt_denoise): a plain restatement
@@ -543,6 +557,164 @@ void bdpt_cpu_denoise(const bdpt_cpu_ctx* c, const bdpt_denoise_params* p, bdpt_
             rgba_out[4 * i + 2] = (unsigned char)to_int8(ping[i].z, c->thr);
             rgba_out[4 * i + 3] = 0;
         }
+}
+
+// Temporal reprojection (include/bdpt.h bdpt_reproject): a plain restatement of the
+// definition there -- the current camera's unjittered first hit, its point projected into the
+// history's camera, four validated bilinear taps, the blend by sample count.  fp32, no
+// contraction, in exactly this order; the HIP kernel (bdpt_reproject_kernel) forms the same bits.
+bool bdpt_cpu_history_present(const bdpt_cpu_ctx* c) {
+    return c->has_hist && c->hsph.size() == c->scene.s.size() &&
+           memcmp(c->hsph.data(), c->scene.s.data(), sizeof(bdpt_sphere) * c->hsph.size()) == 0;
+}
+bool bdpt_cpu_history_stored(const bdpt_cpu_ctx* c, bdpt_camera* cam) {
+    if (c->has_hist && cam) *cam = c->hcam;
+    return c->has_hist;
+}
+void bdpt_cpu_history_clear(bdpt_cpu_ctx* c) { c->has_hist = false; }
+void bdpt_cpu_history_read(const bdpt_cpu_ctx* c, bdpt_vec* colors, float* weight) {
+    if (colors) memcpy(colors, c->hc.data(), sizeof(bdpt_vec) * c->hc.size());
+    if (weight) memcpy(weight, c->hm.data(), sizeof(float) * c->hm.size());
+}
+
+namespace {
+// id, t, position and normal of the unjittered whole-frame first hit under `cam`
+struct FirstHit {
+    std::vector<int> id;
+    std::vector<float> t;
+    std::vector<bdpt_vec> pos, nrm;
+    FirstHit(const bdpt_cpu_ctx* c, const bdpt_camera& cam, bool guides_only) {
+        const size_t np = (size_t)c->W * c->H;
+        id.resize(np);
+        pos.resize(np);
+        bdpt_aov_buffers g;
+        memset(&g, 0, sizeof g);
+        g.id = id.data();
+        g.position = pos.data();
+        if (!guides_only) {
+            t.resize(np);
+            nrm.resize(np);
+            g.t = t.data();
+            g.normal = nrm.data();
+        }
+        render_aov_cam(c, cam, 0, 0, c->W, c->H, 0, 0u, &g);
+    }
+};
+
+// (out, weight_out) of the whole frame from the history present, if any
+void reproject_frame(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, const FirstHit& f,
+                     std::vector<bdpt_vec>& out, std::vector<float>& wout) {
+    const int W = c->W, H = c->H;
+    const bool present = bdpt_cpu_history_present(c);
+    const bdpt_camera& c0 = c->hcam;
+    const V3 ux = unit(of(c0.x)), uy = unit(of(c0.y)), ud = unit(of(c0.dir)), o = of(c0.orig);
+    const float inv_w = (float)(14. / W), inv_h = (float)(10.5 / H);
+    const float hw = (float)((double)(inv_w * (float)W) / 2.), hh = (float)((double)(inv_h * (float)H) / 2.);
+    const float sx = 1.f / inv_w, sy = 1.f / inv_h;
+    parallel_rows(0, H, c->threads, [&](int y) {
+        for (int x = 0; x < W; x++) {
+            const size_t i = (size_t)y * W + x;
+            const V3 col = of(c->colors[i]);
+            const float n = (float)c->counter[i];
+            const int id1 = f.id[i];
+            float m = 0.f;
+            V3 h = v3(0.f, 0.f, 0.f);
+            if (present && id1 >= 0 && (p->materials == BDPT_DENOISE_ALL || c->scene.s[id1].refl == BDPT_DIFF)) {
+                const V3 P = of(f.pos[i]), N = of(f.nrm[i]);
+                const V3 v = P - o;
+                const float a = dot(v, ux), b = dot(v, uy), cz = dot(v, ud);
+                const float r = 1.f / cz;
+                const float kx = (10.f * a) * r, ky = (10.f * b) * r;
+                const float fx = (kx + hw) * sx, fy = (ky + hh) * sy;
+                if (fx >= -1.f && fx < (float)W && fy >= -1.f && fy < (float)H) {
+                    const float xf = floorf(fx), yf = floorf(fy);
+                    const float wx = fx - xf, wy = fy - yf;
+                    const int qx0 = (int)xf, qy0 = (int)yf;
+                    const float lim = p->plane_tol * f.t[i];
+                    float sw = 0.f, sm = 0.f;
+                    V3 sc = v3(0.f, 0.f, 0.f);
+                    bool used = false;
+                    for (int dy = 0; dy < 2; dy++)
+                        for (int dx = 0; dx < 2; dx++) {
+                            const int qx = qx0 + dx, qy = qy0 + dy;
+                            const float bx = dx ? wx : 1.f - wx, by = dy ? wy : 1.f - wy;
+                            const float bw = bx * by;
+                            if (qx < 0 || qx >= W || qy < 0 || qy >= H || !(bw > 0.f)) continue;
+                            const size_t q = (size_t)qy * W + qx;
+                            if (c->gid[q] != id1 || !(c->hm[q] > 0.f)) continue;
+                            if (!(fabsf(dot(of(c->gpos[q]) - P, N)) <= lim)) continue;
+                            sw = sw + bw;
+                            sm = sm + bw * fminf(c->hm[q], p->max_history);
+                            sc = sc + bw * of(c->hc[q]);
+                            used = true;
+                        }
+                    if (used) {
+                        h = (1.f / sw) * sc;
+                        m = sm;
+                    }
+                }
+            }
+            const float tot = n + m;
+            V3 res = col;
+            if (m == 0.f) {
+            } else if (n == 0.f) {
+                res = h;
+            } else {
+                const float rt = 1.f / tot;
+                res = v3((n * col.x + m * h.x) * rt, (n * col.y + m * h.y) * rt, (n * col.z + m * h.z) * rt);
+            }
+            out[i] = {res.x, res.y, res.z};
+            wout[i] = tot;
+        }
+    });
+}
+}  // namespace
+
+void bdpt_cpu_reproject(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, bdpt_vec* colors_out,
+                        float* weight_out, unsigned char* rgba_out) {
+    const size_t np = (size_t)c->W * c->H;
+    const FirstHit f(c, c->cam, false);
+    std::vector<bdpt_vec> out(np);
+    std::vector<float> w(np);
+    reproject_frame(c, p, f, out, w);
+    if (colors_out) memcpy(colors_out, out.data(), sizeof(bdpt_vec) * np);
+    if (weight_out) memcpy(weight_out, w.data(), sizeof(float) * np);
+    if (rgba_out)
+        for (size_t i = 0; i < np; i++) {
+            rgba_out[4 * i] = (unsigned char)to_int8(out[i].x, c->thr);
+            rgba_out[4 * i + 1] = (unsigned char)to_int8(out[i].y, c->thr);
+            rgba_out[4 * i + 2] = (unsigned char)to_int8(out[i].z, c->thr);
+            rgba_out[4 * i + 3] = 0;
+        }
+}
+
+// The new history is formed in buffers of its own while the old one is read, then swapped in; its
+// guides are the first hit the reprojection has just used (the current camera becomes C0).
+void bdpt_cpu_history_capture(bdpt_cpu_ctx* c, const bdpt_reproject_params* p) {
+    const size_t np = (size_t)c->W * c->H;
+    FirstHit f(c, c->cam, false);
+    std::vector<bdpt_vec> out(np);
+    std::vector<float> w(np);
+    reproject_frame(c, p, f, out, w);
+    c->hc.swap(out);
+    c->hm.swap(w);
+    c->gid.swap(f.id);
+    c->gpos.swap(f.pos);
+    c->hcam = c->cam;
+    c->hsph = c->scene.s;
+    c->has_hist = true;
+}
+
+void bdpt_cpu_history_write(bdpt_cpu_ctx* c, const bdpt_camera* cam, const bdpt_vec* colors, const float* weight) {
+    const size_t np = (size_t)c->W * c->H;
+    FirstHit f(c, *cam, true);
+    c->hc.assign(colors, colors + np);
+    c->hm.assign(weight, weight + np);
+    c->gid.swap(f.id);
+    c->gpos.swap(f.pos);
+    c->hcam = *cam;
+    c->hsph = c->scene.s;
+    c->has_hist = true;
 }
 
 bool bdpt_cpu_rand_ready(const bdpt_cpu_ctx* c) { return c->rand_ready; }

@@ -23,6 +23,15 @@ void bdpt_cpu_render_aov(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, in
                          const bdpt_aov_buffers* out);
 void bdpt_cpu_denoise(const bdpt_cpu_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out,
                       unsigned char* rgba_out);
+// temporal reprojection (include/bdpt.h bdpt_reproject); the caller has checked parameters and camera
+bool bdpt_cpu_history_present(const bdpt_cpu_ctx* c);                       // stored and the scene unchanged
+bool bdpt_cpu_history_stored(const bdpt_cpu_ctx* c, bdpt_camera* cam);     // stored at all; *cam = C0 then
+void bdpt_cpu_history_clear(bdpt_cpu_ctx* c);
+void bdpt_cpu_history_read(const bdpt_cpu_ctx* c, bdpt_vec* colors, float* weight);
+void bdpt_cpu_history_write(bdpt_cpu_ctx* c, const bdpt_camera* cam, const bdpt_vec* colors, const float* weight);
+void bdpt_cpu_history_capture(bdpt_cpu_ctx* c, const bdpt_reproject_params* p);
+void bdpt_cpu_reproject(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, bdpt_vec* colors_out,
+                        float* weight_out, unsigned char* rgba_out);
 bool bdpt_cpu_rand_ready(const bdpt_cpu_ctx* c);
 bool bdpt_cpu_camera_set(const bdpt_cpu_ctx* c);
 void bdpt_cpu_read_radiance(const bdpt_cpu_ctx* c, bdpt_vec* colors, unsigned* counter);

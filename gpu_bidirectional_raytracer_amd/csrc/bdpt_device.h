@@ -19,6 +19,8 @@
 //             position, normal, dir of the largest window asked for; made on first use  48 B/pixel
 //   d_dn      float4[3][W*H]        denoiser (bdpt_denoise): guide records {normal, id or -1}, ping and
 //             pong colours; made on the first call                                  48 B/pixel
+//   d_hist    float4[4][W*H] + 20 B/pixel  reprojection (bdpt_reproject): two sets of history records
+//             {gpos, gid}, {hc, hm} and the packed results; made on first use        84 B/pixel
 #ifndef BDPT_DEVICE_H
 #define BDPT_DEVICE_H
 
@@ -186,6 +188,40 @@ struct bdpt_denoise_args {
 #define BDPT_DN_LDS_MAX_STEP 2
 #define BDPT_DN_LDS_W (BDPT_DN_BTW + 4 * BDPT_DN_LDS_MAX_STEP)
 #define BDPT_DN_LDS_H (BDPT_DN_BTH + 4 * BDPT_DN_LDS_MAX_STEP)
+
+// Temporal reprojection (bdpt_history_pack_kernel / bdpt_reproject_kernel; include/bdpt.h
+// bdpt_reproject).  Context-owned history, made on first use: two sets (ping-pong: a capture reads
+// one and writes the other) of
+//   guide  float4[W*H]  {gpos, bits: gid}   position and sphere id of C0's unjittered first hit
+//   col    float4[W*H]  {hc, hm}            colour and weight
+// = 2 x 32 B per pixel, plus the packed results of a call (out3 12 B, weight 4 B, rgba 4 B).
+// The current view's first hit comes from the planes bdpt_aov_kernel has just written.
+struct bdpt_reproject_args {
+    int W, H;
+    int rows;                       // 1: a wave covers 64 x 1 pixels, 0: 8 x 8
+    int all_materials;              // 0: only pixels showing a DIFF sphere take history
+    float max_history, plane_tol;
+    float ux[3], uy[3], ud[3], o[3];   // C0 (camera_args of the history's camera)
+    float hw, hh, sx, sy;
+    const int* id;                  // the current camera's first hit (d_aov planes)
+    const float* t;
+    const bdpt_dev_vec* position;
+    const bdpt_dev_vec* normal;
+    const bdpt_dev_sphere* sph;
+    const bdpt_dev_vec* colors;
+    const unsigned* counter;
+    const float4* hguide;           // nullptr: no history present (out = colors, weight = counter)
+    const float4* hcol;
+    float4* next;                   // capture: the next history's {colour, weight} records
+    bdpt_dev_vec* out3;             // any of these may be nullptr
+    float* weight;
+    uchar4* rgba;
+    const float* gamma_thr;
+};
+#define BDPT_RP_BTW 32
+#define BDPT_RP_BTH 8
+#define BDPT_RP_ROW_BTW 64
+#define BDPT_RP_ROW_BTH 4
 
 // Units' pass ranges: unit_passes (P) passes each, except (taper) the launch's last <= P passes,
 // which are split in halves -- P = 8: ..., 8, 4, 2, 1, 1 -- so that the launch drains over short

@@ -55,6 +55,9 @@ extern "C" __global__ void bdpt_aov_kernel(bdpt_path_args, bdpt_aov_args);
 extern "C" __global__ void bdpt_denoise_pack_kernel(const int*, const bdpt_dev_vec*, const bdpt_dev_vec*,
                                                     const bdpt_dev_sphere*, int, float4*, float4*, int);
 extern "C" const void* bdpt_denoise_level_table[2][7];   // [LDS staging][normal_power]
+extern "C" __global__ void bdpt_history_pack_kernel(const int*, const bdpt_dev_vec*, const bdpt_dev_vec*,
+                                                    const float*, float4*, float4*, int);
+extern "C" __global__ void bdpt_reproject_kernel(bdpt_reproject_args);
 
 // gamma thresholds (host, once): see bdpt_util.c
 extern "C" void bdpt_gamma_thresholds(float thr[256]);
@@ -234,6 +237,17 @@ struct bdpt_ctx {
     hipEvent_t dn_ev[2] = {nullptr, nullptr};    // around the kernels of the last call
     bool dn_ran = false;
     float dn_cpu_ms = 0.f;              // CPU backend: wall time of the last call
+    // temporal reprojection (bdpt_reproject): two sets of {guide, colour + weight} records
+    // (2 x 32 B per pixel; set hist_cur is the history, a capture writes the other) and the packed
+    // results of a call (12 + 4 + 4 B per pixel) in one allocation, made on first use
+    float4* d_hist = nullptr;
+    int hist_cur = 0;
+    bool has_hist = false;              // a history is stored (under hist_cam / hist_spheres)
+    bdpt_camera hist_cam{};
+    std::vector<bdpt_sphere> hist_spheres;
+    hipEvent_t rp_ev[2] = {nullptr, nullptr};    // around the kernels of the last capture / reprojection
+    bool rp_ran = false;
+    float rp_cpu_ms = 0.f;              // CPU backend: wall time of the last call
     unsigned gl_pbo = 0;
 };
 enum { kReduceNone = 0, kReduceRccl = 1, kReducePeer = 2 };
@@ -363,12 +377,14 @@ static void release(bdpt_ctx* c) {
     void* bufs[] = {c->d_params, c->d_rand, c->d_rndp, c->d_scp, c->d_srec, c->d_lp, c->d_sph, c->d_lights, c->d_geom, c->d_lightrec, c->d_colors,
                     c->d_counter, c->d_pixels, c->d_thr, c->d_rbuf, c->d_rmask, c->d_poolctr, c->d_uflags, c->d_uerr, c->d_bvh_nodes,
                     c->d_bvh_geom, c->d_big_geom, c->d_mat, c->d_bvh_ids, c->d_big_ids,
-                    c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc, c->d_aov, c->d_dn};
+                    c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc, c->d_aov, c->d_dn, c->d_hist};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : c->aov_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->dn_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->rp_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& s : c->ring) {
         for (hipEvent_t e : s.kev) (void)hipEventDestroy(e);
@@ -1174,13 +1190,12 @@ static void vnorm3(float v[3]) {
 
 // The frame and camera constants of a launch (the by-value Camera of device.cu:548, as the kernels
 // take it): shared by the path passes and the feature-buffer kernel.
-static void camera_args(const bdpt_ctx* c, bdpt_path_args& a) {
+static void camera_args(const bdpt_ctx* c, const bdpt_camera& cam, bdpt_path_args& a) {
     a.W = c->W; a.H = c->H;
     a.inv_w = (float)(14. / c->W);                       // smallpt_cpu.c:411-412
     a.inv_h = (float)(10.5 / c->H);
     a.half_w = (double)(a.inv_w * (float)c->W) / 2.;      // device.cu:565 inv_width*width/2.
     a.half_h = (double)(a.inv_h * (float)c->H) / 2.;
-    const bdpt_camera& cam = c->cam;
     float ux[3] = {cam.x.x, cam.x.y, cam.x.z}, uy[3] = {cam.y.x, cam.y.y, cam.y.z};
     float ud[3] = {cam.dir.x, cam.dir.y, cam.dir.z};
     vnorm3(ux); vnorm3(uy); vnorm3(ud);
@@ -1194,6 +1209,7 @@ static void camera_args(const bdpt_ctx* c, bdpt_path_args& a) {
     memcpy(a.ux, ux, sizeof(ux)); memcpy(a.uy, uy, sizeof(uy)); memcpy(a.ud, ud, sizeof(ud));
     a.orig[0] = cam.orig.x; a.orig[1] = cam.orig.y; a.orig[2] = cam.orig.z;
 }
+static void camera_args(const bdpt_ctx* c, bdpt_path_args& a) { camera_args(c, c->cam, a); }
 
 static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int npass) {
     if (!c) return BDPT_EINVAL;
@@ -2277,8 +2293,8 @@ int bdpt_update_pixels(bdpt_ctx* c) {
 // Capacity of d_aov, the kernel's arguments and its launch on the context's stream (between the
 // two events, if given); the caller has checked the window, the camera and the table.  *v holds
 // the output planes on return.  Shared with bdpt_denoise, whose guides are these planes.
-static int aov_launch(bdpt_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid, bdpt_aov_args* vout,
-                      bool* bvh_out, hipEvent_t ev0, hipEvent_t ev1) {
+static int aov_launch(bdpt_ctx* c, const bdpt_camera& cam, int x0, int y0, int w, int h, int jitter, unsigned sid,
+                      bdpt_aov_args* vout, bool* bvh_out, hipEvent_t ev0, hipEvent_t ev1) {
     const size_t np = (size_t)w * (size_t)h;
     if (np > c->aov_cap) {
         HIPCHK(c, hipStreamSynchronize(c->stream));           // an earlier call's copies are done anyway
@@ -2294,7 +2310,7 @@ static int aov_launch(bdpt_ctx* c, int x0, int y0, int w, int h, int jitter, uns
     a.n = (unsigned)c->spheres.size();
     a.geom = c->d_geom;
     a.rnd = c->d_rand;
-    camera_args(c, a);
+    camera_args(c, cam, a);
     const bool bvh = c->has_bvh && c->traversal != BDPT_TRAVERSE_BRUTE;
     if (bvh) {
         a.bvh_nodes = c->d_bvh_nodes; a.bvh_geom = c->d_bvh_geom; a.bvh_ids = c->d_bvh_ids;
@@ -2358,7 +2374,7 @@ int bdpt_render_aov(bdpt_ctx* c, int x0, int y0, int w, int h, int jitter, unsig
         if (!e) HIPCHK(c, hipEventCreate(&e));
     bdpt_aov_args v;
     bool bvh = false;
-    if (int rc = aov_launch(c, x0, y0, w, h, jitter, sid, &v, &bvh, c->aov_ev[0], c->aov_ev[1])) return rc;
+    if (int rc = aov_launch(c, c->cam, x0, y0, w, h, jitter, sid, &v, &bvh, c->aov_ev[0], c->aov_ev[1])) return rc;
     c->aov_traversal = bvh ? BDPT_TRAVERSE_BVH : BDPT_TRAVERSE_BRUTE;
     auto back = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
         return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
@@ -2437,7 +2453,7 @@ int bdpt_denoise(bdpt_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out
     HIPCHK(c, hipEventRecord(c->dn_ev[0], c->stream));
     bdpt_aov_args av;
     bool bvh = false;
-    if (int rc = aov_launch(c, 0, 0, c->W, c->H, 0, 0u, &av, &bvh, nullptr, nullptr)) return rc;
+    if (int rc = aov_launch(c, c->cam, 0, 0, c->W, c->H, 0, 0u, &av, &bvh, nullptr, nullptr)) return rc;
     float4 *guide = c->d_dn, *ping = c->d_dn + np, *pong = c->d_dn + 2 * np;
     const dim3 block(256);
     hipLaunchKernelGGL(bdpt_denoise_pack_kernel, dim3((unsigned)((np + 255) / 256)), block, 0, c->stream,
@@ -2493,6 +2509,227 @@ int bdpt_last_denoise_ms(bdpt_ctx* c, float* ms) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipEventSynchronize(c->dn_ev[1]));
     HIPCHK(c, hipEventElapsedTime(ms, c->dn_ev[0], c->dn_ev[1]));
+    return BDPT_OK;
+}
+
+// ---- temporal reprojection (include/bdpt.h bdpt_reproject) ---------------------
+// On the context's stream, after the last fold: the unjittered whole-frame bdpt_aov_kernel under
+// the current camera, (capture) bdpt_history_pack_kernel writing the next history's guide records
+// from its planes, then bdpt_reproject_kernel, which reads the history's records and writes the
+// packed results or the next history's colour records; then the read-back.  Only d_aov and d_hist
+// are written; nothing of the path passes' state is touched.
+static bool hist_present(const bdpt_ctx* c) {
+    if (c->cpu) return bdpt_cpu_history_present(c->cpu);
+    return c->has_hist && c->hist_spheres.size() == c->spheres.size() &&
+           memcmp(c->hist_spheres.data(), c->spheres.data(), sizeof(bdpt_sphere) * c->spheres.size()) == 0;
+}
+
+static int rp_check(bdpt_ctx* c, const bdpt_reproject_params* p, const char* who) {
+    if (c->multi) return fail(c, BDPT_EINVAL, "%s: multi-device contexts keep no history", who);
+    if (!p) return fail(c, BDPT_EINVAL, "%s: no parameters", who);
+    if (p->materials != BDPT_DENOISE_DIFFUSE && p->materials != BDPT_DENOISE_ALL)
+        return fail(c, BDPT_EINVAL, "%s: materials %d", who, p->materials);
+    if (!(p->max_history > 0.f)) return fail(c, BDPT_EINVAL, "%s: max_history must be > 0", who);
+    if (!(p->plane_tol >= 0.f)) return fail(c, BDPT_EINVAL, "%s: plane_tol must be >= 0", who);
+    return BDPT_OK;
+}
+
+// d_hist: float4[4][np] (set s: guide at 2 s, colour + weight at 2 s + 1), then out3, weight, rgba
+struct hist_bufs {
+    float4 *guide[2], *col[2];
+    bdpt_dev_vec* out3;
+    float* weight;
+    uchar4* rgba;
+};
+static int hist_alloc(bdpt_ctx* c, hist_bufs* b) {
+    const size_t np = (size_t)c->W * c->H, bytes = (4 * sizeof(float4) + sizeof(bdpt_dev_vec) + sizeof(float) + 4) * np;
+    if (!c->d_hist && hipMalloc(&c->d_hist, bytes) != hipSuccess) {
+        c->d_hist = nullptr;
+        return fail(c, BDPT_ENOMEM, "bdpt_reproject: history and result buffers (%zu B)", bytes);
+    }
+    for (int s = 0; s < 2; s++) {
+        b->guide[s] = c->d_hist + 2 * s * np;
+        b->col[s] = c->d_hist + (2 * s + 1) * np;
+    }
+    b->out3 = (bdpt_dev_vec*)(c->d_hist + 4 * np);
+    b->weight = (float*)(b->out3 + np);
+    b->rgba = (uchar4*)(b->weight + np);
+    return BDPT_OK;
+}
+
+static int rp_run(bdpt_ctx* c, const bdpt_reproject_params* p, bool capture, bdpt_vec* colors_out,
+                  float* weight_out, unsigned char* rgba_out) {
+    if (c->cpu) {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (capture) bdpt_cpu_history_capture(c->cpu, p);
+        else bdpt_cpu_reproject(c->cpu, p, colors_out, weight_out, rgba_out);
+        c->rp_cpu_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        c->rp_ran = true;
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t np = (size_t)c->W * c->H;
+    hist_bufs b;
+    if (int rc = hist_alloc(c, &b)) return rc;
+    for (hipEvent_t& e : c->rp_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    if (int rc = join_fold(c)) return rc;
+    HIPCHK(c, hipEventRecord(c->rp_ev[0], c->stream));
+    bdpt_aov_args av;
+    bool bvh = false;
+    if (int rc = aov_launch(c, c->cam, 0, 0, c->W, c->H, 0, 0u, &av, &bvh, nullptr, nullptr)) return rc;
+    const int cur = c->hist_cur, nxt = cur ^ 1;
+    bdpt_reproject_args v;
+    memset(&v, 0, sizeof(v));
+    v.W = c->W; v.H = c->H;
+    v.all_materials = p->materials == BDPT_DENOISE_ALL;
+    v.max_history = p->max_history;
+    v.plane_tol = p->plane_tol;
+    v.id = av.id; v.t = av.t; v.position = av.position; v.normal = av.normal;
+    v.sph = c->d_sph;
+    v.colors = c->d_colors;
+    v.counter = c->d_counter;
+    v.gamma_thr = c->d_thr;
+    if (hist_present(c)) {
+        bdpt_path_args ha;                                    // C0 as the kernels' camera constants
+        memset(&ha, 0, sizeof(ha));
+        camera_args(c, c->hist_cam, ha);
+        memcpy(v.ux, ha.ux, sizeof(v.ux)); memcpy(v.uy, ha.uy, sizeof(v.uy)); memcpy(v.ud, ha.ud, sizeof(v.ud));
+        memcpy(v.o, ha.orig, sizeof(v.o));
+        v.hw = (float)ha.half_w; v.hh = (float)ha.half_h;
+        v.sx = 1.f / ha.inv_w; v.sy = 1.f / ha.inv_h;
+        v.hguide = b.guide[cur];
+        v.hcol = b.col[cur];
+    }
+    // wave tile: the measured choice; BDPT_REPROJECT_TILE = 8 / 64 overrides it
+    v.rows = 1;
+    if (const char* e = getenv("BDPT_REPROJECT_TILE")) v.rows = atoi(e) != 8;
+    if (capture) {
+        hipLaunchKernelGGL(bdpt_history_pack_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream,
+                           (const int*)av.id, (const bdpt_dev_vec*)av.position, (const bdpt_dev_vec*)nullptr,
+                           (const float*)nullptr, b.guide[nxt], (float4*)nullptr, (int)np);
+        HIPCHK(c, hipGetLastError());
+        v.next = b.col[nxt];
+    } else {
+        v.out3 = colors_out ? b.out3 : nullptr;
+        v.weight = weight_out ? b.weight : nullptr;
+        v.rgba = rgba_out ? b.rgba : nullptr;
+    }
+    const int btw = v.rows ? BDPT_RP_ROW_BTW : BDPT_RP_BTW, bth = v.rows ? BDPT_RP_ROW_BTH : BDPT_RP_BTH;
+    const dim3 grid((unsigned)((c->W + btw - 1) / btw), (unsigned)((c->H + bth - 1) / bth), 1);
+    hipLaunchKernelGGL(bdpt_reproject_kernel, grid, dim3(256), 0, c->stream, v);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->rp_ev[1], c->stream));
+    c->rp_ran = true;
+    if (capture) {
+        c->hist_cur = nxt;
+        c->has_hist = true;
+        c->hist_cam = c->cam;
+        c->hist_spheres = c->spheres;
+    }
+    if (colors_out) HIPCHK(c, hipMemcpyAsync(colors_out, b.out3, sizeof(bdpt_vec) * np, hipMemcpyDeviceToHost, c->stream));
+    if (weight_out) HIPCHK(c, hipMemcpyAsync(weight_out, b.weight, sizeof(float) * np, hipMemcpyDeviceToHost, c->stream));
+    if (rgba_out) HIPCHK(c, hipMemcpyAsync(rgba_out, b.rgba, 4 * np, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return units_verdict(c);                                 // a frame known to be invalid is an error
+}
+
+int bdpt_reproject(bdpt_ctx* c, const bdpt_reproject_params* p, bdpt_vec* colors_out, float* weight_out,
+                   unsigned char* rgba_out) {
+    if (!c) return BDPT_EINVAL;
+    if (int rc = rp_check(c, p, "bdpt_reproject")) return rc;
+    if (!colors_out && !weight_out && !rgba_out) return fail(c, BDPT_EINVAL, "bdpt_reproject: no output buffer");
+    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_reproject: camera not set");
+    return rp_run(c, p, false, colors_out, weight_out, rgba_out);
+}
+
+int bdpt_history_capture(bdpt_ctx* c, const bdpt_reproject_params* p) {
+    if (!c) return BDPT_EINVAL;
+    if (int rc = rp_check(c, p, "bdpt_history_capture")) return rc;
+    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_history_capture: camera not set");
+    return rp_run(c, p, true, nullptr, nullptr, nullptr);
+}
+
+int bdpt_history_clear(bdpt_ctx* c) {
+    if (!c) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_history_clear: multi-device contexts keep no history");
+    if (c->cpu) bdpt_cpu_history_clear(c->cpu);
+    c->has_hist = false;
+    return BDPT_OK;
+}
+
+int bdpt_history_info(const bdpt_ctx* c, int* present, bdpt_camera* camera) {
+    if (!c || c->multi) return BDPT_EINVAL;
+    if (present) *present = hist_present(c);
+    if (c->cpu) (void)bdpt_cpu_history_stored(c->cpu, camera);
+    else if (c->has_hist && camera) *camera = c->hist_cam;
+    return BDPT_OK;
+}
+
+int bdpt_history_read(bdpt_ctx* c, bdpt_vec* colors, float* weight) {
+    if (!c) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_history_read: multi-device contexts keep no history");
+    if (!colors && !weight) return fail(c, BDPT_EINVAL, "bdpt_history_read: no output buffer");
+    if (!(c->cpu ? bdpt_cpu_history_stored(c->cpu, nullptr) : c->has_hist))
+        return fail(c, BDPT_ESTATE, "bdpt_history_read: no history");
+    if (c->cpu) {
+        bdpt_cpu_history_read(c->cpu, colors, weight);
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t np = (size_t)c->W * c->H;
+    hist_bufs b;
+    if (int rc = hist_alloc(c, &b)) return rc;
+    std::vector<float4> rec(np);
+    HIPCHK(c, hipMemcpyAsync(rec.data(), b.col[c->hist_cur], sizeof(float4) * np, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < np; i++) {
+        if (colors) colors[i] = {rec[i].x, rec[i].y, rec[i].z};
+        if (weight) weight[i] = rec[i].w;
+    }
+    return BDPT_OK;
+}
+
+int bdpt_history_write(bdpt_ctx* c, const bdpt_camera* camera, const bdpt_vec* colors, const float* weight) {
+    if (!c) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_history_write: multi-device contexts keep no history");
+    if (!camera || !colors || !weight) return fail(c, BDPT_EINVAL, "bdpt_history_write: NULL argument");
+    if (c->cpu) {
+        bdpt_cpu_history_write(c->cpu, camera, colors, weight);
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t np = (size_t)c->W * c->H;
+    hist_bufs b;
+    if (int rc = hist_alloc(c, &b)) return rc;
+    if (int rc = join_fold(c)) return rc;
+    // staged in the result buffers, then packed with the guides rendered under `camera`
+    HIPCHK(c, hipMemcpyAsync(b.out3, colors, sizeof(bdpt_vec) * np, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.weight, weight, sizeof(float) * np, hipMemcpyHostToDevice, c->stream));
+    bdpt_aov_args av;
+    bool bvh = false;
+    if (int rc = aov_launch(c, *camera, 0, 0, c->W, c->H, 0, 0u, &av, &bvh, nullptr, nullptr)) return rc;
+    hipLaunchKernelGGL(bdpt_history_pack_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream,
+                       (const int*)av.id, (const bdpt_dev_vec*)av.position, (const bdpt_dev_vec*)b.out3,
+                       (const float*)b.weight, b.guide[c->hist_cur], b.col[c->hist_cur], (int)np);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->has_hist = true;
+    c->hist_cam = *camera;
+    c->hist_spheres = c->spheres;
+    return BDPT_OK;
+}
+
+int bdpt_last_reproject_ms(bdpt_ctx* c, float* ms) {
+    if (!c || !ms) return BDPT_EINVAL;
+    if (!c->rp_ran) return fail(c, BDPT_ESTATE, "bdpt_last_reproject_ms: no frame reprojected");
+    if (c->cpu) {
+        *ms = c->rp_cpu_ms;
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(c->rp_ev[1]));
+    HIPCHK(c, hipEventElapsedTime(ms, c->rp_ev[0], c->rp_ev[1]));
     return BDPT_OK;
 }
 

@@ -2357,4 +2357,112 @@ extern "C" const void* bdpt_denoise_level_table[2][7] = {
     {BDPT_DNL(0), BDPT_DNL(1), BDPT_DNL(2), BDPT_DNL(3), BDPT_DNL(4), BDPT_DNL(5), BDPT_DNL(6)}};
 #undef BDPT_DN
 #undef BDPT_DNL
+
+// ---------------------------------------------------------------------------------------------
+// Temporal reprojection (include/bdpt.h bdpt_reproject; no reference counterpart).
+// Host sequence on the context's stream: bdpt_aov_kernel (unjittered, whole frame, under the
+// current camera), then bdpt_reproject_kernel; a capture also packs the planes into the next
+// history's guide records.  Numerics as for the denoiser above: the definition operation for
+// operation, fp32 without contraction, dot() as (x + y) + z, every reciprocal through rcp_rn
+// (library division outside [2^-125, 2^125): cz = 0, a denormal sw), denormals kept.
+
+// History records from planes: guide = {position, id} (either pair of pointers may be null).
+extern "C" __global__ __launch_bounds__(256) void bdpt_history_pack_kernel(
+    const int* __restrict__ id, const bdpt_dev_vec* __restrict__ position, const bdpt_dev_vec* __restrict__ colors,
+    const float* __restrict__ weight, float4* __restrict__ guide, float4* __restrict__ col, int count) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    if (guide) {
+        const bdpt_dev_vec p = position[i];
+        guide[i] = make_float4(p.x, p.y, p.z, __int_as_float(id[i]));
+    }
+    if (col) {
+        const bdpt_dev_vec c = colors[i];
+        col[i] = make_float4(c.x, c.y, c.z, weight[i]);
+    }
+}
+
+// One lane per pixel: the projection of the pixel's first-hit point into the history's camera,
+// four validated taps of two 16-byte loads each (issued together; a tap outside the frame reads the
+// lane's own record, always a valid address, and is not used), the blend, and the stores the call
+// asked for.  Wave tiles 8 x 8 or 64 x 1 (v.rows), as in bdpt_aov_kernel.
+extern "C" __global__ __launch_bounds__(256) void bdpt_reproject_kernel(bdpt_reproject_args v) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = v.rows ? (int)blockIdx.x * BDPT_RP_ROW_BTW + lane
+                         : (int)blockIdx.x * BDPT_RP_BTW + wave * 8 + (lane & 7);
+    const int y = v.rows ? (int)blockIdx.y * BDPT_RP_ROW_BTH + wave
+                         : (int)blockIdx.y * BDPT_RP_BTH + (lane >> 3);
+    if (x >= v.W || y >= v.H) return;                    // (no cross-lane operation below)
+    const int i = y * v.W + x;
+    const bdpt_dev_vec c3 = v.colors[i];
+    const f3 c = mk(c3.x, c3.y, c3.z);
+    const float n = (float)v.counter[i];
+    const int id1 = v.id[i];
+    bool eligible = v.hguide != nullptr && id1 >= 0;
+    if (eligible && !v.all_materials) eligible = v.sph[id1].refl == BDPT_DEV_DIFF;
+    float m = 0.f;
+    f3 h = mk(0.f, 0.f, 0.f);
+    if (eligible) {
+        const bdpt_dev_vec p3 = v.position[i], n3 = v.normal[i];
+        const f3 P = mk(p3.x, p3.y, p3.z), N = mk(n3.x, n3.y, n3.z);
+        const f3 d = sub(P, mk(v.o[0], v.o[1], v.o[2]));
+        const float a = dot(d, mk(v.ux[0], v.ux[1], v.ux[2]));
+        const float b = dot(d, mk(v.uy[0], v.uy[1], v.uy[2]));
+        const float cz = dot(d, mk(v.ud[0], v.ud[1], v.ud[2]));
+        const float r = rcp_rn(cz);
+        const float kx = (10.f * a) * r, ky = (10.f * b) * r;
+        const float fx = (kx + v.hw) * v.sx, fy = (ky + v.hh) * v.sy;
+        if (fx >= -1.f && fx < (float)v.W && fy >= -1.f && fy < (float)v.H) {   // a NaN fails
+            const float xf = floorf(fx), yf = floorf(fy);
+            const float wx = fx - xf, wy = fy - yf;
+            const int qx0 = (int)xf, qy0 = (int)yf;       // -1 .. W-1, -1 .. H-1
+            const float lim = v.plane_tol * v.t[i];
+            float4 gq[4], cq[4];
+            bool in[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int qx = qx0 + (k & 1), qy = qy0 + (k >> 1);
+                in[k] = qx >= 0 && qx < v.W && qy >= 0 && qy < v.H;
+                const int q = in[k] ? qy * v.W + qx : i;
+                gq[k] = v.hguide[q];
+                cq[k] = v.hcol[q];
+            }
+            float sw = 0.f, sm = 0.f;
+            f3 sc = mk(0.f, 0.f, 0.f);
+            bool used = false;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {                 // dy outer, dx inner, as defined
+                const float bx = (k & 1) ? wx : 1.f - wx, by = (k >> 1) ? wy : 1.f - wy;
+                const float bw = bx * by;
+                if (!in[k] || !(bw > 0.f) || __float_as_int(gq[k].w) != id1 || !(cq[k].w > 0.f)) continue;
+                if (!(fabsf(dot(sub(mk(gq[k].x, gq[k].y, gq[k].z), P), N)) <= lim)) continue;
+                sw = sw + bw;
+                sm = sm + bw * fminf(cq[k].w, v.max_history);
+                sc = add(sc, smul(bw, mk(cq[k].x, cq[k].y, cq[k].z)));
+                used = true;
+            }
+            if (used) {
+                h = smul(rcp_rn(sw), sc);
+                m = sm;
+            }
+        }
+    }
+    const float tot = n + m;
+    f3 o = c;
+    if (m == 0.f) {
+    } else if (n == 0.f) {
+        o = h;
+    } else {
+        const float rt = rcp_rn(tot);
+        o = mk((n * c.x + m * h.x) * rt, (n * c.y + m * h.y) * rt, (n * c.z + m * h.z) * rt);
+    }
+    if (v.next) v.next[i] = make_float4(o.x, o.y, o.z, tot);
+    if (v.out3) {
+        bdpt_dev_vec ov;
+        ov.x = o.x; ov.y = o.y; ov.z = o.z;
+        v.out3[i] = ov;
+    }
+    if (v.weight) v.weight[i] = tot;
+    if (v.rgba) v.rgba[i] = bdpt_dev_to_rgba(o.x, o.y, o.z, v.gamma_thr);
+}
 #endif  // BDPT_JIT

@@ -6,6 +6,7 @@
  *   smallpt [<width> <height> <scene.scn>] [--spp N] [--batch B] [--keys KEYS] [--out F.ppm]
  *           [--device D | --gpus N | --devices D0,D1,...] [--tile ROWS] [--seed S] [--dat PATH]
  *           [--denoise [--denoise-levels N] [--denoise-sigma S] [--denoise-all]]
+ *           [--reproject [--reproject-history N] [--reproject-tol T]]
  *
  * Without positional arguments the built-in CornellSpheres scene is used (smallpt_cpu.c:400).
  * Like the reference, width/height get +1 (smallpt_cpu.c:409-410).  The first frame runs the
@@ -23,6 +24,11 @@
  * --denoise writes --out from the denoised frame (bdpt_denoise: 4 levels, sigma 0.5, diffuse
  * surfaces only, unless --denoise-levels / --denoise-sigma / --denoise-all say otherwise) instead
  * of the raw pixels; one device (or the CPU, --device -1) only.
+ * --reproject keeps the last view's frame across camera keys: every camera key of --keys captures
+ * the frame before re-initialising (bdpt_history_capture), a sphere key clears the history, and
+ * --out is written from the preview's pixels (bdpt_reproject: history weight capped at
+ * --reproject-history, default 64; plane test --reproject-tol, default 0.01); one device (or the
+ * CPU) only.  The accumulation itself is unchanged.
  */
 #include "smallpt_app.h"
 
@@ -37,6 +43,9 @@ int main(int argc, char **argv)
     const char *ckpt = NULL, *resume = NULL;
     int denoise = 0;
     bdpt_denoise_params dn = {4, 5, 0.5f, BDPT_DENOISE_DIFFUSE};
+    h.rp.materials = BDPT_DENOISE_DIFFUSE;
+    h.rp.max_history = 64.f;
+    h.rp.plane_tol = 0.01f;
     for (int a = 1; a < argc; a++) {
         if (!strcmp(argv[a], "--spp") && a + 1 < argc) spp = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--batch") && a + 1 < argc) batch = atoi(argv[++a]);
@@ -59,6 +68,9 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[a], "--denoise-levels") && a + 1 < argc) dn.levels = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--denoise-sigma") && a + 1 < argc) dn.sigma_color = strtof(argv[++a], NULL);
         else if (!strcmp(argv[a], "--denoise-all")) dn.materials = BDPT_DENOISE_ALL;
+        else if (!strcmp(argv[a], "--reproject")) h.reuse_history = 1;
+        else if (!strcmp(argv[a], "--reproject-history") && a + 1 < argc) h.rp.max_history = strtof(argv[++a], NULL);
+        else if (!strcmp(argv[a], "--reproject-tol") && a + 1 < argc) h.rp.plane_tol = strtof(argv[++a], NULL);
         else if (!strcmp(argv[a], "--checkpoint") && a + 1 < argc) ckpt = argv[++a];
         else if (!strcmp(argv[a], "--resume") && a + 1 < argc) resume = argv[++a];
         else if (npos < 3) pos[npos++] = argv[a];
@@ -68,6 +80,10 @@ int main(int argc, char **argv)
     fprintf(stderr, "Usage: %s <window width> <window height> <scene file>\n", argv[0]);
     if (denoise && ndev) {
         fprintf(stderr, "--denoise needs one device (--device D, or -1 for the CPU)\n");
+        return 1;
+    }
+    if (h.reuse_history && (ndev || denoise)) {
+        fprintf(stderr, "--reproject needs one device (--device D, or -1 for the CPU) and no --denoise\n");
         return 1;
     }
     if (npos == 3) {
@@ -139,7 +155,9 @@ int main(int argc, char **argv)
         for (int done = 0; done < spp; done += batch)
             update_rendering(&h, spp - done < batch ? spp - done : batch);
     }
-    if (out) rc = denoise ? save_denoised_ppm(&h, out, p6, &dn) : save_ppm(&h, out, p6);
+    if (out)
+        rc = denoise ? save_denoised_ppm(&h, out, p6, &dn)
+                     : h.reuse_history ? save_preview_ppm(&h, out, p6) : save_ppm(&h, out, p6);
     if (ckpt) {
         host_state st;
         get_state(&h, &st);

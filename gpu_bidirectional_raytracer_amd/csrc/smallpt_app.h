@@ -30,6 +30,8 @@ typedef struct {
     int current_sample, reinit_counter, current_sphere;
     float total_time;
     bdpt_pass_state ps;
+    int reuse_history;                 /* --reproject: camera keys capture the frame before ReInit */
+    bdpt_reproject_params rp;
 } host;
 
 static void report(host *h, int rc, const char *what)
@@ -80,6 +82,7 @@ static void reinit(host *h)
 /* ReInitScene smallpt_cpu.c:365-371 */
 static void reinit_scene(host *h)
 {
+    if (h->reuse_history) report(h, bdpt_history_clear(h->ctx), "ReInitScene history");
     h->current_sample = 0;
     report(h, bdpt_reset_accum(h->ctx), "ReInitScene");
     report(h, bdpt_set_scene(h->ctx, h->spheres, h->n), "ReInitScene upload");
@@ -114,6 +117,19 @@ __attribute__((unused)) static int save_denoised_ppm(host *h, const char *path, 
         rc = binary ? bdpt_save_ppm_binary(path, rgba, h->width, h->height)
                     : bdpt_save_ppm(path, rgba, h->width, h->height);
     report(h, rc, "Denoised SavePPM");
+    free(rgba);
+    return rc;
+}
+
+/* --reproject: the same file from the preview's pixels (bdpt_reproject) */
+__attribute__((unused)) static int save_preview_ppm(host *h, const char *path, int binary)
+{
+    unsigned char *rgba = malloc(4 * (size_t)h->width * h->height);
+    int rc = rgba ? bdpt_reproject(h->ctx, &h->rp, NULL, NULL, rgba) : BDPT_ENOMEM;
+    if (rc == BDPT_OK)
+        rc = binary ? bdpt_save_ppm_binary(path, rgba, h->width, h->height)
+                    : bdpt_save_ppm(path, rgba, h->width, h->height);
+    report(h, rc, "Preview SavePPM");
     free(rgba);
     return rc;
 }
@@ -158,6 +174,8 @@ static void key(host *h, int k)
     } else if (bdpt_sphere_key(h->spheres, h->n, h->current_sphere, k)) {
         reinit_scene(h);
     } else if (bdpt_camera_key(&h->camera, code)) {
+        /* the context still holds the old camera and the frame ReInit is about to discard */
+        if (h->reuse_history) report(h, bdpt_history_capture(h->ctx, &h->rp), "History capture");
         reinit(h);
     }
 }

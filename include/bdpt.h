@@ -325,6 +325,72 @@ int  bdpt_denoise(bdpt_ctx *ctx, const bdpt_denoise_params *params, bdpt_vec *co
  * and level launches, no read-back; wall time on the CPU backend).  BDPT_ESTATE before any call. */
 int  bdpt_last_denoise_ms(bdpt_ctx *ctx, float *ms);
 
+/* ---- temporal reprojection: the last view's frame in the preview after a camera move (no
+ * reference counterpart: every camera key goes through ReInit, smallpt_cpu.c:373-387, which
+ * discards the frame) ----
+ * A preview only: nothing here feeds back into the accumulation or the counters.  fp32, no
+ * contraction, in the order written; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; every 1/x is the
+ * correctly rounded reciprocal; denormals are kept; non-finite radiance is not special.  The GPU,
+ * the CPU backend and the tests' numpy statement form the same bits.
+ *   history   a context-owned snapshot taken under a camera C0 and the sphere array of that
+ *             moment.  Per pixel q: a colour hc[q], a weight hm[q] >= 0 (the float count of passes
+ *             behind the colour) and the guides gid[q], gpos[q] = id and position of
+ *             bdpt_render_aov with jitter = 0 under C0, whole frame, rendered once when the history
+ *             is taken.  While the context's spheres differ from the remembered array byte for
+ *             byte the history counts as absent (a moved sphere changes the lighting everywhere).
+ *   C0        as the kernels' camera constants: ux, uy, ud = vnorm of C0.x, C0.y, C0.dir
+ *             (l = 1.f / sqrtf((x*x + y*y) + z*z), each component times l); o = C0.orig;
+ *             inv_w = (float)(14./W), inv_h = (float)(10.5/H);
+ *             hw = (float)((double)(inv_w*(float)W)/2.), hh likewise; sx = 1.f/inv_w, sy = 1.f/inv_h.
+ *   pixel p = (x, y): c = colors[p], n = (float)counter[p] as they stand; id1, t1, P, N = id, t,
+ *             position, normal of the current camera's unjittered first hit.
+ *    1. m = 0 when no history is present, id1 < 0, or p is not eligible (materials ==
+ *       BDPT_DENOISE_DIFFUSE: spheres[id1].refl == BDPT_DIFF; BDPT_DENOISE_ALL: any hit).
+ *    2. v = P - o; a = dot(v, ux); b = dot(v, uy); cz = dot(v, ud); r = 1/cz;
+ *       kx = (10.f*a)*r; ky = (10.f*b)*r; fx = (kx + hw)*sx; fy = (ky + hh)*sy.
+ *       Unless fx >= -1 && fx < W && fy >= -1 && fy < H (a NaN fails): m = 0.
+ *    3. x0 = floorf(fx), wx = fx - x0, y0 = floorf(fy), wy = fy - y0; sw = sm = +0, sc = (+0,+0,+0);
+ *       for dy = 0, 1, for dx = 0, 1: q = (x0+dx, y0+dy), bx = dx ? wx : 1.f - wx,
+ *       by = dy ? wy : 1.f - wy, bw = bx*by.  The tap is used iff q is inside the frame, bw > 0,
+ *       gid[q] == id1, hm[q] > 0 and fabsf(dot(gpos[q] - P, N)) <= plane_tol * t1; a used tap adds
+ *       sw = sw + bw; sm = sm + bw*fminf(hm[q], max_history); sc = sc + bw*hc[q].  A tap that is
+ *       not used is skipped, not weighted by zero.
+ *    4. No tap used: m = 0.  Otherwise h = sc*(1/sw), m = sm.
+ *    5. tot = n + m; out = c if m == 0 (unchanged, and stale if n == 0, exactly what
+ *       bdpt_read_radiance returns); out = h if n == 0 and m > 0; else out = (n*c + m*h)*(1/tot);
+ *       weight_out = tot.
+ * The id test rejects a point the old view did not show, the plane test one on the far side of the
+ * same sphere.  Defaults: materials DIFFUSE, max_history 64, plane_tol 0.01.
+ *
+ * bdpt_history_capture forms (out, weight_out) as above from the history present, if any (without
+ * one: colors and (float)counter), stores them as the new hc, hm with the current camera as C0, the
+ * current spheres as the key and the guides rendered under the current camera; the records are
+ * ping-ponged, so the capture reads the old history while it writes the new one.  Call it before
+ * the camera changes.  bdpt_history_write uploads a history from the host and renders its guides
+ * under `camera` and the current scene.  bdpt_history_info: *present is 0 also while the scene
+ * differs; *camera is C0 (written only when a history is stored).  bdpt_history_read: the stored
+ * colours and weights (also while the scene differs), BDPT_ESTATE when none is stored.  bdpt_reproject without a history present is
+ * valid and returns colors and (float)counter; rgba_out goes through the toInt thresholds and alpha
+ * of bdpt_read_pixels; any output may be NULL, not all.  bdpt_last_reproject_ms: device time of the
+ * last capture's or reprojection's kernels alone (HIP events; wall time on the CPU backend).
+ * All are synchronous, ordered after whatever the context has queued, and write nothing but the
+ * history and their own buffers: accumulation, counters, pixels, tables, VLPs, path timing, the auto
+ * stream mode's measurements and shards are untouched.  The history is not part of a checkpoint.
+ * BDPT_EINVAL: NULL parameters or all outputs NULL, materials outside 0 and 1, max_history not > 0
+ * (NaN rejected, +inf allowed), plane_tol negative or NaN (+inf: no plane test), a multi-device
+ * context.  BDPT_ESTATE: no camera set (bdpt_reproject, bdpt_history_capture);
+ * bdpt_last_reproject_ms before the first successful call. */
+typedef struct { int materials; float max_history; float plane_tol; } bdpt_reproject_params;
+int  bdpt_history_capture(bdpt_ctx *ctx, const bdpt_reproject_params *params);
+int  bdpt_history_clear(bdpt_ctx *ctx);
+int  bdpt_history_info(const bdpt_ctx *ctx, int *present, bdpt_camera *camera);
+int  bdpt_history_read(bdpt_ctx *ctx, bdpt_vec *colors, float *weight);
+int  bdpt_history_write(bdpt_ctx *ctx, const bdpt_camera *camera, const bdpt_vec *colors,
+                        const float *weight);
+int  bdpt_reproject(bdpt_ctx *ctx, const bdpt_reproject_params *params, bdpt_vec *colors_out,
+                    float *weight_out, unsigned char *rgba_out);
+int  bdpt_last_reproject_ms(bdpt_ctx *ctx, float *ms);
+
 /* ---- optional display: HIP-GL interop ----
  * The caller owns the window, its OpenGL context (current on the calling thread) and a
  * pixel-unpack buffer of at least 4*W*H bytes (glGenBuffers + glBufferData(GL_PIXEL_UNPACK_BUFFER,
