@@ -27,6 +27,7 @@
 #include "bdpt_device.h"
 #include "bdpt_bvh.h"
 #include "bdpt_cpu.h"
+#include "bdpt_plan.h"
 #include <chrono>
 
 static_assert(kBvhEmissive == BDPT_DEV_BVH_EMISSIVE, "BVH id flag");
@@ -111,40 +112,12 @@ struct bdpt_ctx {
     bool rand_ready = false;
     int shard = 0, nshards = 1, band_rows = 8;
     int streams_req = 0;                // bdpt_set_streams: 0 = auto (measured), -1 = one pass per lane
-    // auto mode: the first eight calls of >= 2 passes run, in this order, the pass-stream kernels
-    // with two passes per lane, the fused S = 1 kernel with paired segment loads (bdpt_kernels.hip
-    // BDPT_RNG_PAIR), pass streams with four passes per lane, two per lane again, the fused kernel
-    // without pairing, four per lane again, and twice pass streams with pixel pools (specialised
-    // builds only, bdpt_kernels.hip BDPT_POOL).  The pass-stream variant kept is the one with the
-    // fastest call; the faster fused variant replaces it only if it beats that by kTuneMargin.
-    // Calls are compared per pass by path-kernel time plus a quarter of the call's fold: the fold
-    // runs on its own stream beside the next call's kernels (fold_timing).  (A cold first call -- clocks still ramping -- no
-    // longer decides for the fused kernel.)  tune_phase 0..7: measuring; 8: all issued; 9:
-    // decided.  Reset by scene / shard / traversal / specialisation / stream-mode changes.
-    // BDPT_STREAMS_TUNE=0: no measurement (two passes per lane).
-    // (5 %: open scenes gain >= 10 % from the fused kernel, closed ones lose >= 7 %; with 2 % a
-    // one-call measurement once kept the fused kernel for gantz, 7 % slower, profiles/r03_s27_*.
-    // Four passes per lane: cornell_glass / cornell_mirror +1.2 %, synthetic64 -2.8 % at 128-pass
-    // launches, profiles/r03_s45_ab_passes_per_lane.txt -- so it is measured, not fixed.)
-    static constexpr double kTuneMargin = 0.05;
-    static constexpr int kTunePhases = 10;
-    bool tune_enabled = true;
-    int tune_phase = 0;
-    bool tune_fused = false;
-    bool tune_pair = true;              // the fused variant kept: paired segment loads or not
-    bool tune_quarter = false;          // the pass-stream variant kept: four passes per lane
-    bool tune_pool = false;             // the pass-stream variant kept: pixel pools
-    bool tune_units = false;            // the pass-stream variant kept: the ordered in-kernel fold
-    long long tune_call[kTunePhases] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-    double tune_ms[kTunePhases] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    // whether each tuning call really ran its role's variant: four passes per lane needs launches
-    // of >= 8 passes, and the unpaired fused variant exists only as a specialised (JIT) build --
-    // otherwise the role repeated another role's kernel and must not decide anything
-    bool tune_real[kTunePhases] = {false, false, false, false, false, false, false, false, false, false};
-    int tune_npass[kTunePhases] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // auto mode: the first ten calls of >= 2 passes each measure one kernel variant (roles 0..9,
+    // the table in bdpt_plan.h); the eleventh decides which one later calls run.
+    bdpt_tuner tuner;
     // multi-device groups: the peers follow the stream mode devices[0] measured (its decision is
     // copied when they reach the decision point), so every device of a group runs the same kernels
-    bdpt_ctx* tune_leader = nullptr;
+    bdpt_ctx* group_leader = nullptr;
     int last_streams = 1;               // S of the last path-pass launch
     bool last_bvh = false;              // the last path-pass launch traversed the BVH
     int cus = 256;                      // compute units (auto stream count)
@@ -271,7 +244,7 @@ static int fail(bdpt_ctx* c, int code, const char* fmt, ...) {
 
 static int join_fold(bdpt_ctx* c);
 static int upload_scene(bdpt_ctx* c) {
-    c->tune_phase = 0;                                      // re-measure the stream mode
+    c->tuner.reset();                                       // re-measure the stream mode
     for (auto& row : c->jit_memo)                           // the specialised kernels change too
         for (auto& m : row) m.valid = false;
     const unsigned n = (unsigned)c->spheres.size();
@@ -612,48 +585,44 @@ static int fused_max_passes() {
 }
 
 // Pixel pools for the pass-stream kernel (bdpt_kernels.hip BDPT_POOL), a specialised build of
-// its own launched with one pass per lane slice: the auto stream mode measures it (tuning roles
-// 6, 7).  BDPT_POOL: unset = measured, 0 = never, R > 0 = always (streams launches), chunks of
-// R x 64 pixels; BDPT_POOL_GRID = G: G x 64 pixels per wave and pass.
+// its own launched with one pass per lane slice: the auto stream mode measures it (bdpt_plan.h).
+// BDPT_POOL: unset = measured, 0 = never, R > 0 = always (streams launches), chunks of
+// R x 64 pixels; BDPT_POOL_GRID = G: G x 64 pixels per wave and pass (bdpt_plan.h bdpt_pool_shape).
 static int pool_env() {
     const char* e = getenv("BDPT_POOL");
     if (!e || !*e) return -1;
     const int v = atoi(e);
     return v < 1 ? 0 : (v > 64 ? 64 : v);
 }
-// Launch shape of a pooled launch of nloc pixels per pass: {chunk R, grid G} (a wave claims R x 64
-// pixels at a time; a pass has nloc / (256 G) workgroups).  With the sparse serial fold and
-// overlapped launches, larger chunks and grids measured best (profiles/r05_s44_pool_shape.txt,
-// r05_s45_*, r05_s46_*, r05_s48_*, r05_s49_*; interleaved rounds, ms per step): whole frame
-// (2.08 M) G = 128, R = 64 3.54-3.55 against G = 64, R = 16 3.66-3.68; 1/2 share G = 128, R = 32
-// 1.88-1.89 against 1.95-1.96; 1/4 share 0.943-0.954 against 0.956-0.962; 1/8 share (260 K)
-// G = 128, R = 16 0.548-0.553 against G = 64, R = 16 0.567-0.568 and G = 128, R = 32 0.576-0.578.
-// Launches that are not overlapped (the auto-tuner's calls, BDPT_POOL_OVERLAP=0) keep the shape
-// that measured best before the overlap, G = 64, R = 16: a serial launch pays the large shapes'
-// drain in full, and with them the tuner's pooled call at the 1/8 share lost to S = 32
-// (r05_s50_strong.txt, N = 8 row).
-static void pool_shape(long nloc, bool overlap, int* R, int* G) {
-    int g = overlap ? 128 : 64;
-    int r = !overlap ? 16 : nloc >= 1500000 ? 64 : (nloc >= 400000 ? 32 : 16);
-    if (const char* e = getenv("BDPT_POOL_GRID")) {
-        const int v = atoi(e);
-        if (v >= 1) g = v > 256 ? 256 : v;
-    }
-    const int pe = pool_env();
-    *G = g;
-    *R = pe > 0 ? pe : r;
-}
 
 // The specialised kernel for the context's scene and pass-stream mode, compiled on first use;
 // nullptr = use the precompiled instance (reason in c->jit_err).
 // Pass streams with the ordered fold inside the kernel (bdpt_kernels.hip BDPT_UNITS): BDPT_UNITS=P
 // forces it with ranges of P passes (experiments; 0 = never).
-static constexpr int kUnitPasses = 8;   // passes per unit range in the auto mode (profiles/r05_s5_*)
 static int units_env() {
     const char* e = getenv("BDPT_UNITS");
     if (!e || !*e) return -1;
     const int v = atoi(e);
     return v < 1 ? 0 : (v > 128 ? 128 : v);
+}
+
+// The planner's switches (bdpt_plan.h), read at every call -- tests and in-process A/Bs change
+// them between calls -- except the three that are read once per process.
+static bdpt_path_env path_env() {
+    static const bdpt_path_env once = [] {
+        bdpt_path_env e;
+        e.fused_max_passes = fused_max_passes();
+        if (const char* v = getenv("BDPT_POOL_OVERLAP")) e.pool_overlap = atoi(v) != 0;
+        if (const char* v = getenv("BDPT_UNITS_TAPER")) e.units_taper = atoi(v) != 0;
+        return e;
+    }();
+    bdpt_path_env e = once;
+    e.pool = pool_env();
+    e.units = units_env();
+    if (const char* v = getenv("BDPT_MAX_LAUNCH_PASSES")) e.max_launch_passes = atoi(v);
+    if (const char* v = getenv("BDPT_POOL_GRID")) e.pool_grid = std::min(atoi(v), 256);
+    if (const char* v = getenv("BDPT_SMEM_PAD")) e.smem_pad = atoi(v);
+    return e;
 }
 
 static hipFunction_t jit_path_kernel_build(bdpt_ctx* c, bool streams, bool pair, bool pool, bool units) {
@@ -731,13 +700,13 @@ static hipFunction_t jit_path_kernel_build(bdpt_ctx* c, bool streams, bool pair,
         if (!fn) return nullptr;
         // The 4-KB sincos table costs a workgroup per CU when LDS bounds the count (large
         // scenes: 16 B per sphere; the fused kernel: a VLP and a sid per pass of the launch);
-        // then take the 2-KB table of even entries (bdpt_math.h).  Estimated with bdpt_path_passes'
-        // smem formula: one pass slot for the pass-stream kernel, fused_max_passes() for the fused.
+        // then take the 2-KB table of even entries (bdpt_math.h).  Estimated with the launches'
+        // LDS formula (bdpt_plan.h) over a table of 5 per sphere: one pass slot for the pass-stream kernel, fused_max_passes() for the fused.
         int stat = 0;
         if (!coarse && !user_coarse &&
             hipFuncGetAttribute(&stat, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, fn) == hipSuccess) {
             const size_t slots = units ? (size_t)std::max(units_env(), 16) : streams ? 1 : (size_t)fused_max_passes();
-            const size_t dyn = sizeof(float4) * (5 * (size_t)n + 3 * slots + 5 + 4 * 128 * 2) + sizeof(unsigned) * slots;
+            const size_t dyn = bdpt_path_smem(5 * (size_t)n, slots, 0, 0);
             const size_t lds = 160 * 1024, fine = lds / (dyn + stat), half = lds / (dyn + stat - 2048);
             if (fine < (size_t)waves && half > fine) {
                 coarse = true;
@@ -838,8 +807,8 @@ static int fold_timing(bdpt_ctx* c, long long upto) {
         // 3.79 ms kernels + 1.10 ms fold -> 4.05 ms per call, two passes per lane 4.85 + 0.84 ->
         // 4.95, profiles/r04_s20_*)
         // (a call whose folds ran on its own stream after its path kernels is charged in full)
-        for (int r = 0; r < bdpt_ctx::kTunePhases; r++)
-            if (c->folded == c->tune_call[r]) c->tune_ms[r] = s.serial_fold ? (double)ms : kms + 0.25 * ((double)ms - kms);
+        for (int r = 0; r < kTuneRoles; r++)
+            if (c->folded == c->tuner.call[r]) c->tuner.set_ms(r, s.serial_fold ? (double)ms : kms + 0.25 * ((double)ms - kms));
         c->acc_launches += s.launches;
         s.pending = false;
     }
@@ -892,7 +861,7 @@ int bdpt_create(bdpt_ctx** out, const bdpt_sphere* spheres, unsigned n, int W, i
         fail(c, BDPT_EHIP, "%s: %s", #call, hipGetErrorString(e_)); return bail(BDPT_EHIP); } } while (0)
     CK(hipSetDevice(device));
     CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    if (const char* tv = getenv("BDPT_STREAMS_TUNE")) c->tune_enabled = atoi(tv) != 0;
+    if (const char* tv = getenv("BDPT_STREAMS_TUNE")) c->tuner.enabled = atoi(tv) != 0;
     {
         // BDPT_FOLD_PRIORITY=high|low: the fold stream's priority (experiments; default normal)
         const char* fp = getenv("BDPT_FOLD_PRIORITY");
@@ -1018,7 +987,7 @@ static int one_set_shard(bdpt_ctx* c, int shard, int nshards, int band_rows) {
         return c ? fail(c, BDPT_EINVAL, "bdpt_set_shard: bad shard %d/%d band %d", shard, nshards, band_rows)
                  : BDPT_EINVAL;
     c->shard = shard; c->nshards = nshards; c->band_rows = band_rows;
-    c->tune_phase = 0;
+    c->tuner.reset();
     if (c->cpu) bdpt_cpu_set_shard(c->cpu, shard, nshards, band_rows);
     return BDPT_OK;
 }
@@ -1028,17 +997,14 @@ static int one_set_streams(bdpt_ctx* c, int streams) {
     if (streams < BDPT_STREAMS_PER_LANE || streams > BDPT_MAX_STREAMS)
         return fail(c, BDPT_EINVAL, "bdpt_set_streams: bad stream count %d", streams);
     c->streams_req = streams;
-    c->tune_phase = 0;
+    c->tuner.reset();
     return BDPT_OK;
 }
 
 int bdpt_last_streams(const bdpt_ctx* c) { return c ? c->last_streams : BDPT_EINVAL; }
 
 static int choice_of(const bdpt_ctx* c) {
-    if (c->streams_req != 0 || !c->tune_enabled || c->tune_phase != bdpt_ctx::kTunePhases + 1) return 0;
-    return BDPT_CHOICE_DECIDED | (c->tune_fused ? BDPT_CHOICE_FUSED : 0) | (c->tune_pair ? BDPT_CHOICE_PAIRED : 0) |
-           (c->tune_quarter ? BDPT_CHOICE_QUARTER : 0) | (c->tune_pool ? BDPT_CHOICE_POOLS : 0) |
-           (c->tune_units ? BDPT_CHOICE_UNITS : 0);
+    return c->streams_req == 0 ? c->tuner.choice() : 0;
 }
 
 static int one_set_stream_choice(bdpt_ctx* c, int choice) {
@@ -1048,13 +1014,7 @@ static int one_set_stream_choice(bdpt_ctx* c, int choice) {
         return fail(c, BDPT_EINVAL, "bdpt_set_stream_choice: bad choice 0x%x", choice);
     if (c->streams_req != 0)
         return fail(c, BDPT_ESTATE, "bdpt_set_stream_choice: the stream mode is not auto (%d)", c->streams_req);
-    c->tune_fused = (choice & BDPT_CHOICE_FUSED) != 0;
-    c->tune_pair = (choice & BDPT_CHOICE_PAIRED) != 0;
-    c->tune_quarter = (choice & BDPT_CHOICE_QUARTER) != 0;
-    c->tune_pool = (choice & BDPT_CHOICE_POOLS) != 0;
-    c->tune_units = (choice & BDPT_CHOICE_UNITS) != 0;
-    c->tune_enabled = true;
-    c->tune_phase = bdpt_ctx::kTunePhases + 1;
+    c->tuner.set_choice(choice);
     return BDPT_OK;
 }
 
@@ -1064,7 +1024,7 @@ static int one_set_specialize(bdpt_ctx* c, int on) {
     if (!c) return BDPT_EINVAL;
     c->specialize = on != 0;
     jit_forget(c);
-    c->tune_phase = 0;
+    c->tuner.reset();
     return BDPT_OK;
 }
 
@@ -1077,7 +1037,7 @@ static int one_set_traversal(bdpt_ctx* c, int mode) {
     if (mode != BDPT_TRAVERSE_AUTO && mode != BDPT_TRAVERSE_BRUTE && mode != BDPT_TRAVERSE_BVH)
         return fail(c, BDPT_EINVAL, "bdpt_set_traversal: bad mode %d", mode);
     c->traversal = mode;
-    c->tune_phase = 0;
+    c->tuner.reset();
     return BDPT_OK;
 }
 
@@ -1211,36 +1171,26 @@ static void camera_args(const bdpt_ctx* c, const bdpt_camera& cam, bdpt_path_arg
 }
 static void camera_args(const bdpt_ctx* c, bdpt_path_args& a) { camera_args(c, c->cam, a); }
 
-static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int npass) {
-    if (!c) return BDPT_EINVAL;
-    if (npass < 0 || (npass > 0 && (!sid || !vlp))) return fail(c, BDPT_EINVAL, "bdpt_path_passes: bad pass list");
-    if (npass == 0) return BDPT_OK;
-    if (!c->rand_ready) return fail(c, BDPT_ESTATE, "bdpt_path_passes: no random table (run the light pass first)");
-    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_path_passes: camera not set");
-    if (c->cpu) {                                           // synchronous; wall-clock timing
-        const auto t0 = std::chrono::steady_clock::now();
-        bdpt_cpu_path_passes(c->cpu, sid, vlp, npass);
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        c->last_ms = (float)ms;
-        c->acc_ms += ms;
-        c->acc_kernel_ms += ms;
-        c->acc_launches += 1;
-        c->last_streams = 1;
-        c->last_specialized = false;
-        c->last_bvh = false;
-        c->last_features = 0;
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    // this call's ring slot was last used kRing calls ago: wait for (only) that call
-    const int slot = (int)(c->issued % bdpt_ctx::kRing);
-    if (int rc = fold_timing(c, c->issued - bdpt_ctx::kRing + 1)) return rc;
-    // every launch carries its pass table (<= 128 passes: the launch cap below) in the kernel
-    // arguments: no upload, no copy kernel (and its gap) before the path kernel
-    static_assert(BDPT_DEV_INLINE_PASSES >= 128, "launches of up to 128 passes");
-    bdpt_ctx::call_slot& cs = c->ring[slot];
+// ---- bdpt_path_passes: the steps of one call, in the order one_path_passes runs them.  What a
+// call launches is decided in bdpt_plan.h; the functions below issue it. ----
 
-    bdpt_path_args a;
+static int cpu_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int npass) {
+    const auto t0 = std::chrono::steady_clock::now();       // synchronous; wall-clock timing
+    bdpt_cpu_path_passes(c->cpu, sid, vlp, npass);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->last_ms = (float)ms;
+    c->acc_ms += ms;
+    c->acc_kernel_ms += ms;
+    c->acc_launches += 1;
+    c->last_streams = 1;
+    c->last_specialized = false;
+    c->last_bvh = false;
+    c->last_features = 0;
+    return BDPT_OK;
+}
+
+// The argument fields every launch of the context shares, whatever the plan.
+static int path_args_base(bdpt_ctx* c, bdpt_path_args& a) {
     memset(&a, 0, sizeof(a));
     a.sph = c->d_sph;
     a.n = (unsigned)c->spheres.size();
@@ -1265,415 +1215,376 @@ static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int
         HIPCHK(c, hipMemset(c->d_prof, 0, 24 * sizeof(unsigned long long)));
     }
     a.prof = c->d_prof;
+    return BDPT_OK;
+}
 
-    // Grid rows: every tile row, or (bands a whole number of tile rows) only this shard's bands.
-    const int tile_rows = (c->H + BDPT_BTH - 1) / BDPT_BTH;
-    int grid_rows = tile_rows;
-    a.tiles_per_band = 0;
-    if (c->nshards > 1 && c->band_rows % BDPT_BTH == 0) {
-        const int tpb = c->band_rows / BDPT_BTH;
-        const int nbands = (c->H + c->band_rows - 1) / c->band_rows;
-        const int owned = c->shard < nbands ? (nbands - c->shard + c->nshards - 1) / c->nshards : 0;
-        a.tiles_per_band = tpb;
-        grid_rows = owned * tpb;
-        // only the frame's last band can be partial: launch none of its tile rows below the frame
-        if (owned > 0) {
-            const int last = c->shard + (owned - 1) * c->nshards;          // this shard's last band
-            const int tail = (last + 1) * tpb - tile_rows;
-            if (tail > 0) grid_rows -= tail;
-        }
+// The plan's part of the arguments: the shard's grid and, for a plan that traverses it, the BVH.
+static void path_args_plan(const bdpt_ctx* c, const bdpt_plan& plan, bdpt_path_args& a) {
+    a.tiles_per_band = plan.tiles_per_band;
+    a.nloc = (int)plan.lanes;
+    if (!plan.bvh) return;
+    a.bvh_nodes = c->d_bvh_nodes; a.bvh_geom = c->d_bvh_geom; a.bvh_ids = c->d_bvh_ids;
+    a.big_geom = c->d_big_geom; a.big_ids = c->d_big_ids; a.mat = c->d_mat;
+    a.bvh_nn = c->bvh_nn; a.bvh_ns = c->bvh_ns; a.big_n = c->big_n;
+    for (int k = 0; k < 3; k++) a.bvh_c[k] = c->bvh_c[k];
+    a.bvh_r = c->bvh_r;
+    a.bvh_q = c->bvh_q;
+}
+
+// Auto stream mode with every role's call issued: a group peer takes the decision of devices[0]
+// once that exists; otherwise wait for the last measured call and decide.
+static int settle_stream_mode(bdpt_ctx* c) {
+    bdpt_tuner& t = c->tuner;
+    if (c->streams_req != 0 || !t.enabled || t.measuring() || t.decided()) return BDPT_OK;
+    const bdpt_ctx* lead = c->group_leader;
+    if (lead && lead->streams_req == 0 && lead->tuner.decided()) {
+        t.adopt(lead->tuner);
+        return BDPT_OK;
     }
-    // Pass streams: auto = one pass per lane (S = the launch's pass count).  Eye paths are capped
-    // at 7 segments and most reach the cap, so single-path lanes keep a wave almost perfectly
-    // balanced, while a lane that regenerates through many passes waits for the wave's slowest
-    // sum (+11.7 % at 1080p, and it fills the GPU when a shard has few pixels).
-    const long lanes = (long)grid_rows * BDPT_BTH * c->W;
-    int S = c->streams_req;
-    if (S <= 0) S = BDPT_MAX_STREAMS;
-    // auto: measure both kernels on the first two calls, then keep the faster
-    int tune_role = -1;
-    bool pair = true;                                        // fused kernel: paired segment loads
-    if (c->streams_req == 0 && c->tune_enabled) {
-        const bdpt_ctx* lead = c->tune_leader;
-        if (c->tune_phase == bdpt_ctx::kTunePhases && lead && lead->streams_req == 0 &&
-            lead->tune_phase == bdpt_ctx::kTunePhases + 1) {  // a group peer: devices[0] decided
-            c->tune_fused = lead->tune_fused;
-            c->tune_pair = lead->tune_pair;
-            c->tune_quarter = lead->tune_quarter;
-            c->tune_pool = lead->tune_pool;
-            c->tune_units = lead->tune_units;
-            c->tune_phase = bdpt_ctx::kTunePhases + 1;
-        }
-        if (c->tune_phase == bdpt_ctx::kTunePhases) {        // waits for the last measured call
-            if (int rc = fold_timing(c, c->tune_call[bdpt_ctx::kTunePhases - 1] + 1)) return rc;
-            const double inf = std::numeric_limits<double>::infinity();
-            auto per = [&](int r) { return c->tune_real[r] ? c->tune_ms[r] / c->tune_npass[r] : inf; };
-            const double half = std::min(per(0), per(3)), quarter = std::min(per(2), per(5));
-            const double pooled = std::min(per(6), per(7)), units = std::min(per(8), per(9));
-            const double fp = per(1), fn = per(4);
-            c->tune_pair = !(fn < fp);                       // the default unless unpaired was measured faster
-            c->tune_quarter = quarter < half;
-            c->tune_pool = pooled < std::min(half, quarter) && !(units < pooled);
-            c->tune_units = units < std::min(std::min(half, quarter), pooled);
-            const double fused = c->tune_pair ? fp : fn;
-            const double streams = std::min(std::min(std::min(half, quarter), pooled), units);
-            c->tune_fused = fused * (1.0 + bdpt_ctx::kTuneMargin) < streams;
-            c->tune_phase = bdpt_ctx::kTunePhases + 1;
-        }
-        if (c->tune_phase < bdpt_ctx::kTunePhases && npass >= 2) {
-            tune_role = c->tune_phase;
-            if (tune_role == 1 || tune_role == 4) S = 1;
-            pair = tune_role != 4;
-        } else if (c->tune_phase == bdpt_ctx::kTunePhases + 1 && c->tune_fused) {
-            S = 1;
-            pair = c->tune_pair;
-        }
+    if (int rc = fold_timing(c, t.call[kTuneRoles - 1] + 1)) return rc;
+    t.decide();
+    return BDPT_OK;
+}
+
+// The pass-stream radiance buffer and the pools' mask (two halves each), grown to the plan's
+// largest launch; the in-kernel fold needs neither.
+static int ensure_radiance_buffers(bdpt_ctx* c, const bdpt_plan& plan, int npass) {
+    if (plan.S <= 1 || plan.want_units) return BDPT_OK;
+    const size_t lanes = (size_t)plan.lanes;
+    const size_t need = (size_t)(npass < plan.chunk ? npass : plan.chunk) * lanes;
+    if (need <= c->rbuf_cap && lanes <= c->rmask_lanes) return BDPT_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // queued passes and folds may use it
+    HIPCHK(c, hipStreamSynchronize(c->fstream));
+    for (hipStream_t ps : c->pstream)
+        if (ps) HIPCHK(c, hipStreamSynchronize(ps));
+    if (c->d_rbuf) HIPCHK(c, hipFree(c->d_rbuf));
+    if (c->d_rmask) HIPCHK(c, hipFree(c->d_rmask));
+    c->d_rbuf = nullptr;
+    c->d_rmask = nullptr;
+    c->rbuf_cap = 0;
+    c->rb_used[0] = c->rb_used[1] = false;
+    if (hipMalloc(&c->d_rbuf, 2 * sizeof(bdpt_dev_vec) * need) != hipSuccess)
+        return fail(c, BDPT_ENOMEM, "bdpt_path_passes: pass-stream buffer (2 x %zu B)", sizeof(bdpt_dev_vec) * need);
+    if (hipMalloc(&c->d_rmask, 2 * 16 * lanes) != hipSuccess)
+        return fail(c, BDPT_ENOMEM, "bdpt_path_passes: pass-stream mask (2 x %zu B)", 16 * lanes);
+    c->rmask_lanes = lanes;
+    c->rbuf_cap = need;
+    // touch every page now (queued before this call's timing event): the first launch
+    // would otherwise pay the first-touch cost, and the stream-mode measurement with it
+    HIPCHK(c, hipMemsetAsync(c->d_rbuf, 0, 2 * sizeof(bdpt_dev_vec) * need, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_rmask, 0, 2 * 16 * lanes, c->stream));
+    return BDPT_OK;
+}
+
+// The specialised kernels of a call by bdpt_launch_kernel (nullptr: the precompiled instance runs),
+// and what its launches need besides.
+struct path_kernels {
+    hipFunction_t jf[BDPT_KERNEL_KINDS] = {};
+    bool any_fused = false, any_streams = false;
+    bool use_srec = false;          // the pass-stream launches read sample records
+};
+
+// Resolve the specialised kernels (a compile on first use) and build the derived table the call's
+// pass-stream kernels read, both before the timed region starts.
+static int resolve_path_kernels(bdpt_ctx* c, const bdpt_plan& plan, int npass, bdpt_path_args& a, path_kernels& k) {
+    for (int p0 = 0; plan.grid_rows > 0 && p0 < npass; p0 += plan.chunk) {
+        const int np = npass - p0 < plan.chunk ? npass - p0 : plan.chunk;
+        const bool st = (plan.S < np ? plan.S : np) > 1;
+        k.any_fused |= !st;
+        k.any_streams |= st;
+        if (plan.bvh) continue;
+        hipFunction_t& pool = k.jf[BDPT_KERNEL_POOL], &units = k.jf[BDPT_KERNEL_UNITS];
+        if (st && plan.want_pool && !pool) pool = jit_path_kernel(c, true, true, true);
+        if (st && plan.want_units && !units) units = jit_path_kernel(c, true, true, false, true);
+        if (st && !pool && !units && !k.jf[BDPT_KERNEL_STREAMS]) k.jf[BDPT_KERNEL_STREAMS] = jit_path_kernel(c, true);
+        if (!st && !k.jf[BDPT_KERNEL_FUSED]) k.jf[BDPT_KERNEL_FUSED] = jit_path_kernel(c, false, plan.pair);
     }
-    a.nloc = (int)lanes;
-    dim3 grid((c->W + BDPT_BTW - 1) / BDPT_BTW, grid_rows, 1), block(256);
-    // keep single launches bounded (~2^28 samples, <= 128 passes for the LDS pass tables)
-    const long per_pass = lanes > 0 ? lanes : 1;
-    int chunk = (int)((1L << 28) / per_pass);
-    if (chunk < 1) chunk = 1;
-    if (chunk > 128) chunk = 128;
-    if (const char* mp = getenv("BDPT_MAX_LAUNCH_PASSES")) {   // experiments: smaller launches
-        const int m = atoi(mp);
-        if (m >= 1 && m < chunk) chunk = m;
-    }
-    if (S > chunk) S = chunk;
-    if (S > npass) S = npass;
-    if (S < 1) S = 1;
-    if (S == 1 && chunk > fused_max_passes()) chunk = fused_max_passes();   // fused: LDS per pass
-    // equal launches: 128 passes over a 4097 x 513-row band (chunk 126) are 2 x 64, not 126 + 2
-    if (npass > chunk) {
-        const int nch = (npass + chunk - 1) / chunk;
-        chunk = (npass + nch - 1) / nch;
-        if (S > chunk) S = chunk;
-    }
-    const bool bvh = c->has_bvh && (c->traversal == BDPT_TRAVERSE_BVH ||
-                                    (c->traversal == BDPT_TRAVERSE_AUTO && c->bvh_ns >= kBvhAutoSpheres));
-    // auto: the pass-stream kernel renders two passes per lane in launches of >= 4 passes (lanes
-    // whose first path ends early start the second in groups, bdpt_kernels.hip BDPT_REGEN_STREAMS):
-    // cornell +0.6 %, cornell_glass +1.7 %, cornell_mirror +1.5 %; not for BVH traversal
-    // (complex -4.6 %: its lanes' traversal costs differ more than their path lengths)
-    // (four passes per lane when the measurement chose them, or to measure them; launches of >= 8)
-    bool quarter_ran = false;
-    if (c->streams_req == 0 && S >= 4 && !bvh) {
-        const bool quarter = tune_role >= 0 ? (tune_role == 2 || tune_role == 5)
-                                            : (c->tune_phase == bdpt_ctx::kTunePhases + 1 && c->tune_quarter);
-        quarter_ran = quarter && S >= 8;
-        S = quarter_ran ? (S + 3) / 4 : (S + 1) / 2;
-    }
-    // pixel pools: forced by BDPT_POOL=R, or measured (tuning roles 6, 7) and kept
-    const int penv = pool_env();
-    const bool want_pool = !bvh && S > 1 && penv != 0 &&
-                           (penv > 0 || (c->streams_req == 0 &&
-                                         (tune_role == 6 || tune_role == 7 ||
-                                          (tune_role < 0 && c->tune_phase == bdpt_ctx::kTunePhases + 1 &&
-                                           c->tune_pool))));
-    if (want_pool) S = chunk < npass ? chunk : npass;        // one pass per lane slice
-    // ordered in-kernel fold (units of a tile and a range of passes; no radiance buffer): forced by
-    // BDPT_UNITS=P (ranges of P passes), or measured (tuning roles 8, 9) and kept; not for shards
-    // whose tile workgroups cannot keep the chip busy with one range per tile (a tile's units run
-    // one after another)
-    const int uenv = units_env();
-    const bool units_fit = (long)((c->W + BDPT_BTW - 1) / BDPT_BTW) * grid_rows >= 2L * c->cus * 6;
-    const bool want_units = !bvh && S > 1 && !want_pool && uenv != 0 &&
-                            (uenv > 0 || (c->streams_req == 0 && units_fit &&
-                                          (tune_role >= 8 || (tune_role < 0 && c->tune_phase == bdpt_ctx::kTunePhases + 1 &&
-                                                              c->tune_units))));
-    const int unit_passes = uenv > 0 ? uenv : kUnitPasses;
-    c->last_streams = S;
-    const int kidx = bvh ? 17 : (a.n <= 16 ? (int)a.n : 0);
-    if (bvh) {
-        a.bvh_nodes = c->d_bvh_nodes; a.bvh_geom = c->d_bvh_geom; a.bvh_ids = c->d_bvh_ids;
-        a.big_geom = c->d_big_geom; a.big_ids = c->d_big_ids; a.mat = c->d_mat;
-        a.bvh_nn = c->bvh_nn; a.bvh_ns = c->bvh_ns; a.big_n = c->big_n;
-        for (int k = 0; k < 3; k++) a.bvh_c[k] = c->bvh_c[k];
-        a.bvh_r = c->bvh_r;
-        a.bvh_q = c->bvh_q;
-    }
-    c->last_bvh = bvh;
-    if (S > 1 && !want_units) {
-        const int cmax = npass < chunk ? npass : chunk;
-        const size_t need = (size_t)cmax * (size_t)lanes;
-        if (need > c->rbuf_cap || (size_t)lanes > c->rmask_lanes) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));     // queued passes and folds may use it
-            HIPCHK(c, hipStreamSynchronize(c->fstream));
-            for (hipStream_t ps : c->pstream)
-                if (ps) HIPCHK(c, hipStreamSynchronize(ps));
-            if (c->d_rbuf) HIPCHK(c, hipFree(c->d_rbuf));
-            if (c->d_rmask) HIPCHK(c, hipFree(c->d_rmask));
-            c->d_rbuf = nullptr;
-            c->d_rmask = nullptr;
-            c->rbuf_cap = 0;
-            c->rb_used[0] = c->rb_used[1] = false;
-            if (hipMalloc(&c->d_rbuf, 2 * sizeof(bdpt_dev_vec) * need) != hipSuccess)
-                return fail(c, BDPT_ENOMEM, "bdpt_path_passes: pass-stream buffer (2 x %zu B)", sizeof(bdpt_dev_vec) * need);
-            if (hipMalloc(&c->d_rmask, 2 * 16 * (size_t)lanes) != hipSuccess)
-                return fail(c, BDPT_ENOMEM, "bdpt_path_passes: pass-stream mask (2 x %zu B)", 16 * (size_t)lanes);
-            c->rmask_lanes = (size_t)lanes;
-            c->rbuf_cap = need;
-            // touch every page now (queued before this call's timing event): the first launch
-            // would otherwise pay the first-touch cost, and the stream-mode measurement with it
-            HIPCHK(c, hipMemsetAsync(c->d_rbuf, 0, 2 * sizeof(bdpt_dev_vec) * need, c->stream));
-            HIPCHK(c, hipMemsetAsync(c->d_rmask, 0, 2 * 16 * (size_t)lanes, c->stream));
-        }
-    }
-    const size_t nchunks = grid_rows > 0 ? (size_t)((npass + chunk - 1) / chunk) : 0;
-    while (cs.kev.size() < 2 * nchunks) {
-        hipEvent_t e;
-        HIPCHK(c, hipEventCreate(&e));
-        cs.kev.push_back(e);
-    }
-    // resolve the specialised kernels (a compile on first use) before the timed region starts
-    hipFunction_t jf_streams = nullptr, jf_fused = nullptr, jf_pool = nullptr, jf_units = nullptr;
-    bool any_fused = false, any_streams = false, pool_ran = false, units_ran = false;
-    for (int p0 = 0; grid_rows > 0 && p0 < npass; p0 += chunk) {
-        const int np = npass - p0 < chunk ? npass - p0 : chunk;
-        const bool st = (S < np ? S : np) > 1;
-        any_fused |= !st;
-        any_streams |= st;
-        if (bvh) continue;
-        if (st && want_pool && !jf_pool) jf_pool = jit_path_kernel(c, true, true, true);
-        if (st && want_units && !jf_units) jf_units = jit_path_kernel(c, true, true, false, true);
-        if (st && !jf_pool && !jf_units && !jf_streams) jf_streams = jit_path_kernel(c, true);
-        if (!st && !jf_fused) jf_fused = jit_path_kernel(c, false, pair);
-    }
-    // Pixel pools fold on the context's stream right after each path kernel (serial fold, over
+    // the derived table (the pooled build reads neither): sample records for a specialised build
+    // that has them, else the sin/cos planes -- built if the table changed since they last were
+    const bool pool = k.jf[BDPT_KERNEL_POOL] != nullptr;
+    k.use_srec = k.any_streams && !pool && (k.jf[BDPT_KERNEL_UNITS] || k.jf[BDPT_KERNEL_STREAMS]) && jit_srec_enabled();
+    const bool use_scp = k.any_streams && !pool && !k.use_srec;
+    if (k.use_srec)
+        if (int rc = ensure_srec(c)) return rc;
+    if (use_scp)
+        if (int rc = ensure_scp(c)) return rc;
+    a.scp = k.use_srec ? (const float2*)c->d_srec : use_scp ? c->d_scp : nullptr;
+    return BDPT_OK;
+}
+
+// The LDS table terms of the call's launches (bdpt_plan.h bdpt_path_smem): scene tables (4 per
+// sphere + the non-emitters, or the BVH: 2 per node + 1 per sphere) and BVH sphere ids.
+static void path_lds_table(const bdpt_path_args& a, bool bvh, size_t* tab, size_t* ids) {
+#ifdef BDPT_BVH_LDS
+    const size_t tree = 2 * (size_t)a.bvh_nn + a.bvh_ns, tree_ids = a.bvh_ns;
+#else
+    const size_t tree = 0, tree_ids = 0;                     // tree read through L1/L2
+#endif
+    *tab = bdpt_path_tab(bvh, a.n, (size_t)a.n_vac, tree, (size_t)a.big_n);
+    *ids = bvh ? tree_ids + a.big_n : 0;
+}
+
+// A call between begin_call and end_call.
+struct path_call {
+    bdpt_ctx::call_slot* cs = nullptr;
+    // Pixel pools fold on the launch's stream right after each path kernel (serial fold, over
     // their sparse radiance): the concurrent fold's HBM traffic slowed the next call's pooled path
     // kernel more than the fold costs on its own -- caustic pools 4.10 -> 4.04-4.07 ms per call,
     // path kernel 3.93 -> 3.29-3.31 ms; two passes per lane keep the concurrent fold (cornell
     // S = 64 33.82 -> 33.92 ms serial), profiles/r05_s11_serial_fold.txt.
-    // the derived table this call's pass-stream kernels read (the pooled build reads neither):
-    // sample records for a specialised build that has them, else the sin/cos planes -- built here,
-    // before the call's timing starts, if the table changed since they were last built
-    const bool use_srec = any_streams && !jf_pool && (jf_units || jf_streams) && jit_srec_enabled();
-    const bool use_scp = any_streams && !jf_pool && !use_srec;
-    if (use_srec)
-        if (int rc = ensure_srec(c)) return rc;
-    if (use_scp)
-        if (int rc = ensure_scp(c)) return rc;
-    a.scp = use_srec ? (const float2*)c->d_srec : use_scp ? c->d_scp : nullptr;
-    const bool serial_fold = jf_pool != nullptr;
-    // Pooled launches overlap: each runs (with its fold) on pstream[half], so a launch's drain --
-    // ~0.1 ms at its end, when all passes' pools run out together and the last paths finish at
-    // falling occupancy -- overlaps the next launch's start (caustic8 +1.1 to +1.7 %, its 1/4 and
-    // 1/8 shares +4 to +6 %, profiles/r05_s37_pool_overlap.txt).  Not in the stream mode's tuning
-    // calls (measured one at a time, as the other modes); BDPT_POOL_OVERLAP=0 turns it off.
-    static const bool overlap_env = !getenv("BDPT_POOL_OVERLAP") || atoi(getenv("BDPT_POOL_OVERLAP")) != 0;
-    const bool overlap = serial_fold && overlap_env && tune_role < 0;
+    bool serial_fold = false;
+    bool overlap = false;           // pooled launches on the pstreams (bdpt_plan.h bdpt_plan_overlap)
+    bool ev0_done = false;
+    int launches = 0;
+    bool pool_ran = false, units_ran = false;
+};
+
+// Order the call behind the outstanding fold where it must be, and start its timing.
+static int begin_call(bdpt_ctx* c, const bdpt_plan& plan, const bdpt_path_env& env, const path_kernels& k,
+                      path_call& call) {
+    call.serial_fold = k.jf[BDPT_KERNEL_POOL] != nullptr;
+    call.overlap = bdpt_plan_overlap(plan, env, call.serial_fold);
     // a fused launch updates colors itself, and a serial fold does so on this stream: they wait
     // for the outstanding concurrent fold, before the call's timing starts (so the stream-mode
     // measurement does not charge that fold to it); overlapped pooled launches order their folds
     // through rb_fold_ev instead
-    if (any_fused || jf_units || (serial_fold && !overlap))
+    if (k.any_fused || k.jf[BDPT_KERNEL_UNITS] || (call.serial_fold && !call.overlap))
         if (int rc = join_fold(c)) return rc;
-    if (overlap) {
+    if (call.overlap) {
         if (!c->pstream[0]) {
             for (hipStream_t& ps : c->pstream) HIPCHK(c, hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
             HIPCHK(c, hipEventCreateWithFlags(&c->amark, hipEventDisableTiming));
         }
         HIPCHK(c, hipEventRecord(c->amark, c->stream));  // the pstreams follow `stream`'s earlier work
     }
-    bool ev0_done = !overlap;
-    if (!overlap) HIPCHK(c, hipEventRecord(cs.ev0, c->stream));
-    int launches = 0;
-    for (int p0 = 0; grid_rows > 0 && p0 < npass; p0 += chunk, launches++) {
-        a.npass = npass - p0 < chunk ? npass - p0 : chunk;
-        a.sid = nullptr;
-        a.vlp = nullptr;
-        for (int q = 0; q < a.npass; q++) {
-            a.sid_inl[q] = sid[p0 + q];
-            a.vlp_inl[q] = vlp[p0 + q];
-        }
-        // scene tables (4 per sphere, or the BVH: 2 per node + 1 per sphere) + per-pass VLPs +
-        // camera + 4 wave shadow queues (results written over maxt) + sids (+ BVH sphere ids)
-#ifdef BDPT_BVH_LDS
-        const size_t tree = 2 * (size_t)a.bvh_nn + a.bvh_ns, tree_ids = a.bvh_ns;
-#else
-        const size_t tree = 0, tree_ids = 0;                 // tree read through L1/L2
-#endif
-        const size_t tab = bvh ? tree + a.big_n : 4 * (size_t)a.n + (size_t)a.n_vac;   // (bdpt_kernels.hip ntab)
-        const size_t ids = bvh ? tree_ids + a.big_n : 0;
-        // S per launch: a short last chunk gets no idle stream slices
-        const bool st = (S < a.npass ? S : a.npass) > 1;     // the pass-stream kernel
-        const bool pooled = st && jf_pool != nullptr;        // its pixel-pool build
-        const bool unitsl = st && jf_units != nullptr;       // its ordered in-kernel fold build
-        a.streams = S < a.npass ? S : a.npass;
-        if (unitsl) a.unit_passes = unit_passes < a.npass ? unit_passes : a.npass;
-        // a workgroup stages the VLPs and sids of its own passes only (bdpt_kernels.hip nslot)
-        const size_t slots = unitsl ? (size_t)a.unit_passes : ((size_t)a.npass + a.streams - 1) / a.streams;
-        size_t smem = sizeof(float4) * (tab + 3 * slots + 5 + 4 * 128 * 2)
-                      + sizeof(unsigned) * (slots + ids);
-        if (const char* pad = getenv("BDPT_SMEM_PAD"))       // experiments: cap workgroups per CU
-            smem += (size_t)atoi(pad);
-        if (smem > 160 * 1024)
-            return fail(c, BDPT_EINVAL, "bdpt_path_passes: scene too large for LDS (%u spheres)", a.n);
-        const void* kern = bdpt_path_kernel_table[st * 18 + kidx];
-        const hipFunction_t jf = st ? (pooled ? jf_pool : unitsl ? jf_units : jf_streams) : jf_fused;
-        c->last_specialized = jf != nullptr;
-        c->last_features = BDPT_FEAT_LAST_SKIP | (bvh ? BDPT_FEAT_BVH : 0) | (st ? BDPT_FEAT_STREAMS : 0) |
-                           (pooled ? BDPT_FEAT_POOLS : 0) | (unitsl ? BDPT_FEAT_UNITS : 0) |
-                           (st && !pooled ? BDPT_FEAT_SCP : 0) | (st && use_srec ? BDPT_FEAT_SREC : 0) |
-                           (jf ? BDPT_FEAT_SPECIALIZED | BDPT_FEAT_DET_SKIP | (c->jit_zero_exit ? BDPT_FEAT_ZERO_EXIT : 0) : 0);
-        void* kargs[] = {&a};
-        grid.z = a.streams;
-        const int half = c->rb_next;
-        // the stream of this launch (and of its fold): `stream`, or pstream[half] for an
-        // overlapped pooled launch
-        hipStream_t ls = c->stream;
-        if (pooled && overlap) {
-            ls = c->pstream[half];
-            HIPCHK(c, hipStreamWaitEvent(ls, c->amark, 0));
-        }
-        if (!ev0_done) {                                     // the call's time starts here
-            HIPCHK(c, hipEventRecord(cs.ev0, ls));
-            ev0_done = true;
-        }
-        if (unitsl) {
-            // the units fold in the kernel: no radiance buffer; the previous call's folds were
-            // joined above
-            a.rbuf = nullptr;
-            a.rmask = nullptr;
-        } else if (st) {
-            // this half was last read by the fold of the launch before the previous one
-            if (c->rb_used[half]) HIPCHK(c, hipStreamWaitEvent(ls, c->rb_fold_ev[half], 0));
-            a.rbuf = c->d_rbuf + (size_t)half * c->rbuf_cap;
-            a.rmask = c->d_rmask + (size_t)half * 4 * c->rmask_lanes;
-            // pools mark their stored samples in the mask: cleared first (the fold that read this
-            // half ran earlier on this stream)
-            if (jf_pool) HIPCHK(c, hipMemsetAsync(a.rmask, 0, 16 * (size_t)lanes, ls));
-        } else if (int rc = join_fold(c)) {                  // the fused kernel updates colors itself
-            return rc;
-        }
-        // pixel pools (a specialised pass-stream build with BDPT_POOL): waves of pool x 64 pixels
-        dim3 pgrid = grid;
-        a.pool = 0;
-        a.pool_ctr = nullptr;
-        if (pooled) {                                        // per pass 8 counters, a 128-B line each
-            if (a.streams != a.npass || a.npass > 128)
-                return fail(c, BDPT_EINVAL, "bdpt_path_passes: pixel pools need one pass per stream (%d of %d)",
-                            a.streams, a.npass);
-            constexpr size_t kSet = 128 * 8 * 32;            // words per set
-            if (!c->d_poolctr) {
-                HIPCHK(c, hipMalloc(&c->d_poolctr, 2 * kSet * sizeof(unsigned)));
-                HIPCHK(c, hipMemsetAsync(c->d_poolctr, 0, 2 * kSet * sizeof(unsigned), c->stream));
-                c->pool_set = 0;
-            }
-            int R = 1, G = 1;
-            pool_shape(lanes, overlap, &R, &G);
-            a.pool = R;
-            if (overlap) {
-                // set `half`, cleared on this launch's stream (its previous user, the launch two
-                // back, ran earlier on the same stream); the kernel clears no next set
-                a.pool_ctr = c->d_poolctr + (size_t)half * kSet;
-                a.pool_ctr_next = nullptr;
-                HIPCHK(c, hipMemsetAsync(a.pool_ctr, 0, kSet * sizeof(unsigned), ls));
-                c->pool_dirty = true;
-            } else {
-                if (c->pool_dirty) {                         // overlapped launches left both sets used
-                    HIPCHK(c, hipMemsetAsync(c->d_poolctr, 0, 2 * kSet * sizeof(unsigned), c->stream));
-                    c->pool_dirty = false;
-                }
-                a.pool_ctr = c->d_poolctr + (size_t)c->pool_set * kSet;
-                a.pool_ctr_next = c->d_poolctr + (size_t)(c->pool_set ^ 1) * kSet;
-                c->pool_set ^= 1;
-            }
-            // 1-D, passes interleaved in groups of 8 workgroups (bdpt_kernels.hip s0)
-            const long span = 256L * G, per = ((lanes + span - 1) / span + 7) / 8 * 8;
-            pgrid = dim3((unsigned)(per * a.streams), 1, 1);
-            pool_ran = true;
-        }
-        if (unitsl) {
-            // one workgroup per unit; each claims its unit from its XCD's queue (bdpt_kernels.hip)
-            const int wgs = (int)grid.x * grid_rows;
-            // the last passes in halving ranges (bdpt_device.h bdpt_unit_range); BDPT_UNITS_TAPER=0 off
-            static const int taper = getenv("BDPT_UNITS_TAPER") ? atoi(getenv("BDPT_UNITS_TAPER")) != 0 : 1;
-            a.unit_taper = taper;
-            const int nranges = bdpt_unit_ranges(a.npass, a.unit_passes, a.unit_taper);
-            const size_t nflags = (size_t)wgs * 4;
-            if (!c->d_uerr) {                                // error word + 8 queue counters, 128 B apart
-                HIPCHK(c, hipMalloc(&c->d_uerr, sizeof(unsigned) * (32 + 8 * 32)));
-                HIPCHK(c, hipMemsetAsync(c->d_uerr, 0, sizeof(unsigned), c->stream));
-            }
-            HIPCHK(c, hipMemsetAsync(c->d_uerr + 32, 0, sizeof(unsigned) * 8 * 32, c->stream));
-            if (nflags > c->uflags_cap || ((c->uepoch + 1) & 0xffffffu) == 0) {
-                if (nflags > c->uflags_cap) {
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    if (c->d_uflags) HIPCHK(c, hipFree(c->d_uflags));
-                    c->d_uflags = nullptr;
-                    HIPCHK(c, hipMalloc(&c->d_uflags, sizeof(unsigned) * nflags));
-                    c->uflags_cap = nflags;
-                }
-                HIPCHK(c, hipMemsetAsync(c->d_uflags, 0, sizeof(unsigned) * c->uflags_cap, c->stream));
-                c->uepoch = 0;
-            }
-            c->uepoch++;                                     // tags never repeat within 2^24 launches
-            a.unit_tag = c->uepoch << 8;
-            a.unit_flags = c->d_uflags;
-            a.unit_err = c->d_uerr;
-            a.unit_ctr = c->d_uerr + 32;
-            a.unit_wgs = wgs;
-            a.gx = (int)grid.x;
-            a.gy = grid_rows;
-            pgrid = dim3((unsigned)(wgs * nranges), 1, 1);
-            c->units_check = true;
-            units_ran = true;
-        }
-        HIPCHK(c, hipEventRecord(cs.kev[2 * launches], ls));
-        if (jf)
-            HIPCHK(c, hipModuleLaunchKernel(jf, pgrid.x, pgrid.y, pgrid.z, block.x, 1, 1, (unsigned)smem,
-                                            ls, kargs, nullptr));
-        else
-            HIPCHK(c, hipLaunchKernel(kern, grid, block, kargs, smem, ls));
-        HIPCHK(c, hipEventRecord(cs.kev[2 * launches + 1], ls));
-        const dim3 fgrid((unsigned)((lanes + 255) / 256), 1, 1);   // the fold: 1-D over the launch's rows
-        if (st && !unitsl && serial_fold) {                 // the fold after the path kernel
-            // (overlapped: after the previous fold too, wherever it ran)
-            if (overlap && c->fold_pending) HIPCHK(c, hipStreamWaitEvent(ls, c->rb_fold_ev[c->fold_last], 0));
-            HIPCHK(c, hipLaunchKernel((const void*)&bdpt_accum_serial_kernel, fgrid, block, kargs, 0, ls));
-            if (overlap) {
-                HIPCHK(c, hipEventRecord(c->rb_fold_ev[half], ls));
-                c->rb_used[half] = true;
-                c->fold_last = half;
-                c->fold_pending = true;
-                c->fold_stream = ls;
-                c->rb_next = half ^ 1;
-            }
-        } else if (st && !unitsl) {                         // the ordered fold, on fstream
-            HIPCHK(c, hipEventRecord(c->rb_path_ev[half], c->stream));
-            HIPCHK(c, hipStreamWaitEvent(c->fstream, c->rb_path_ev[half], 0));
-            // after the previous fold (an overlapped pooled launch's ran on a pstream)
-            if (c->fold_pending && c->fold_stream != c->fstream)
-                HIPCHK(c, hipStreamWaitEvent(c->fstream, c->rb_fold_ev[c->fold_last], 0));
-            c->fold_stream = c->fstream;
-            HIPCHK(c, hipLaunchKernel((const void*)&bdpt_accum_kernel, fgrid, block, kargs, 0, c->fstream));
-            HIPCHK(c, hipEventRecord(c->rb_fold_ev[half], c->fstream));
-            c->rb_used[half] = true;
-            c->fold_last = half;
-            c->fold_pending = true;
-            c->rb_next = half ^ 1;
-        }
+    call.ev0_done = !call.overlap;                       // (overlapped: the first launch's stream starts it)
+    if (!call.overlap) HIPCHK(c, hipEventRecord(call.cs->ev0, c->stream));
+    return BDPT_OK;
+}
+
+// Pixel pools (a specialised pass-stream build with BDPT_POOL): the chunk size and the launch's
+// claim counters, per pass 8 of them, a 128-B line each.
+static int prepare_pool_launch(bdpt_ctx* c, const bdpt_launch& L, hipStream_t ls, int half, bdpt_path_args& a) {
+    if (L.streams != L.npass || L.npass > 128)
+        return fail(c, BDPT_EINVAL, "bdpt_path_passes: pixel pools need one pass per stream (%d of %d)",
+                    L.streams, L.npass);
+    constexpr size_t kSet = 128 * 8 * 32;                // words per set
+    if (!c->d_poolctr) {
+        HIPCHK(c, hipMalloc(&c->d_poolctr, 2 * kSet * sizeof(unsigned)));
+        HIPCHK(c, hipMemsetAsync(c->d_poolctr, 0, 2 * kSet * sizeof(unsigned), c->stream));
+        c->pool_set = 0;
     }
+    a.pool = L.pool;
+    if (L.overlap) {
+        // set `half`, cleared on this launch's stream (its previous user, the launch two
+        // back, ran earlier on the same stream); the kernel clears no next set
+        a.pool_ctr = c->d_poolctr + (size_t)half * kSet;
+        a.pool_ctr_next = nullptr;
+        HIPCHK(c, hipMemsetAsync(a.pool_ctr, 0, kSet * sizeof(unsigned), ls));
+        c->pool_dirty = true;
+    } else {
+        if (c->pool_dirty) {                             // overlapped launches left both sets used
+            HIPCHK(c, hipMemsetAsync(c->d_poolctr, 0, 2 * kSet * sizeof(unsigned), c->stream));
+            c->pool_dirty = false;
+        }
+        a.pool_ctr = c->d_poolctr + (size_t)c->pool_set * kSet;
+        a.pool_ctr_next = c->d_poolctr + (size_t)(c->pool_set ^ 1) * kSet;
+        c->pool_set ^= 1;
+    }
+    return BDPT_OK;
+}
+
+// The ordered in-kernel fold: one workgroup per unit, each claims its unit from its XCD's queue
+// (bdpt_kernels.hip); the queue counters, the tiles' flags and this launch's tag.
+static int prepare_units_launch(bdpt_ctx* c, const bdpt_plan& plan, const bdpt_launch& L, bdpt_path_args& a) {
+    const int wgs = plan.gx * plan.grid_rows;
+    a.unit_taper = L.unit_taper;
+    const size_t nflags = (size_t)wgs * 4;
+    if (!c->d_uerr) {                                    // error word + 8 queue counters, 128 B apart
+        HIPCHK(c, hipMalloc(&c->d_uerr, sizeof(unsigned) * (32 + 8 * 32)));
+        HIPCHK(c, hipMemsetAsync(c->d_uerr, 0, sizeof(unsigned), c->stream));
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_uerr + 32, 0, sizeof(unsigned) * 8 * 32, c->stream));
+    if (nflags > c->uflags_cap || ((c->uepoch + 1) & 0xffffffu) == 0) {
+        if (nflags > c->uflags_cap) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (c->d_uflags) HIPCHK(c, hipFree(c->d_uflags));
+            c->d_uflags = nullptr;
+            HIPCHK(c, hipMalloc(&c->d_uflags, sizeof(unsigned) * nflags));
+            c->uflags_cap = nflags;
+        }
+        HIPCHK(c, hipMemsetAsync(c->d_uflags, 0, sizeof(unsigned) * c->uflags_cap, c->stream));
+        c->uepoch = 0;
+    }
+    c->uepoch++;                                         // tags never repeat within 2^24 launches
+    a.unit_tag = c->uepoch << 8;
+    a.unit_flags = c->d_uflags;
+    a.unit_err = c->d_uerr;
+    a.unit_ctr = c->d_uerr + 32;
+    a.unit_wgs = wgs;
+    a.gx = plan.gx;
+    a.gy = plan.grid_rows;
+    c->units_check = true;
+    return BDPT_OK;
+}
+
+// The fold of a pass-stream launch's radiance half into colors (1-D over the launch's rows):
+// after the path kernel on its stream (pools), or on fstream beside the next path kernel.
+static int issue_fold(bdpt_ctx* c, const path_call& call, long lanes, hipStream_t ls, int half, void** kargs) {
+    const dim3 fgrid((unsigned)((lanes + 255) / 256), 1, 1), block(256);
+    if (call.serial_fold) {
+        // (overlapped: after the previous fold too, wherever it ran)
+        if (call.overlap && c->fold_pending) HIPCHK(c, hipStreamWaitEvent(ls, c->rb_fold_ev[c->fold_last], 0));
+        HIPCHK(c, hipLaunchKernel((const void*)&bdpt_accum_serial_kernel, fgrid, block, kargs, 0, ls));
+        if (!call.overlap) return BDPT_OK;
+        HIPCHK(c, hipEventRecord(c->rb_fold_ev[half], ls));
+        c->fold_stream = ls;
+    } else {                                             // the ordered fold, on fstream
+        HIPCHK(c, hipEventRecord(c->rb_path_ev[half], c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->fstream, c->rb_path_ev[half], 0));
+        // after the previous fold (an overlapped pooled launch's ran on a pstream)
+        if (c->fold_pending && c->fold_stream != c->fstream)
+            HIPCHK(c, hipStreamWaitEvent(c->fstream, c->rb_fold_ev[c->fold_last], 0));
+        c->fold_stream = c->fstream;
+        HIPCHK(c, hipLaunchKernel((const void*)&bdpt_accum_kernel, fgrid, block, kargs, 0, c->fstream));
+        HIPCHK(c, hipEventRecord(c->rb_fold_ev[half], c->fstream));
+    }
+    c->rb_used[half] = true;
+    c->fold_last = half;
+    c->fold_pending = true;
+    c->rb_next = half ^ 1;
+    return BDPT_OK;
+}
+
+// One launch: its pass table and mode fields, its radiance half, the path kernel between the
+// launch's two timing events, and its fold.
+static int launch_path_kernel(bdpt_ctx* c, const bdpt_plan& plan, const bdpt_launch& L, const path_kernels& k,
+                              path_call& call, bdpt_path_args& a, const unsigned* sid, const int* vlp) {
+    // every launch carries its pass table (<= 128 passes: the plan's cap) in the kernel
+    // arguments: no upload, no copy kernel (and its gap) before the path kernel
+    static_assert(BDPT_DEV_INLINE_PASSES >= 128, "launches of up to 128 passes");
+    a.npass = L.npass;
+    a.sid = nullptr;
+    a.vlp = nullptr;
+    for (int q = 0; q < L.npass; q++) {
+        a.sid_inl[q] = sid[q];
+        a.vlp_inl[q] = vlp[q];
+    }
+    a.streams = L.streams;
+    if (L.unitsl) a.unit_passes = L.unit_passes;
+    if (L.smem > 160 * 1024)
+        return fail(c, BDPT_EINVAL, "bdpt_path_passes: scene too large for LDS (%u spheres)", a.n);
+    const hipFunction_t jf = k.jf[L.kernel];
+    c->last_specialized = jf != nullptr;
+    c->last_features = L.features;
+    void* kargs[] = {&a};
+    const int half = c->rb_next;
+    // the stream of this launch (and of its fold): `stream`, or pstream[half] for an
+    // overlapped pooled launch
+    hipStream_t ls = c->stream;
+    if (L.overlap) {
+        ls = c->pstream[half];
+        HIPCHK(c, hipStreamWaitEvent(ls, c->amark, 0));
+    }
+    if (!call.ev0_done) {                                    // the call's time starts here
+        HIPCHK(c, hipEventRecord(call.cs->ev0, ls));
+        call.ev0_done = true;
+    }
+    if (L.unitsl) {
+        // the units fold in the kernel: no radiance buffer; the previous call's folds were
+        // joined in begin_call
+        a.rbuf = nullptr;
+        a.rmask = nullptr;
+    } else if (L.st) {
+        // this half was last read by the fold of the launch before the previous one
+        if (c->rb_used[half]) HIPCHK(c, hipStreamWaitEvent(ls, c->rb_fold_ev[half], 0));
+        a.rbuf = c->d_rbuf + (size_t)half * c->rbuf_cap;
+        a.rmask = c->d_rmask + (size_t)half * 4 * c->rmask_lanes;
+        // pools mark their stored samples in the mask: cleared first (the fold that read this
+        // half ran earlier on this stream)
+        if (L.pooled) HIPCHK(c, hipMemsetAsync(a.rmask, 0, 16 * (size_t)plan.lanes, ls));
+    } else if (int rc = join_fold(c)) {                      // the fused kernel updates colors itself
+        return rc;
+    }
+    a.pool = 0;
+    a.pool_ctr = nullptr;
+    if (L.pooled)
+        if (int rc = prepare_pool_launch(c, L, ls, half, a)) return rc;
+    if (L.unitsl)
+        if (int rc = prepare_units_launch(c, plan, L, a)) return rc;
+    call.pool_ran |= L.pooled;
+    call.units_ran |= L.unitsl;
+    const dim3 grid(L.grid[0], L.grid[1], L.grid[2]), block(256);
+    HIPCHK(c, hipEventRecord(call.cs->kev[2 * call.launches], ls));
+    if (jf)
+        HIPCHK(c, hipModuleLaunchKernel(jf, grid.x, grid.y, grid.z, block.x, 1, 1, (unsigned)L.smem, ls, kargs, nullptr));
+    else
+        HIPCHK(c, hipLaunchKernel(bdpt_path_kernel_table[L.st * 18 + plan.kidx], grid, block, kargs, L.smem, ls));
+    HIPCHK(c, hipEventRecord(call.cs->kev[2 * call.launches + 1], ls));
+    call.launches++;
+    return L.st && !L.unitsl ? issue_fold(c, call, plan.lanes, ls, half, kargs) : BDPT_OK;
+}
+
+// Close the call's timing and its ring slot, and tell the tuner what a measuring call ran.
+static int end_call(bdpt_ctx* c, const bdpt_plan& plan, const path_kernels& k, const path_call& call, int npass) {
     // the call ends with its last fold (fstream, which waited for the path kernels) if one is
     // outstanding, else on the context's stream
-    HIPCHK(c, hipEventRecord(cs.ev1, c->fold_pending ? c->fold_stream : c->stream));
-    cs.launches = launches;
-    cs.pending = true;
-    cs.serial_fold = serial_fold;
-    if (tune_role >= 0) {
-        c->tune_real[tune_role] = tune_role == 2 || tune_role == 5 ? quarter_ran
-                                  : tune_role == 1 || tune_role == 4 ? (jf_fused != nullptr || tune_role == 1)
-                                  : tune_role == 6 || tune_role == 7 ? pool_ran
-                                  : tune_role >= 8 ? units_ran
-                                  : true;
-        c->tune_call[tune_role] = c->issued;
-        c->tune_npass[tune_role] = npass;
-        c->tune_phase = tune_role + 1;
-    }
+    HIPCHK(c, hipEventRecord(call.cs->ev1, c->fold_pending ? c->fold_stream : c->stream));
+    call.cs->launches = call.launches;
+    call.cs->pending = true;
+    call.cs->serial_fold = call.serial_fold;
+    if (plan.tune_role >= 0)
+        c->tuner.record(plan.tune_role,
+                        bdpt_role_real(plan.tune_role, plan.quarter_ran, k.jf[BDPT_KERNEL_FUSED] != nullptr,
+                                       call.pool_ran, call.units_ran),
+                        c->issued, npass);
     c->issued++;
     return BDPT_OK;
+}
+
+static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int npass) {
+    if (!c) return BDPT_EINVAL;
+    if (npass < 0 || (npass > 0 && (!sid || !vlp))) return fail(c, BDPT_EINVAL, "bdpt_path_passes: bad pass list");
+    if (npass == 0) return BDPT_OK;
+    if (!c->rand_ready) return fail(c, BDPT_ESTATE, "bdpt_path_passes: no random table (run the light pass first)");
+    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_path_passes: camera not set");
+    if (c->cpu) return cpu_path_passes(c, sid, vlp, npass);
+    HIPCHK(c, hipSetDevice(c->device));
+    // this call's ring slot was last used kRing calls ago: wait for (only) that call
+    path_call call;
+    call.cs = &c->ring[c->issued % bdpt_ctx::kRing];
+    if (int rc = fold_timing(c, c->issued - bdpt_ctx::kRing + 1)) return rc;
+    bdpt_path_args a;
+    if (int rc = path_args_base(c, a)) return rc;
+    if (int rc = settle_stream_mode(c)) return rc;
+
+    const bdpt_path_env env = path_env();
+    const bdpt_plan_in in = {c->W, c->H, c->shard, c->nshards, c->band_rows, c->streams_req, npass, a.n,
+                             c->has_bvh, c->traversal, c->bvh_ns, kBvhAutoSpheres, c->cus};
+    const bdpt_plan plan = bdpt_plan_call(in, c->tuner, env);
+    c->last_streams = plan.S;
+    c->last_bvh = plan.bvh;
+    path_args_plan(c, plan, a);
+
+    if (int rc = ensure_radiance_buffers(c, plan, npass)) return rc;
+    while (call.cs->kev.size() < 2 * (size_t)plan.launches) {   // per launch {before, after}
+        hipEvent_t e;
+        HIPCHK(c, hipEventCreate(&e));
+        call.cs->kev.push_back(e);
+    }
+    path_kernels k;
+    if (int rc = resolve_path_kernels(c, plan, npass, a, k)) return rc;
+    size_t tab = 0, ids = 0;
+    path_lds_table(a, plan.bvh, &tab, &ids);
+
+    if (int rc = begin_call(c, plan, env, k, call)) return rc;
+    for (int p0 = 0; call.launches < plan.launches; p0 += plan.chunk) {
+        const bdpt_launch L = bdpt_plan_launch(plan, p0, npass, k.jf[BDPT_KERNEL_POOL] != nullptr,
+                                               k.jf[BDPT_KERNEL_UNITS] != nullptr, k.jf[BDPT_KERNEL_STREAMS] != nullptr,
+                                               k.jf[BDPT_KERNEL_FUSED] != nullptr, k.use_srec, c->jit_zero_exit, tab, ids, env);
+        if (int rc = launch_path_kernel(c, plan, L, k, call, a, sid + p0, vlp + p0)) return rc;
+    }
+    return end_call(c, plan, k, call, npass);
 }
 
 // After the stream has drained: did a unit's handover wait time out in a units launch since the
@@ -2056,7 +1967,7 @@ int bdpt_create_multi(bdpt_ctx** out, const bdpt_sphere* spheres, unsigned n, in
             snprintf(g_create_err, sizeof g_create_err, "%s", msg);
             return rc;
         }
-        p->tune_leader = c;
+        p->group_leader = c;
         c->peers.push_back(p);
     }
     if (int rc = group_set_shard(c, 0, 1, 8)) {

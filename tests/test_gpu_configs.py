@@ -187,6 +187,39 @@ def test_north_star_linf_cornell_513_1024spp(gpu, rnd0):
     r.close()
 
 
+def test_auto_stream_mode_measures_ten_roles_then_decides(gpu, rnd0, monkeypatch):
+    """The auto stream mode's whole sequence on a small frame (cornell 97x65, calls of 8 passes):
+    the first ten calls run the ten roles of bdpt_plan.h -- two passes per lane, fused, four per
+    lane, the three again with the unpaired fused kernel, pixel pools twice, and twice two per lane
+    where the units would run if the frame had the tile workgroups for them -- the eleventh decides,
+    and the 96 passes of the twelve calls equal the oracle's bit for bit."""
+    for v in ("BDPT_STREAMS_TUNE", "BDPT_POOL", "BDPT_UNITS", "BDPT_MAX_LAUNCH_PASSES"):
+        monkeypatch.delenv(v, raising=False)
+    W, H, n = 97, 65, 8
+    r, cam, sp = _setup("cornell", W, H, gpu)
+    sid, vlp = _schedule(12 * n)
+    want = [4, 1, 2, 4, 1, 2, 8, 8, 4, 4]
+    DECIDED, UNITS = 1, 32                                   # BDPT_CHOICE_* (include/bdpt.h)
+    for k in range(12):
+        r.path_passes(sid[k * n:(k + 1) * n], vlp[k * n:(k + 1) * n])
+        feats = r.last_features
+        print(f"call {k + 1}: S = {r.last_streams}, {feats}, choice {r.stream_choice:#x}")
+        if k < 10:
+            assert r.last_streams == want[k], (k, r.last_streams)
+            assert ("pixel_pools" in feats) == (k in (6, 7)), (k, feats)
+            assert "unit_fold" not in feats, (k, feats)
+            assert r.stream_choice == 0, (k, r.stream_choice)
+        else:                                                # decided when the eleventh call was issued
+            assert r.stream_choice & DECIDED and not r.stream_choice & UNITS, (k, r.stream_choice)
+    col, cnt = r.read_radiance()
+    lp = oracle.light_pass(sp, rnd0, 0)
+    ocol, ocnt, opix = oracle.path_passes(sp, rnd0, cam, W, H, lp, sid, vlp)
+    _same(cnt, ocnt, "counter")
+    _same(col, ocol, "colors")
+    _same(r.read_pixels(), opix, "pixels")
+    r.close()
+
+
 @pytest.mark.parametrize("name", ["cornell", "caustic", "cornell_glass"])
 def test_1080p_whole_frame_identical_in_every_kernel_mode(gpu, rnd0, name, monkeypatch):
     """Whole 1921x1081 frames (not sampled rows): the same 128 passes rendered by every kernel

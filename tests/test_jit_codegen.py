@@ -169,3 +169,15 @@ def test_unit_ranges_partition(tmp_path):
                            os.path.join(REPO, "tests", "native", "unit_ranges_check.cpp")])
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
+def test_path_pass_planner(tmp_path):
+    """The path-pass planner (bdpt_plan.h, what bdpt_path_passes launches: the shard grid, the cut
+    into launches and S, pools and units, the auto stream mode's roles, decision and choice bits,
+    and the LDS formula) against figures worked out by hand (tests/native/plan_check.cpp)."""
+    exe = tmp_path / "plan_check"
+    subprocess.check_call([HIPCC, "-O1", "-std=c++17", "-o", str(exe),
+                           os.path.join(REPO, "tests", "native", "plan_check.cpp")])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout
