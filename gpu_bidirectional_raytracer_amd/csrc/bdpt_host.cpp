@@ -1313,15 +1313,10 @@ static int resolve_path_kernels(bdpt_ctx* c, const bdpt_plan& plan, int npass, b
 }
 
 // The LDS table terms of the call's launches (bdpt_plan.h bdpt_path_smem): scene tables (4 per
-// sphere + the non-emitters, or the BVH: 2 per node + 1 per sphere) and BVH sphere ids.
+// sphere + the non-emitters, or the BVH's brute-force spheres) and those spheres' ids.
 static void path_lds_table(const bdpt_path_args& a, bool bvh, size_t* tab, size_t* ids) {
-#ifdef BDPT_BVH_LDS
-    const size_t tree = 2 * (size_t)a.bvh_nn + a.bvh_ns, tree_ids = a.bvh_ns;
-#else
-    const size_t tree = 0, tree_ids = 0;                     // tree read through L1/L2
-#endif
-    *tab = bdpt_path_tab(bvh, a.n, (size_t)a.n_vac, tree, (size_t)a.big_n);
-    *ids = bvh ? tree_ids + a.big_n : 0;
+    *tab = bdpt_path_tab(bvh, a.n, (size_t)a.n_vac, (size_t)a.big_n);
+    *ids = bvh ? a.big_n : 0;
 }
 
 // A call between begin_call and end_call.

@@ -7,6 +7,14 @@
 // steps of device.cu:565-566,594 kept in fp64, and sinf/cosf evaluated as (float)sincos((double)x).
 // Every float operation below is in the reference's order; reordering any of them changes
 // results (SURVEY.md 7 "Hard parts").
+
+// Switches whose experiment ended: the winning side is the code now, so a build that still passes
+// one would silently be the default build (and an A/B through it a kernel against itself).
+#if defined(BDPT_SCP) || defined(BDPT_SCP_LATE) || defined(BDPT_LG_RULE) || defined(BDPT_VAC_SKIP) || \
+    defined(BDPT_UNITS_FENCE) || defined(BDPT_BVH_LDS)
+#error "retired switch: BDPT_SCP, BDPT_SCP_LATE, BDPT_LG_RULE, BDPT_VAC_SKIP, BDPT_UNITS_FENCE and BDPT_BVH_LDS no longer exist (DESIGN_LOG.md, Retired path-kernel switches)"
+#endif
+
 #ifndef __HIPCC_RTC__                       // hipRTC provides the HIP runtime itself
 #include <hip/hip_runtime.h>
 #include <utility>
@@ -158,18 +166,7 @@ __device__ __forceinline__ troots roots_of(tdet q) {
 // key otherwise: the closest-hit update becomes one min3 with the running key (plus the compare
 // and select of the index), and the shadow test one unsigned compare against key(maxt) (0 when
 // maxt <= EPS or NaN: nothing occludes, as in the float test).
-// (The rule is checked on edge values and random roots by tests/test_ikey_rule.py.)  On in the
-// scene-specialised kernels: cornell +0.7 to +1.1 %, cornell_glass +0.6 %, synthetic64 +-0.1 %,
-// fused caustic / open +0.4 to +1.5 %, simple +3 to +4 % (one session each,
-// profiles/r03_s33_ab_ikey.txt); with the min3 written in C the compiler emits two v_min_u32
-// and the kernels run 0.5-1 % slower than without keys.
-#ifndef BDPT_IKEY
-#ifdef BDPT_JIT
-#define BDPT_IKEY 1
-#else
-#define BDPT_IKEY 0
-#endif
-#endif
+// (The rule is checked on edge values and random roots by tests/test_ikey_rule.py.)
 constexpr unsigned kKeyC = 0x3C23D70Bu;                      // bits(0.01f) + 1
 __device__ __forceinline__ unsigned key_of(float x) { return __float_as_uint(x) - kKeyC; }
 __device__ __forceinline__ unsigned umin2(unsigned a, unsigned b) { return a < b ? a : b; }
@@ -237,129 +234,105 @@ __device__ __forceinline__ f3 cosine_tail(f3 w, f3 u, float u_phi, float u_r2, f
     return cosine_tail_sc(w, u, s, c, u_r2, r2s);
 }
 
-// sinf / cosf of 2 pi u for every entry u of the random table, computed once per table
-// (bdpt_sincos_planar_kernel, planar like d_rndp) instead of per use (BDPT_SCP, pass-stream
-// kernels): the phi of the NEE light sample (u = d_Rand[j + 4], device.cu:162) and of the cosine
-// direction (u = d_Rand[j], :677) are both 2 pi u of a table entry, so the per-vertex fp64 sincos
-// becomes one 8-B load from the same plane offset as the entry itself.  The stored pair is
-// sincos_cr's result for that u, so results are unchanged bit for bit.
-#ifndef BDPT_SCP
-#define BDPT_SCP 1
+// ---------------------------------------------------------------------------------------------
+// The path kernel's compile-time switches.  "pre" = default of the precompiled instances (the
+// Makefile build), "jit" = default of a scene-specialised build (BDPT_JIT; bdpt_host.cpp
+// jit_path_kernel_build, which also passes the scene as BDPT_JIT_N / _EMIS / _GEOM); then who sets
+// it otherwise, and the measurement that decided it.  BDPT_JIT_FLAGS (environment) appends -D
+// options to a specialised build: tests and instruments use it, the product never does.
+// DESIGN_LOG.md has the history of each, and of the switches that were retired (guard at the top).
+//
+// Results are the same bit for bit under every setting: each one only changes where a value is
+// computed or how the work is laid out, never a float operation or its order.
+//
+//  BDPT_IKEY        pre 0, jit 1.  Nobody sets it.  Hit distances as unsigned keys (key_of above):
+//                   the closest hit is one v_min3_u32 per sphere, a shadow test one unsigned
+//                   compare.  Rule checked by tests/test_ikey_rule.py.  profiles/r03_s33_ab_ikey.txt
+//  BDPT_SREC        pre 0, jit 1.  tests/test_gpu_sample_records.py builds =0; the host reads the
+//                   flag back (bdpt_host.cpp jit_srec_enabled) to fill the right table.  Pass streams
+//                   without pixel pools load one 32-B sample record per segment
+//                   (bdpt_sample_records_kernel, bdpt_math.h bdpt_sample_record): the cosine
+//                   direction's three coefficients and the NEE light sample, computed once per
+//                   table, in place of four 4-B and two 8-B gathers and the per-vertex root, products
+//                   and sin/cos.  Where it is off, the same kernels load the sin/cos planes: {sinf,
+//                   cosf}(2 pi u) of every table entry u (bdpt_sincos_planar_kernel), at the plane
+//                   offset of the entry itself.  The pixel-pool build and the fused kernel take
+//                   neither and keep the table-driven fp64 sincos (pools: the two extra gathers cost
+//                   caustic8 2.5 %).  profiles/srec_ab_bench.txt, r06_s3_ab_scp.txt,
+//                   r06_s8_ab_scp_caustic8.txt
+//  BDPT_VAC_LIST    pre 0, jit 1.  The host builds =0 for scenes where the shorter list saves no
+//                   lane-group iteration (and tools/jit_codegen_check.py with it).  A part-full
+//                   shadow round of VLP rays only (IntersectPVacuumDevice ignores emitters) splits
+//                   the non-emitters' list (bdpt_path_args.vgeom, staged in LDS as GV) among its lane
+//                   groups.  Never in the pixel-pool build; the precompiled per-N instances would
+//                   spill SGPRs from N = 9.  profiles/r06_s23_ab_vac_list.txt, r06_s24_ab_vac_list.txt
+//  BDPT_PF_UNROLL   pre 0, jit 1.  The host builds =0 for pixel pools and where the build with it
+//                   spills above 5 waves/SIMD; tests/test_gpu_partfull_rounds.py builds both.
+//                   Part-full shadow rounds as straight-line code (pf_round below), one body per
+//                   group count and list, instead of the per-lane loop.
+//                   profiles/pf_unroll_ab_bench.txt
+//  BDPT_PF_MAX_IT   8.  Nobody sets it.  A (list, lg) pair that would unroll to more iterations
+//                   keeps the loop (synthetic64 at lg <= 2).  profiles/pf_unroll_ab_bench.txt
+//  BDPT_REGEN_K     48.  tests/test_gpu_fused_variants.py builds =1 and =64.  A lane whose path ends
+//                   parks until that many lanes of its wave (or all its live ones) are parked; they
+//                   start their next passes together, so the camera-ray code runs for groups of
+//                   lanes.  1 = restart at once, 64 = whole-wave lockstep.  Pass-stream lanes that
+//                   render more than one pass are grouped the same way.
+//                   profiles/r03_s13_ab_regen.txt, r03_s16_ab_regen_streams.txt
+//  BDPT_RNG_PAIR    1 (fused kernel only).  The host's auto stream mode builds =0 as well and keeps
+//                   the faster; tests/test_gpu_fused_variants.py builds =0.  The randoms of two
+//                   segments (depth d even and d + 1) are loaded together, so a path's table line is
+//                   fetched once for both.  profiles/r03_s22_ab_rng_pair.txt
+//  BDPT_POOL        0.  The host builds =1 for pixel-pool launches (a.pool = R): a wave renders ONE
+//                   pass, and a lane whose path ends takes the next pixel of the wave's pool, so a
+//                   restarted group's gathers stay adjacent in the planar copy.  Pools are chunks of
+//                   a.pool x 64 consecutive pixels, claimed with one vector atomic per chunk from 8
+//                   per-pass counters (a wave starts at its XCD's).  profiles/r04_s20_pools_auto.txt
+//  BDPT_UNITS       0.  The host builds =1 for launches with the ordered fold inside the kernel: a
+//                   1-D grid of units (tile, pass range; bdpt_path_args.unit_*), no radiance buffer,
+//                   no fold kernel.  profiles/r05_s5_units.txt
+//  BDPT_SC_COARSE   0 (bdpt_math.h).  The host builds =1 where the 4-KB sincos table costs a
+//                   workgroup per CU; tests/test_math.py checks both tables.  The 2-KB table of even
+//                   entries.  profiles/r03_s1_ab_fused.txt
+//  BDPT_BVH_K, BDPT_WAVES_PER_SIMD, BDPT_BVH_WAVES, BDPT_FUSED_WAVES, BDPT_JIT_ZERO_SAFE: described
+//                   where they are defined or used, below.
+//  BDPT_STATS, BDPT_PROF, BDPT_COUNTS: instruments (scripts/shadow_stats.py,
+//                   scripts/section_profile.sh, tools/valu_attrib.py); off in every product build.
+#ifdef BDPT_JIT
+#define BDPT_JIT_DEFAULT 1
+#else
+#define BDPT_JIT_DEFAULT 0
 #endif
-#ifndef BDPT_SCP_LATE
-#define BDPT_SCP_LATE 0
+#ifndef BDPT_IKEY
+#define BDPT_IKEY BDPT_JIT_DEFAULT
 #endif
-// Sample records (BDPT_SREC, where the sin/cos planes are used: pass streams without pixel
-// pools): everything a segment takes from d_Rand[j..j+4] that is a pure function of the table --
-// the cosine direction's coefficients cosf * sqrt(r2), sinf * sqrt(r2), sqrt(1 - r2) and the NEE
-// light sample uniform_sphere_sc(...) -- is computed once per table (bdpt_sample_records_kernel,
-// bdpt_math.h bdpt_sample_record) and loaded as one 32-B record per segment: two 16-B gathers and
-// the camera's d_Rand[j+1] instead of four 4-B and two 8-B gathers, and no per-vertex root,
-// products or sin/cos.  The record holds the same floats the per-segment code formed, so results
-// are unchanged bit for bit.  With it sqrt(cos2t) moves into the refraction branch (it shared an
-// instruction sequence with sqrt(r2)).  Scene-specialised builds only: the precompiled instances
-// keep the sin/cos planes.
 #ifndef BDPT_SREC
-#ifdef BDPT_JIT
-#define BDPT_SREC 1
-#else
-#define BDPT_SREC 0
+#define BDPT_SREC BDPT_JIT_DEFAULT
 #endif
-#endif
-// Shadow rounds whose rays are all VLP rays (IntersectPVacuumDevice, device.cu:141-154, ignores
-// emitters) skip the emitters' sphere tests: the NEE rays fill the queue first, so a segment's
-// second round is usually VLP rays only.
-#ifndef BDPT_VAC_SKIP
-#define BDPT_VAC_SKIP 1
-#endif
-// Lane groups of a part-full shadow round: 2^lg groups for rounds of <= 64 / 2^lg rays (lg <= 5),
-// reduced only while fewer groups take as few iterations -- caustic's 3 spheres in 1 iteration
-// instead of 2, cornell's 9 in 1 for rounds of <= 4 rays (BDPT_LG_RULE=0: the round-5 rule, lg <= 3,
-// reduced while 2^lg exceeds the list)
-#ifndef BDPT_LG_RULE
-#define BDPT_LG_RULE 1
-#endif
-// The same rounds when they are part-full (<= 32 rays, traced by lane groups that split the sphere
-// list): the groups split the non-emitters' list (bdpt_path_args.vgeom, staged in LDS as GV).
-// Not in the pixel-pool build: caustic8 ran 2 % slower with it (profiles/r06_s23_ab_vac_list.txt);
-// scene-specialised builds only (the precompiled per-N instances would spill SGPRs from N = 9).
 #ifndef BDPT_VAC_LIST
-#ifdef BDPT_JIT
-#define BDPT_VAC_LIST 1
-#else
-#define BDPT_VAC_LIST 0
+#define BDPT_VAC_LIST BDPT_JIT_DEFAULT
 #endif
-#endif
-// Part-full rounds as straight-line code (scene-specialised builds; pf_round below): one body per
-// group count and list, unrolled over its ceil(nl / 2^lg) iterations, instead of the per-lane
-// loop.  A (list, lg) pair that would take more than BDPT_PF_MAX_IT iterations keeps the loop
-// (synthetic64 at lg <= 2: 16 and 32 iterations, 0.5 and 1 KB of code each for rounds that its
-// 64-ray steps rarely leave).
 #ifndef BDPT_PF_UNROLL
-#ifdef BDPT_JIT
-#define BDPT_PF_UNROLL 1
-#else
-#define BDPT_PF_UNROLL 0
-#endif
+#define BDPT_PF_UNROLL BDPT_JIT_DEFAULT
 #endif
 #ifndef BDPT_PF_MAX_IT
 #define BDPT_PF_MAX_IT 8
 #endif
-#ifdef BDPT_JIT
-constexpr int kJitNLights = __builtin_popcountll(kJitEmis);      // bdpt_host.cpp upload_scene lights
-#endif
-
-// Fused S = 1 kernel: a lane whose path ends parks until at least BDPT_REGEN_K lanes of its wave
-// (or all of its live lanes) are parked; then they start their next passes together, so the
-// camera-ray and path-start code runs for groups of lanes instead of a few lanes in almost every
-// iteration.  1 = restart at once (no parking); 64 = whole-wave lockstep.  One-session A/B
-// (profiles/r03_s13_ab_regen.txt): caustic8 48.5 -> 52.3 Gs/s (+7.8 %) at 48, the same within
-// 0.5 % for 16..56, 49.1 at 64; open +2 to +3.5 %, simple +1 %, cornell (fused) +10 %.
 #ifndef BDPT_REGEN_K
 #define BDPT_REGEN_K 48
 #endif
-// The same grouping for pass-stream lanes that render more than one pass (S < npass; the auto
-// stream mode runs two passes per lane, bdpt_host.cpp); then the planar RNG copy is read too (a
-// group restarts on one slot, so one sid and depth).  Two passes per lane with grouping against
-// one pass per lane, one-session A/B (profiles/r03_s16_ab_regen_streams.txt): cornell +0.7 %,
-// cornell_glass +0.8 %, synthetic64 -0.2 %; without grouping two passes per lane cost 3.5-6 %.
-// Fused kernel: a parking lane loads its next pass's first-segment randoms at once (it waits at
-// least an iteration before it uses them), and its camera randoms a second time into cr0, cr1
-// (buffer loads, so the compiler does not merge them with the q0, q1 loads).  caustic8 +1.9 %,
-// open +0.3 % in one-session A/B (profiles/r03_s19_ab_park_prefetch.txt); pass streams keep
-// loading at release (cornell -1.1 % with it).  An ablation without any table reads runs caustic8
-// 37 % faster: the fused kernel's random gathers (20 B per lane and segment at unrelated
-// addresses, 6.6 TB/s of L2 fills) are what is left to win on open scenes.
-// Fused kernel: the randoms of two segments (depth d even and d + 1) are loaded together, so a
-// path's table line is fetched once for both instead of being evicted from L2 between them
-// (caustic8 +9 %, open -4 %: the auto stream mode measures the fused kernel with and without it
-// and keeps the faster, bdpt_host.cpp; profiles/r03_s22_ab_rng_pair.txt)
 #ifndef BDPT_RNG_PAIR
 #define BDPT_RNG_PAIR 1
 #endif
-// pass streams: radiance stores to the fold buffer with the nontemporal (streaming) hint
-// pass streams: parked lanes load their next pass's randoms at park time (see the loop)
-// pass streams: the segment's randoms settled before the radiance stores (see the loop)
-// Pass streams with pixel pools (a build with BDPT_POOL; bdpt_host.cpp launches it with a.pool = R):
-// a wave renders ONE pass, and a lane whose path ends takes the next pixel of the wave's pool --
-// the lanes stay on one sid, so a restarted group's random gathers stay adjacent in the planar
-// copy, unlike lanes that restart on their next pass (another sid each).  The pools are chunks
-// of a.pool x 64 consecutive pixels of the launch's rows, claimed with one vector atomic per
-// chunk until the pass's pixels are used up, so the waves of a pass finish together instead of
-// each waiting on its own last paths.  A pass's pixels are split in 8 parts with a counter each
-// (on lines of their own), and a wave claims from the part of its XCD first (one counter word
-// saturates near 90 claims/us), then from the others.  (A single queue running through all the
-// launch's passes, lanes carrying their pass, measured slower at one GPU: caustic >= 16 %.)
 #ifndef BDPT_POOL
 #define BDPT_POOL 0
 #endif
-// Pass streams with the ordered fold inside the kernel (a build with BDPT_UNITS; bdpt_host.cpp
-// launches it as a 1-D grid of units, bdpt_path_args.unit_*): no radiance buffer, no fold kernel.
 #ifndef BDPT_UNITS
 #define BDPT_UNITS 0
 #endif
-// paired loads: the odd-depth copy of the paired randoms at the point of use (see the loop)
-// camera terms: per-lane fp64 base in LDS, kz products formed once per workgroup
+#ifdef BDPT_JIT
+constexpr int kJitNLights = __builtin_popcountll(kJitEmis);      // bdpt_host.cpp upload_scene lights
+#endif
 
 }  // namespace
 
@@ -397,7 +370,7 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_rand_planar_kernel(const 
     rndp[o] = src < BDPT_DEV_RAND_N ? rnd[src] : 0.f;
 }
 
-// {sinf, cosf}(2 pi u) for every entry u of the planar copy (BDPT_SCP): the path kernel's own
+// The sin/cos planes, {sinf, cosf}(2 pi u) for every entry u of the planar copy: the path kernel's own
 // sincos_cr on the same float argument 2.f * kPi * u, with the 512-entry table (bdpt_math.h), so
 // each stored pair is what the path kernel would compute for that entry (a build with the
 // 256-entry BDPT_SC_COARSE table computes the same pair: both are the correctly rounded values,
@@ -564,9 +537,7 @@ __device__ __forceinline__ float4 ld_const(const float4* p, int i) {
 #endif
 }
 
-// d_Rand[j .. j+4] (device.cu:619): five dword loads, or (BDPT_RAND_X4) one dwordx4 + one dword
-// through a 4-byte-aligned vector type.  BDPT_ABL_RNG (ablation, changes results): no loads,
-// a hash of j instead -- the cost of the table reads.
+// d_Rand[j .. j+4] (device.cu:619): five dword loads
 __device__ __forceinline__ void load_rand5(const float* __restrict__ rnd, unsigned j, float& q0,
                                            float& q1, float& q2, float& q3, float& q4) {
     q0 = rnd[j]; q1 = rnd[j + 1]; q2 = rnd[j + 2]; q3 = rnd[j + 3]; q4 = rnd[j + 4];
@@ -599,8 +570,9 @@ __device__ __forceinline__ void load_rand5p(__amdgpu_buffer_rsrc_t rs, unsigned 
     q4 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, 4 * P4, 0));
 }
 
-// BDPT_SCP: d_Rand[j .. j+3] and {sinf, cosf}(2 pi d_Rand[j]), {sinf, cosf}(2 pi d_Rand[j+4]) --
-// d_Rand[j+4] itself is used only as that angle -- from the planar copies (same plane offsets)
+// The sin/cos planes: d_Rand[j .. j+3] and {sinf, cosf}(2 pi d_Rand[j]), {sinf, cosf}(2 pi
+// d_Rand[j+4]) -- d_Rand[j+4] itself is used only as that angle -- from the planar copies (same
+// plane offsets)
 __device__ __forceinline__ void load_rand_scp(__amdgpu_buffer_rsrc_t rs, __amdgpu_buffer_rsrc_t rsc,
                                               unsigned j, float& q0, float& q1, float& q2, float& q3,
                                               float& s0, float& c0, float& s4, float& c4) {
@@ -612,29 +584,6 @@ __device__ __forceinline__ void load_rand_scp(__amdgpu_buffer_rsrc_t rs, __amdgp
     q1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, P4, 0));
     q2 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, 2 * P4, 0));
     q3 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, 3 * P4, 0));
-    const u2v a = __builtin_amdgcn_raw_buffer_load_b64(rsc, vs, 0, 0);
-    const u2v b = __builtin_amdgcn_raw_buffer_load_b64(rsc, vs, 4 * P8, 0);
-    s0 = __uint_as_float(a.x); c0 = __uint_as_float(a.y);
-    s4 = __uint_as_float(b.x); c4 = __uint_as_float(b.y);
-}
-
-// the two parts of load_rand_scp on their own (BDPT_SCP_LATE)
-__device__ __forceinline__ void load_rand4p(__amdgpu_buffer_rsrc_t rs, unsigned j, float& q0, float& q1,
-                                            float& q2, float& q3) {
-    const unsigned qd = j / 25u, r = j - qd * 25u;
-    const unsigned vo = (r * BDPT_DEV_RANDP_PL + qd) * 4u;
-    constexpr unsigned P4 = BDPT_DEV_RANDP_PL * 4u;
-    q0 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, 0, 0));
-    q1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, P4, 0));
-    q2 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, 2 * P4, 0));
-    q3 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, 3 * P4, 0));
-}
-__device__ __forceinline__ void load_sc(__amdgpu_buffer_rsrc_t rsc, unsigned j, float& s0, float& c0,
-                                        float& s4, float& c4) {
-    typedef unsigned u2v __attribute__((ext_vector_type(2)));
-    const unsigned qd = j / 25u, r = j - qd * 25u;
-    const unsigned vs = (r * BDPT_DEV_RANDP_PL + qd) * 8u;
-    constexpr unsigned P8 = BDPT_DEV_RANDP_PL * 8u;
     const u2v a = __builtin_amdgcn_raw_buffer_load_b64(rsc, vs, 0, 0);
     const u2v b = __builtin_amdgcn_raw_buffer_load_b64(rsc, vs, 4 * P8, 0);
     s0 = __uint_as_float(a.x); c0 = __uint_as_float(a.y);
@@ -680,8 +629,8 @@ __device__ __forceinline__ void unroll_down(F& f) {
 // whose 2^LG candidate spheres hold no emitter has no test for it.  Returns the rays' occlusion
 // bits.
 constexpr int pf_iters(int nl, int lg) { return (nl + (1 << lg) - 1) >> lg; }
-// lists that reach lg under BDPT_LG_RULE's reduction (2^(lg - 1) < nl; with the older rule every
-// such list too) and fit the bound
+// lists that reach lg (the path loop lowers lg while half as many groups still cover the list, so
+// a round has 2^lg groups only where 2^(lg - 1) < nl) and fit the bound
 constexpr bool pf_fits(int nl, int lg) { return (1 << (lg - 1)) < nl && pf_iters(nl, lg) <= BDPT_PF_MAX_IT; }
 constexpr int kJitNVac = BDPT_JIT_N - kJitNLights;                // bdpt_host.cpp upload_scene n_vac
 template <int LG, int NL, bool EMIS>
@@ -738,14 +687,8 @@ __device__ __forceinline__ unsigned long long pf_round(const float4* GL, const f
 // Handover between the units of a tile (BDPT_UNITS): agent-scope relaxed atomics are coherent
 // across XCDs (sc1 loads / stores on gfx950, no L2 invalidation); the producer waits for its data
 // stores (s_waitcnt vmcnt(0)) before it stores the flag.  Every value handed over (colours,
-// counter, flag) is such an atomic, so no cache maintenance is needed; the C++-model form of the
-// same ordering (BDPT_UNITS_FENCE=1: an agent-scope release fence before the flag store and an
-// acquire fence after the flag load) compiles to buffer_wbl2 sc1 / buffer_inv sc1 -- a write-back
-// and an invalidation of the XCD's whole L2 per unit -- and is kept as a measured variant only
-// ("Units").
-#ifndef BDPT_UNITS_FENCE
-#define BDPT_UNITS_FENCE 0
-#endif
+// counter, flag) is such an atomic, so no cache maintenance is needed.  (Agent-scope release /
+// acquire fences in their place were measured and rejected: DESIGN.md section 4, "Units".)
 __device__ __forceinline__ float ld_coherent(float* p) {
     return __uint_as_float(__hip_atomic_load((unsigned*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
@@ -766,11 +709,7 @@ __device__ __forceinline__ void unit_wait(unsigned* f, unsigned want, unsigned* 
         }
         __builtin_amdgcn_s_sleep(10);
     }
-#if BDPT_UNITS_FENCE
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#else
     asm volatile("" ::: "memory");
-#endif
 }
 
 __device__ __forceinline__ void wave_lds_fence() {
@@ -861,9 +800,7 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
     constexpr bool kBVH = N < 0;      // large scene: walls brute force + BVH (bdpt_bvh.cpp)
     const int n = N > 0 ? N : (int)a.n;
     constexpr int kUnroll = N > 0 ? N : 1;
-    constexpr bool kTreeLds = false;  // tree read through L1/L2: 4 workgroups per CU (+10 %)
-    const int ntree = kTreeLds ? 2 * a.bvh_nn + a.bvh_ns : 0;
-    const int ntab = kBVH ? ntree + a.big_n : 4 * n + a.n_vac;      // (bdpt_host.cpp tab)
+    const int ntab = kBVH ? a.big_n : 4 * n + a.n_vac;               // (bdpt_plan.h bdpt_path_tab)
     // pass stream: this workgroup's lanes render passes s0, s0+S, s0+2S, ... (slots k = 0, 1, ...)
     // of their pixels (S == 1: all, and each lane keeps the running mean itself; S > 1: radiance
     // goes to rbuf, bdpt_accum_kernel folds it in pass order).  Only the slots' VLPs and sids are
@@ -919,27 +856,19 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
     float4* P = smem + 2 * n;         // {px, py, pz, 0}  (hit normal)
     float4* G = smem + 3 * n;         // {px, py, pz, rad^2}  (N == 0 traversal)
     float4* GV = smem + 4 * n;        // the same for the non-emitters only (VLP-only shadow rounds)
-    float4* ND = smem;                // BVH: nodes (2 float4 each)
-    float4* SG = ND + 2 * a.bvh_nn;   // BVH: sphere geometry in leaf order
-    float4* BG = smem + ntree;        // BVH: brute-force (wall) geometry
+    float4* BG = smem;                // BVH: brute-force (wall) geometry
     float4* V = smem + ntab;          // per slot: VLP {hx,hy,hz,rx}{ry,rz,nx,ny}{nz,-,-,-}
     float4* K = V + 3 * mslot;        // camera constants (5 float4)
     float4* Q = K + 5;                // shadow queues: 4 waves x kQueue x 2 float4
     // (a ray's occlusion bit is written over its maxt, SQ[idx].w, once the ray is traced)
     unsigned* SID = (unsigned*)(Q + 4 * kQueue * 2);   // per slot sid
-    int* SI = (int*)(SID + mslot);    // BVH: sphere ids (| emissive flag), leaf order
-    int* BI = SI + (kTreeLds ? a.bvh_ns : 0);   // BVH: wall ids
-    const float4* __restrict__ NDt = kTreeLds ? (const float4*)ND : a.bvh_nodes;
-    const float4* __restrict__ SGt = kTreeLds ? (const float4*)SG : a.bvh_geom;
-    const int* __restrict__ SIt = kTreeLds ? (const int*)SI : a.bvh_ids;
+    int* BI = (int*)(SID + mslot);    // BVH: wall ids (| emissive flag)
+    // BVH, not staged (read through L1/L2, which leaves LDS for 4 workgroups per CU): nodes (2
+    // float4 each), sphere geometry and sphere ids (| emissive flag) in leaf order
+    const float4* __restrict__ NDt = a.bvh_nodes;
+    const float4* __restrict__ SGt = a.bvh_geom;
+    const int* __restrict__ SIt = a.bvh_ids;
     if constexpr (kBVH) {
-        if constexpr (kTreeLds) {
-            for (int q = threadIdx.x; q < 2 * a.bvh_nn; q += 256) ND[q] = a.bvh_nodes[q];
-            for (int q = threadIdx.x; q < a.bvh_ns; q += 256) {
-                SG[q] = a.bvh_geom[q];
-                SI[q] = a.bvh_ids[q];
-            }
-        }
         for (int q = threadIdx.x; q < a.big_n; q += 256) {
             BG[q] = a.big_geom[q];
             BI[q] = a.big_ids[q];
@@ -1004,12 +933,12 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
     }
     // sin(2pi k/N) for the table-driven sincos (bdpt_math.h; cos is entry k + N/4), 4 KB (2 KB
     // with BDPT_SC_COARSE: every other entry)
-    // (not with BDPT_SCP: the pass-stream kernels load precomputed pairs -- except the pixel-pool
-    // build, whose restarted lanes are bound by their random-table gathers: the two extra gathers
-    // per segment cost caustic8 2.5 %, one-session A/B profiles/r06_s8_ab_scp_caustic8.txt)
-    // (nor with BDPT_SREC, which replaces the planes by the sample records in the same kernels)
+    // (not where the pass-stream kernels load precomputed values, the sin/cos planes (kScp) or the
+    // sample records that replace them (kSrec) -- that is, only in the fused kernel and the
+    // pixel-pool build, whose restarted lanes are bound by their random-table gathers: the two
+    // extra gathers per segment cost caustic8 2.5 %, profiles/r06_s8_ab_scp_caustic8.txt)
     constexpr bool kSrec = STREAMS && BDPT_SREC && !BDPT_POOL;
-    constexpr bool kScp = STREAMS && BDPT_SCP && !BDPT_POOL && !kSrec;
+    constexpr bool kScp = STREAMS && !BDPT_POOL && !kSrec;
     constexpr int kSct = BDPT_SC_N >> BDPT_SC_COARSE;
     const double* SCT = nullptr;
     if constexpr (!kScp && !kSrec) {
@@ -1217,18 +1146,15 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
     };
     const __amdgpu_buffer_rsrc_t rsp = __builtin_amdgcn_make_buffer_rsrc(
         (void*)a.rndp, (short)0, (int)(BDPT_DEV_RANDP_PLANES * BDPT_DEV_RANDP_PL * 4u), 0x00020000);
-    // BDPT_SCP: {sinf, cosf}(2 pi d_Rand[j]) and (2 pi d_Rand[j + 4]) (q4 is not loaded)
+    // the sin/cos planes: {sinf, cosf}(2 pi d_Rand[j]) and (2 pi d_Rand[j + 4]) (q4 is not loaded)
     float sn0 = 0.f, cs0 = 0.f, sn4 = 0.f, cs4 = 0.f;
     // (BDPT_SREC: a.scp is the record table; q0 = u0, q2 = u2, sn0, cs0 = B, A, q3 = C and
     // sn4, cs4, q4 = Y, X, Z of the record -- the registers of the values they replace)
     const __amdgpu_buffer_rsrc_t rss = __builtin_amdgcn_make_buffer_rsrc(
         (void*)a.scp, (short)0,
         (int)(kSrec ? 2u * BDPT_DEV_SREC_HALF * 16u : BDPT_DEV_RANDP_PLANES * BDPT_DEV_RANDP_PL * 8u), 0x00020000);
-    // BDPT_SCP_LATE (experiment): the pairs loaded at the top of their own segment instead of
-    // one segment ahead with d_Rand[j..j+3] (shorter register lifetimes, less time to arrive)
     auto load_plan = [&](unsigned jj) {
         if constexpr (kSrec) load_srec(rsp, rss, jj, cs0, sn0, q3, q2, cs4, sn4, q4, q0, q1);
-        else if constexpr (kScp && BDPT_SCP_LATE) load_rand4p(rsp, jj, q0, q1, q2, q3);
         else if constexpr (kScp) load_rand_scp(rsp, rss, jj, q0, q1, q2, q3, sn0, cs0, sn4, cs4);
         else load_rand5p(rsp, jj, q0, q1, q2, q3, q4);
     };
@@ -1270,9 +1196,6 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
         bool done = false, diff = false;
         float t = 1e20f;
         int id = -1;
-        if constexpr (kScp && BDPT_SCP_LATE) {
-            if (alive) load_sc(rss, j, sn0, cs0, sn4, cs4);
-        }
         if (alive) {
             if (fresh) {                  // camera ray (:562-600); d_Rand[kk] == q0 (kk == j)
                 const float4 c0 = K[0], c1 = K[1], c2 = K[2], c3 = K[3], k4 = K[4];
@@ -1599,22 +1522,17 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
                         const bool allvac = BDPT_VAC_LIST && !kPool && base >= cn;   // uniform
                         const int nl = allvac ? a.n_vac : n;
                         const float4* GL = allvac ? GV : G;
-#if BDPT_LG_RULE
                         // as many groups as the round's rays allow, down to the fewest that still
                         // take the same number of iterations (ceil(nl / 2^lg)); groups past the
                         // list's end idle
                         int lg = c <= 2 ? 5 : c <= 4 ? 4 : c <= 8 ? 3 : (c <= 16 ? 2 : (c <= 32 ? 1 : 0));
                         while (lg > 0 && (1 << (lg - 1)) >= nl) lg--;
-#else
-                        int lg = c <= 8 ? 3 : (c <= 16 ? 2 : (c <= 32 ? 1 : 0));
-                        while (lg > 0 && (1 << lg) > nl) lg--;
-#endif
                         if (lg > 0) {
                             BDPT_CNTN(8, 1);
                             unsigned long long m;
 #if defined(BDPT_JIT) && BDPT_PF_UNROLL
                             // straight-line bodies (pf_round), one per group count the list can
-                            // have (BDPT_LG_RULE: 2^(lg - 1) < nl) and at most BDPT_PF_MAX_IT
+                            // have (2^(lg - 1) < nl after the reduction above) and at most BDPT_PF_MAX_IT
                             // iterations long, picked by the uniform lg; other rounds: the loop
                             bool unrolled = false;
                             if constexpr (N == BDPT_JIT_N) {
@@ -1721,7 +1639,7 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
                         auto step = [&](int s) -> bool {                  // IntersectP(Vacuum)Device
                             // a round of VLP rays only (the queue holds the NEE rays first):
                             // IntersectPVacuumDevice never counts an emitter, so its test is skipped
-                            if (BDPT_VAC_SKIP && emissive(s) && vacm == live) return true;
+                            if (emissive(s) && vacm == live) return true;
                             BDPT_CNTN(9, 1);
                             const tdet qd = sphere_det(geom(s), o, d);
                             if (small_sphere(s) && __builtin_amdgcn_ballot_w64(!(qd.det < 0.f)) == 0) {
@@ -1942,11 +1860,7 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
         // pixels once, by the launch's last range: plain stores of several units (on several XCDs,
         // each with its own write-back L2) would reach memory in no defined order
         if (active && s0 + nslot >= a.npass) a.pixels[iu] = bdpt_dev_to_rgba(col.x, col.y, col.z, a.gamma_thr);
-#if BDPT_UNITS_FENCE
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the stores above are performed
-#endif
         if (lane == 0)
             __hip_atomic_store(a.unit_flags + uflag, a.unit_tag | (urange + 1u), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);

@@ -275,14 +275,13 @@ inline bool bdpt_plan_overlap(const bdpt_plan& p, const bdpt_path_env& env, bool
 }
 
 // Dynamic LDS of a path-kernel workgroup: the scene table of `tab` float4 (4 per sphere + the
-// non-emitters' list, or the BVH's brute-force spheres and, with BDPT_BVH_LDS, the tree: 2 per node
-// + 1 per sphere; bdpt_kernels.hip ntab) + a VLP per staged pass + camera + 4 wave shadow queues
-// (results written over maxt) + a sid per staged pass + `ids` BVH sphere ids (+ an experiment's pad).
+// non-emitters' list, or a BVH scene's brute-force spheres) + a VLP per staged pass + camera + 4 wave
+// shadow queues (results written over maxt) + a sid per staged pass + `ids` brute-force ids (+ a pad).
 inline size_t bdpt_path_smem(size_t tab, size_t slots, size_t ids, int pad) {
     return 16 * (tab + 3 * slots + 5 + 4 * 128 * 2) + sizeof(unsigned) * (slots + ids) + (size_t)pad;
 }
-inline size_t bdpt_path_tab(bool bvh, size_t n, size_t n_vac, size_t tree, size_t big_n) {
-    return bvh ? tree + big_n : 4 * n + n_vac;
+inline size_t bdpt_path_tab(bool bvh, size_t n, size_t n_vac, size_t big_n) {
+    return bvh ? big_n : 4 * n + n_vac;
 }
 
 // Which kernel a launch runs: the precompiled instance or one of the specialised builds.

@@ -230,8 +230,8 @@ static void choice_bits() {
 }
 
 static void lds() {
-    CHECK(bdpt_path_tab(false, 9, 8, 0, 0) == 44 && bdpt_path_tab(true, 200, 190, 0, 6) == 6);
-    CHECK(bdpt_path_smem(bdpt_path_tab(false, 9, 8, 0, 0), 10, 0, 0) == 16 * (44 + 30 + 5 + 1024) + 4 * 10);
+    CHECK(bdpt_path_tab(false, 9, 8, 0) == 44 && bdpt_path_tab(true, 200, 190, 6) == 6);
+    CHECK(bdpt_path_smem(bdpt_path_tab(false, 9, 8, 0), 10, 0, 0) == 16 * (44 + 30 + 5 + 1024) + 4 * 10);
     CHECK(bdpt_path_smem(44, 10, 0, 0) == 17688);
     CHECK(bdpt_path_smem(5 * 64, 1, 0, 0) == 16 * (320 + 3 + 5 + 1024) + 4);    // the JIT estimate, n = 64
     CHECK(bdpt_path_smem(5 * 64, 1, 0, 0) == 21636);

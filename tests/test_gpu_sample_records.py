@@ -10,7 +10,9 @@ takes from d_Rand[j..j+4] instead of computing it per vertex.
      and with BDPT_JIT_FLAGS=-DBDPT_SREC=0 (the sin/cos planes);
  (c) the derived tables are rebuilt after every table change before a kernel reads them
      (light pass, bdpt_generate_rand, specialisation off and on again);
- (d) a two-shard context on one GPU (each shard owns its tables) equals the single context."""
+ (d) a two-shard context on one GPU (each shard owns its tables) equals the single context;
+ (e) a retired switch in BDPT_JIT_FLAGS fails the specialised build, and the call falls back to the
+     precompiled instance with the same frame."""
 import os
 
 import numpy as np
@@ -148,6 +150,33 @@ def test_tables_follow_the_random_table(gpu, tables):
         check(r, 7, True, "generate_rand(7)")
         r.set_specialize(False)
         check(r, 7, False, "generate_rand(7), planes")
+
+
+def test_retired_switch_falls_back_to_the_precompiled_kernel(gpu, tables, monkeypatch):
+    """A retired switch in BDPT_JIT_FLAGS fails the specialised build (the guard at the top of
+    bdpt_kernels.hip) instead of building the default kernel under another name: the call runs
+    the precompiled instance, says why, and the frame is still the oracle's."""
+    W, H = 33, 25
+    cam, sp = _scene("cornell", W, H)
+    s = g.PassScheduler()
+    s.light()
+    sid, vlp = s.next(4)
+    rnd0 = tables(0)
+    want = oracle.path_passes(sp, rnd0, cam, W, H, oracle.light_pass(sp, rnd0, 0), sid, vlp)
+    for flags, specialised in (("-DBDPT_LG_RULE=0", False), (None, True)):
+        if flags:
+            monkeypatch.setenv("BDPT_JIT_FLAGS", flags)
+        else:
+            monkeypatch.delenv("BDPT_JIT_FLAGS", raising=False)
+        with g.Renderer(sp, W, H, cam, device=gpu) as r:
+            r.set_streams(-1)
+            r.light_pass(0)
+            r.path_passes(sid, vlp)
+            assert r.last_specialized == specialised, (flags, r.specialize_status)
+            if not specialised:
+                assert "BDPT_LG_RULE" in r.specialize_status, r.specialize_status
+            col, cnt = r.read_radiance()
+            _same((col, cnt, r.read_pixels()), want, f"BDPT_JIT_FLAGS={flags}")
 
 
 def test_two_shards_equal_single_context(gpu, tables):

@@ -62,6 +62,26 @@ def test_specialised_build_offline(scene):
     assert r.returncode == 0, r.stdout + r.stderr
 
 
+RETIRED = ["BDPT_SCP", "BDPT_SCP_LATE", "BDPT_LG_RULE", "BDPT_VAC_SKIP", "BDPT_UNITS_FENCE", "BDPT_BVH_LDS"]
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
+@pytest.mark.parametrize("name", [None] + RETIRED)
+def test_retired_switch_is_a_compile_error(name):
+    """A switch whose experiment ended (bdpt_kernels.hip, the guard at its top) must not compile:
+    the build would silently be the default one.  Without any of them the source compiles."""
+    cmd = [HIPCC, "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-fsyntax-only"]
+    if name:
+        cmd.append(f"-D{name}=1")
+    r = subprocess.run(cmd + [os.path.join(REPO, "gpu_bidirectional_raytracer_amd", "csrc", "bdpt_kernels.hip")],
+                       capture_output=True, text=True, timeout=300)
+    if name is None:
+        assert r.returncode == 0, r.stderr
+    else:
+        assert r.returncode != 0 and name in r.stderr, r.stderr
+        assert "error" in r.stderr and "retired switch" in r.stderr, r.stderr
+
+
 def _c_rule(sp):
     import ctypes
     sys.path.insert(0, REPO)
