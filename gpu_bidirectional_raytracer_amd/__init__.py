@@ -19,8 +19,8 @@ import numpy as np
 
 from ._lib import (BDPT_OK, CHOICES, COUNTER_CAP, DEFAULT_DAT, DIFF, FEATURES, KEY_DOWN, KEY_LEFT, KEY_PAGE_DOWN,
                    KEY_PAGE_UP, KEY_RIGHT, KEY_UP, LIGHT_POINTS, LITE, RAND_N, REFR, SCENE_DIR, SPEC,
-                   DENOISE_MATERIALS, AovBuffers, BdptError, Camera, DenoiseParams, LightPath, PassState, RandState,
-                   ReprojectParams, Sphere, Vec, lib)
+                   DENOISE_MATERIALS, AovBuffers, BdptError, Camera, DenoiseParams, LightPath, PassState, PreviewParams,
+                   RandState, ReprojectParams, Sphere, Vec, lib)
 
 __all__ = [
     "Vec", "Sphere", "Camera", "LightPath", "Renderer", "SmallPT", "PassScheduler", "read_scene",
@@ -542,6 +542,35 @@ class Renderer:
         self._chk(lib.bdpt_last_reproject_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
+    # -- the reprojected preview, denoised (no reference counterpart; include/bdpt.h bdpt_preview_denoise)
+    def preview_denoise(self, levels: int = 4, normal_power: int = 5, sigma_color: float = 0.5,
+                        count_ref: float = 8.0, max_history: float = 64.0, plane_tol: float = 0.01,
+                        materials: str = "diffuse", weight: bool = False, pixels: bool = False):
+        """reproject() and denoise() in one call that knows each pixel's sample count: the
+        reprojected frame (max_history, plane_tol, materials as for reproject()) through `levels`
+        a-trous levels (0..8; 0 is reproject() itself) in which a tap is weighted by its count and
+        the colour stopping is scaled by a_p a_q / (a_p + a_q) * 2 / count_ref -- two pixels of
+        count_ref passes each are told apart as denoise() would, pixels with more history are
+        blurred less readily, one-pass pixels take their neighbours' colour.  materials selects the
+        pixels for both stages.  Returns the [H, W, 3] float32 frame, followed by the [H, W]
+        float32 carried sample count with weight=True and by the rgba [H, W, 4] uint8 with
+        pixels=True.  Changes nothing else of the context, the history included."""
+        prm = PreviewParams(self._reproject_params(max_history, plane_tol, materials), int(levels),
+                            int(normal_power), float(sigma_color), float(count_ref))
+        col = np.empty((self.height, self.width, 3), np.float32)
+        w = np.empty((self.height, self.width), np.float32) if weight else None
+        px = np.empty((self.height, self.width, 4), np.uint8) if pixels else None
+        self._chk(lib.bdpt_preview_denoise(self._h, ctypes.byref(prm), _ptr(col), _ptr(w) if weight else None,
+                                           _ptr(px) if pixels else None))
+        out = (col,) + ((w,) if weight else ()) + ((px,) if pixels else ())
+        return out if len(out) > 1 else col
+
+    def last_preview_ms(self) -> float:
+        """Device time (ms) of the last preview_denoise call's kernels alone."""
+        ms = ctypes.c_float()
+        self._chk(lib.bdpt_last_preview_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
     def device_buffers(self) -> Tuple[int, int, int]:
         c, n, p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         self._chk(lib.bdpt_device_buffers(self._h, ctypes.byref(c), ctypes.byref(n), ctypes.byref(p)))
@@ -730,16 +759,22 @@ class SmallPT:
         save_ppm(path, px, binary)
         return path
 
-    def preview(self, **params):
+    def preview(self, denoise: bool = False, **params):
         """The frame with the last view's history reprojected into it (Renderer.reproject(**params));
-        with reuse_history=False there is no history and this is the raw frame."""
+        with reuse_history=False there is no history and this is the raw frame.  denoise=True: the
+        same through the count-weighted filter (Renderer.preview_denoise(**params))."""
+        if denoise:
+            return self.renderer.preview_denoise(**params)
         return self.renderer.reproject(**params)
 
-    def SavePreviewPPM(self, path: Optional[str] = None, binary: bool = False, **params) -> str:
+    def SavePreviewPPM(self, path: Optional[str] = None, binary: bool = False, denoise: bool = False,
+                       **params) -> str:
         """SavePPM of the preview's pixels; without a path, SavePPM's file name with `_preview`
-        before `.ppm`."""
+        (denoise=True: `_preview_denoised`) before `.ppm`."""
         if path is None:
-            path = ppm_name(self.total_time, self.current_sample)[:-len(".ppm")] + "_preview.ppm"
-        px = self.renderer.reproject(pixels=True, **params)[-1]
+            suffix = "_preview_denoised.ppm" if denoise else "_preview.ppm"
+            path = ppm_name(self.total_time, self.current_sample)[:-len(".ppm")] + suffix
+        call = self.renderer.preview_denoise if denoise else self.renderer.reproject
+        px = call(pixels=True, **params)[-1]
         save_ppm(path, px, binary)
         return path

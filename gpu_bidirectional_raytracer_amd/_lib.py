@@ -67,6 +67,12 @@ class ReprojectParams(ctypes.Structure):
     _fields_ = [("materials", ctypes.c_int), ("max_history", ctypes.c_float), ("plane_tol", ctypes.c_float)]
 
 
+class PreviewParams(ctypes.Structure):
+    """bdpt_preview_params."""
+    _fields_ = [("rp", ReprojectParams), ("levels", ctypes.c_int), ("normal_power", ctypes.c_int),
+                ("sigma_color", ctypes.c_float), ("count_ref", ctypes.c_float)]
+
+
 class RandState(ctypes.Structure):
     _fields_ = [("state", ctypes.c_int * 31), ("f", ctypes.c_int), ("r", ctypes.c_int)]
 
@@ -149,6 +155,8 @@ _SIGS = [
     ("bdpt_history_write", ctypes.c_int, [_P, ctypes.POINTER(Camera), _P, _P]),
     ("bdpt_reproject", ctypes.c_int, [_P, ctypes.POINTER(ReprojectParams), _P, _P, _P]),
     ("bdpt_last_reproject_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
+    ("bdpt_preview_denoise", ctypes.c_int, [_P, ctypes.POINTER(PreviewParams), _P, _P, _P]),
+    ("bdpt_last_preview_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_gl_register_pbo", ctypes.c_int, [_P, ctypes.c_uint]),
     ("bdpt_gl_publish", ctypes.c_int, [_P]),
     ("bdpt_gl_unregister", ctypes.c_int, [_P]),

@@ -688,6 +688,105 @@ void bdpt_cpu_reproject(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, b
         }
 }
 
+// Count-weighted denoising of the reprojected preview (include/bdpt.h bdpt_preview_denoise;
+// DESIGN.md 4f): a plain restatement of the definition there.  The input is reproject_frame's
+// (out, tot); the guides are the first hit the reprojection has just used; a record's count is
+// clamped when the record is written.  fp32, no contraction, in exactly this order -- the HIP
+// kernels (bdpt_preview_level_t) form the same bits.  The caller has checked the parameters.
+static inline float preview_clampc(float w) { return w == 0.f ? 0.f : fminf(fmaxf(w, 0x1p-20f), 0x1p40f); }
+
+void bdpt_cpu_preview_denoise(const bdpt_cpu_ctx* c, const bdpt_preview_params* p, bdpt_vec* colors_out,
+                              float* weight_out, unsigned char* rgba_out) {
+    const int W = c->W, H = c->H;
+    const size_t np = (size_t)W * H;
+    FirstHit f(c, c->cam, false);
+    std::vector<bdpt_vec> ping(np), pong(np);
+    std::vector<float> aping(np), apong(np);
+    reproject_frame(c, &p->rp, f, ping, aping);
+    std::vector<int>& id = f.id;
+    const std::vector<bdpt_vec>& nrm = f.nrm;
+    if (p->levels > 0) {
+        for (size_t i = 0; i < np; i++) {                 // an ineligible pixel: id -1
+            if (id[i] >= 0 && p->rp.materials == BDPT_DENOISE_DIFFUSE && c->scene.s[id[i]].refl != BDPT_DIFF) id[i] = -1;
+            aping[i] = preview_clampc(aping[i]);
+        }
+    }
+    static const float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
+    const float isc0 = 1.0f / (p->sigma_color * p->sigma_color);
+    const float c2 = 2.f / p->count_ref;
+    for (int k = 0; k < p->levels; k++) {
+        const int s = 1 << k;
+        const float isc = isc0 * (float)(1 << (2 * k));
+        const bdpt_vec* cur = ping.data();
+        const float* acur = aping.data();
+        bdpt_vec* out = pong.data();
+        float* aout = apong.data();
+        parallel_rows(0, H, c->threads, [&](int y) {
+            for (int x = 0; x < W; x++) {
+                const size_t i = (size_t)y * W + x;
+                const bdpt_vec cp = cur[i];
+                const float a_p = acur[i];
+                if (id[i] < 0) {
+                    out[i] = cp;
+                    aout[i] = a_p;
+                    continue;
+                }
+                const V3 n_p = of(nrm[i]);
+                float su = 0.f, sw = 0.f;
+                V3 sc = v3(0.f, 0.f, 0.f);
+                bool used = false;
+                for (int j = 0; j < 5; j++) {
+                    const int qy = y + (j - 2) * s;
+                    if (qy < 0 || qy >= H) continue;
+                    for (int t = 0; t < 5; t++) {
+                        const int qx = x + (t - 2) * s;
+                        if (qx < 0 || qx >= W) continue;
+                        const size_t q = (size_t)qy * W + qx;
+                        const float a_q = acur[q];
+                        if (id[q] != id[i] || !(a_q > 0.f)) continue;
+                        const float d = dot(n_p, of(nrm[q]));
+                        float wn = d > 0.f ? d : 0.f;
+                        for (int r = 0; r < p->normal_power; r++) wn = wn * wn;
+                        const V3 cq = of(cur[q]);
+                        const V3 dc = cq - of(cp);
+                        const float e2 = dot(dc, dc);
+                        float wc = 1.f;
+                        if (a_p != 0.f) {
+                            const float g = ((a_p * a_q) * (1.f / (a_p + a_q))) * c2;
+                            wc = 1.f / (1.f + (e2 * isc) * g);
+                        }
+                        const float u = ((hk[j] * hk[t]) * wn) * wc;
+                        const float w = u * a_q;
+                        su = su + u;
+                        sw = sw + w;
+                        sc = sc + w * cq;
+                        used = true;
+                    }
+                }
+                if (!used) {
+                    out[i] = cp;
+                    aout[i] = a_p;
+                    continue;
+                }
+                const float r = 1.f / sw;
+                out[i] = {sc.x * r, sc.y * r, sc.z * r};
+                aout[i] = preview_clampc(sw / su);
+            }
+        });
+        ping.swap(pong);
+        aping.swap(apong);
+    }
+    if (colors_out) memcpy(colors_out, ping.data(), sizeof(bdpt_vec) * np);
+    if (weight_out) memcpy(weight_out, aping.data(), sizeof(float) * np);
+    if (rgba_out)
+        for (size_t i = 0; i < np; i++) {
+            rgba_out[4 * i] = (unsigned char)to_int8(ping[i].x, c->thr);
+            rgba_out[4 * i + 1] = (unsigned char)to_int8(ping[i].y, c->thr);
+            rgba_out[4 * i + 2] = (unsigned char)to_int8(ping[i].z, c->thr);
+            rgba_out[4 * i + 3] = 0;
+        }
+}
+
 // The new history is formed in buffers of its own while the old one is read, then swapped in; its
 // guides are the first hit the reprojection has just used (the current camera becomes C0).
 void bdpt_cpu_history_capture(bdpt_cpu_ctx* c, const bdpt_reproject_params* p) {

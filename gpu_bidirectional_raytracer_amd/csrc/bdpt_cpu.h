@@ -32,6 +32,9 @@ void bdpt_cpu_history_write(bdpt_cpu_ctx* c, const bdpt_camera* cam, const bdpt_
 void bdpt_cpu_history_capture(bdpt_cpu_ctx* c, const bdpt_reproject_params* p);
 void bdpt_cpu_reproject(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, bdpt_vec* colors_out,
                         float* weight_out, unsigned char* rgba_out);
+// count-weighted denoising of the reprojected preview (include/bdpt.h bdpt_preview_denoise)
+void bdpt_cpu_preview_denoise(const bdpt_cpu_ctx* c, const bdpt_preview_params* p, bdpt_vec* colors_out,
+                              float* weight_out, unsigned char* rgba_out);
 bool bdpt_cpu_rand_ready(const bdpt_cpu_ctx* c);
 bool bdpt_cpu_camera_set(const bdpt_cpu_ctx* c);
 void bdpt_cpu_read_radiance(const bdpt_cpu_ctx* c, bdpt_vec* colors, unsigned* counter);

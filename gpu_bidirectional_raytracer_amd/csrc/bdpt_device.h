@@ -21,6 +21,7 @@
 //             pong colours; made on the first call                                  48 B/pixel
 //   d_hist    float4[4][W*H] + 20 B/pixel  reprojection (bdpt_reproject): two sets of history records
 //             {gpos, gid}, {hc, hm} and the packed results; made on first use        84 B/pixel
+//   bdpt_preview_denoise works in d_dn (the count in the colour records' .w) and d_hist's results
 #ifndef BDPT_DEVICE_H
 #define BDPT_DEVICE_H
 
@@ -189,6 +190,24 @@ struct bdpt_denoise_args {
 #define BDPT_DN_LDS_W (BDPT_DN_BTW + 4 * BDPT_DN_LDS_MAX_STEP)
 #define BDPT_DN_LDS_H (BDPT_DN_BTH + 4 * BDPT_DN_LDS_MAX_STEP)
 
+// The reprojected preview, denoised with per-pixel counts (bdpt_preview_level_t; include/bdpt.h
+// bdpt_preview_denoise).  The denoiser's records and tiles: `cur` / `nxt` are {colour, count a};
+// the last level may write the packed results (out3, weight, rgba; any may be nullptr).
+struct bdpt_preview_args {
+    int W, H;
+    int step;                       // 2^k
+    float isc;                      // isc_0 * 4^k
+    float c2;                       // 2.f / count_ref
+    int rows;                       // 1: a wave covers 64 x 1 pixels, 0: 8 x 8
+    const float4* guide;
+    const float4* cur;
+    float4* nxt;                    // nullptr on a last level
+    bdpt_dev_vec* out3;
+    float* weight;
+    uchar4* rgba;
+    const float* gamma_thr;
+};
+
 // Temporal reprojection (bdpt_history_pack_kernel / bdpt_reproject_kernel; include/bdpt.h
 // bdpt_reproject).  Context-owned history, made on first use: two sets (ping-pong: a capture reads
 // one and writes the other) of
@@ -217,6 +236,10 @@ struct bdpt_reproject_args {
     float* weight;
     uchar4* rgba;
     const float* gamma_thr;
+    // bdpt_preview_denoise only (nullptr / 0 otherwise): the denoiser's guide record {normal, bits:
+    // id1 or -1 for an ineligible pixel} of the pixel, and `next`'s count through clampc
+    float4* dn_guide;
+    int clamp_next;
 };
 #define BDPT_RP_BTW 32
 #define BDPT_RP_BTH 8

@@ -59,6 +59,7 @@ extern "C" const void* bdpt_denoise_level_table[2][7];   // [LDS staging][normal
 extern "C" __global__ void bdpt_history_pack_kernel(const int*, const bdpt_dev_vec*, const bdpt_dev_vec*,
                                                     const float*, float4*, float4*, int);
 extern "C" __global__ void bdpt_reproject_kernel(bdpt_reproject_args);
+extern "C" const void* bdpt_preview_level_table[2][7];   // [LDS staging][normal_power]
 
 // gamma thresholds (host, once): see bdpt_util.c
 extern "C" void bdpt_gamma_thresholds(float thr[256]);
@@ -221,6 +222,10 @@ struct bdpt_ctx {
     hipEvent_t rp_ev[2] = {nullptr, nullptr};    // around the kernels of the last capture / reprojection
     bool rp_ran = false;
     float rp_cpu_ms = 0.f;              // CPU backend: wall time of the last call
+    // denoised preview (bdpt_preview_denoise): works in d_dn and d_hist's result buffers
+    hipEvent_t pv_ev[2] = {nullptr, nullptr};    // around the kernels of the last call
+    bool pv_ran = false;
+    float pv_cpu_ms = 0.f;              // CPU backend: wall time of the last call
     unsigned gl_pbo = 0;
 };
 enum { kReduceNone = 0, kReduceRccl = 1, kReducePeer = 2 };
@@ -358,6 +363,8 @@ static void release(bdpt_ctx* c) {
     for (hipEvent_t e : c->dn_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->rp_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->pv_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& s : c->ring) {
         for (hipEvent_t e : s.kev) (void)hipEventDestroy(e);
@@ -2463,6 +2470,38 @@ static int hist_alloc(bdpt_ctx* c, hist_bufs* b) {
     return BDPT_OK;
 }
 
+// bdpt_reproject_kernel's arguments but for its outputs: the current view's first hit (av), the
+// frame, and the history present, if any
+static void rp_args(bdpt_ctx* c, const bdpt_reproject_params* p, const bdpt_aov_args& av, const hist_bufs& b,
+                    bdpt_reproject_args* vout) {
+    bdpt_reproject_args v;
+    memset(&v, 0, sizeof(v));
+    v.W = c->W; v.H = c->H;
+    v.all_materials = p->materials == BDPT_DENOISE_ALL;
+    v.max_history = p->max_history;
+    v.plane_tol = p->plane_tol;
+    v.id = av.id; v.t = av.t; v.position = av.position; v.normal = av.normal;
+    v.sph = c->d_sph;
+    v.colors = c->d_colors;
+    v.counter = c->d_counter;
+    v.gamma_thr = c->d_thr;
+    if (hist_present(c)) {
+        bdpt_path_args ha;                                    // C0 as the kernels' camera constants
+        memset(&ha, 0, sizeof(ha));
+        camera_args(c, c->hist_cam, ha);
+        memcpy(v.ux, ha.ux, sizeof(v.ux)); memcpy(v.uy, ha.uy, sizeof(v.uy)); memcpy(v.ud, ha.ud, sizeof(v.ud));
+        memcpy(v.o, ha.orig, sizeof(v.o));
+        v.hw = (float)ha.half_w; v.hh = (float)ha.half_h;
+        v.sx = 1.f / ha.inv_w; v.sy = 1.f / ha.inv_h;
+        v.hguide = b.guide[c->hist_cur];
+        v.hcol = b.col[c->hist_cur];
+    }
+    // wave tile: the measured choice (DESIGN.md 4e); BDPT_REPROJECT_TILE = 8 / 64 overrides it
+    v.rows = 1;
+    if (const char* e = getenv("BDPT_REPROJECT_TILE")) v.rows = atoi(e) != 8;
+    *vout = v;
+}
+
 static int rp_run(bdpt_ctx* c, const bdpt_reproject_params* p, bool capture, bdpt_vec* colors_out,
                   float* weight_out, unsigned char* rgba_out) {
     if (c->cpu) {
@@ -2484,32 +2523,10 @@ static int rp_run(bdpt_ctx* c, const bdpt_reproject_params* p, bool capture, bdp
     bdpt_aov_args av;
     bool bvh = false;
     if (int rc = aov_launch(c, c->cam, 0, 0, c->W, c->H, 0, 0u, &av, &bvh, nullptr, nullptr)) return rc;
-    const int cur = c->hist_cur, nxt = cur ^ 1;
+    const int nxt = c->hist_cur ^ 1;
     bdpt_reproject_args v;
-    memset(&v, 0, sizeof(v));
-    v.W = c->W; v.H = c->H;
-    v.all_materials = p->materials == BDPT_DENOISE_ALL;
-    v.max_history = p->max_history;
-    v.plane_tol = p->plane_tol;
-    v.id = av.id; v.t = av.t; v.position = av.position; v.normal = av.normal;
-    v.sph = c->d_sph;
-    v.colors = c->d_colors;
-    v.counter = c->d_counter;
-    v.gamma_thr = c->d_thr;
-    if (hist_present(c)) {
-        bdpt_path_args ha;                                    // C0 as the kernels' camera constants
-        memset(&ha, 0, sizeof(ha));
-        camera_args(c, c->hist_cam, ha);
-        memcpy(v.ux, ha.ux, sizeof(v.ux)); memcpy(v.uy, ha.uy, sizeof(v.uy)); memcpy(v.ud, ha.ud, sizeof(v.ud));
-        memcpy(v.o, ha.orig, sizeof(v.o));
-        v.hw = (float)ha.half_w; v.hh = (float)ha.half_h;
-        v.sx = 1.f / ha.inv_w; v.sy = 1.f / ha.inv_h;
-        v.hguide = b.guide[cur];
-        v.hcol = b.col[cur];
-    }
-    // wave tile: the measured choice (DESIGN.md 4e); BDPT_REPROJECT_TILE = 8 / 64 overrides it
-    v.rows = 1;
-    if (const char* e = getenv("BDPT_REPROJECT_TILE")) v.rows = atoi(e) != 8;
+    rp_args(c, p, av, b, &v);
+
     if (capture) {
         hipLaunchKernelGGL(bdpt_history_pack_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream,
                            (const int*)av.id, (const bdpt_dev_vec*)av.position, (const bdpt_dev_vec*)nullptr,
@@ -2636,6 +2653,128 @@ int bdpt_last_reproject_ms(bdpt_ctx* c, float* ms) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipEventSynchronize(c->rp_ev[1]));
     HIPCHK(c, hipEventElapsedTime(ms, c->rp_ev[0], c->rp_ev[1]));
+    return BDPT_OK;
+}
+
+// ---- the reprojected preview, denoised with per-pixel counts (include/bdpt.h
+// bdpt_preview_denoise) ----------------------------------------------------------
+// On the context's stream, after the last fold: bdpt_aov_kernel once, bdpt_reproject_kernel with
+// its {o, clampc(tot)} record going into the denoiser's ping buffer and the guide record into the
+// guide buffer (BDPT_PREVIEW_GUIDE=pack: bdpt_denoise_pack_kernel writes the guide records instead,
+// the alternative that was measured), then one count-aware level kernel per level, the last of
+// which writes the packed results into d_hist's result buffers; then the read-back.  levels == 0 is
+// the reprojection alone.  Only d_aov, d_dn and d_hist's result buffers are written.
+int bdpt_preview_denoise(bdpt_ctx* c, const bdpt_preview_params* p, bdpt_vec* colors_out, float* weight_out,
+                         unsigned char* rgba_out) {
+    if (!c) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: multi-device contexts keep no history");
+    if (!p) return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: no parameters");
+    if (int rc = rp_check(c, &p->rp, "bdpt_preview_denoise")) return rc;
+    if (!colors_out && !weight_out && !rgba_out) return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: no output buffer");
+    if (p->levels < 0 || p->levels > 8) return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: levels %d outside 0..8", p->levels);
+    if (p->normal_power < 0 || p->normal_power > 6)
+        return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: normal_power %d outside 0..6", p->normal_power);
+    if (!(p->sigma_color > 0.f)) return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: sigma_color must be > 0");
+    if (!(p->count_ref > 0.f && p->count_ref < INFINITY))
+        return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: count_ref must be > 0 and finite");
+    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_preview_denoise: camera not set");
+    if (c->cpu) {
+        const auto t0 = std::chrono::steady_clock::now();
+        bdpt_cpu_preview_denoise(c->cpu, p, colors_out, weight_out, rgba_out);
+        c->pv_cpu_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        c->pv_ran = true;
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t np = (size_t)c->W * c->H;
+    hist_bufs b;
+    if (int rc = hist_alloc(c, &b)) return rc;
+    if (!c->d_dn && hipMalloc(&c->d_dn, 3 * sizeof(float4) * np) != hipSuccess) {
+        c->d_dn = nullptr;
+        return fail(c, BDPT_ENOMEM, "bdpt_preview_denoise: guide, ping and pong buffers (%zu B)", 3 * sizeof(float4) * np);
+    }
+    for (hipEvent_t& e : c->pv_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    if (int rc = join_fold(c)) return rc;
+    HIPCHK(c, hipEventRecord(c->pv_ev[0], c->stream));
+    bdpt_aov_args av;
+    bool bvh = false;
+    if (int rc = aov_launch(c, c->cam, 0, 0, c->W, c->H, 0, 0u, &av, &bvh, nullptr, nullptr)) return rc;
+    float4 *guide = c->d_dn, *ping = c->d_dn + np, *pong = c->d_dn + 2 * np;
+    const dim3 block(256);
+    bdpt_reproject_args rv;
+    rp_args(c, &p->rp, av, b, &rv);
+    if (p->levels == 0) {
+        rv.out3 = colors_out ? b.out3 : nullptr;
+        rv.weight = weight_out ? b.weight : nullptr;
+        rv.rgba = rgba_out ? b.rgba : nullptr;
+    } else {
+        bool pack = false;
+        if (const char* e = getenv("BDPT_PREVIEW_GUIDE")) pack = strcmp(e, "pack") == 0;
+        if (pack) {
+            hipLaunchKernelGGL(bdpt_denoise_pack_kernel, dim3((unsigned)((np + 255) / 256)), block, 0, c->stream,
+                               (const int*)av.id, (const bdpt_dev_vec*)av.normal, (const bdpt_dev_vec*)nullptr,
+                               (const bdpt_dev_sphere*)c->d_sph, rv.all_materials, guide, (float4*)nullptr, (int)np);
+            HIPCHK(c, hipGetLastError());
+        } else {
+            rv.dn_guide = guide;
+        }
+        rv.next = ping;
+        rv.clamp_next = 1;
+    }
+    {
+        const int btw = rv.rows ? BDPT_RP_ROW_BTW : BDPT_RP_BTW, bth = rv.rows ? BDPT_RP_ROW_BTH : BDPT_RP_BTH;
+        const dim3 grid((unsigned)((c->W + btw - 1) / btw), (unsigned)((c->H + bth - 1) / bth), 1);
+        hipLaunchKernelGGL(bdpt_reproject_kernel, grid, block, 0, c->stream, rv);
+        HIPCHK(c, hipGetLastError());
+    }
+    bdpt_preview_args v;
+    memset(&v, 0, sizeof(v));
+    v.W = c->W; v.H = c->H;
+    v.guide = guide;
+    v.gamma_thr = c->d_thr;
+    v.c2 = 2.f / p->count_ref;
+    // tile shape and LDS staging: the denoiser's choices and switches
+    v.rows = 1;
+    bool lds = true;
+    if (const char* e = getenv("BDPT_DENOISE_TILE")) v.rows = atoi(e) == 64;
+    if (const char* e = getenv("BDPT_DENOISE_LDS")) lds = atoi(e) == 1;
+    const float isc0 = 1.0f / (p->sigma_color * p->sigma_color);
+    for (int k = 0; k < p->levels; k++) {
+        const bool last = k == p->levels - 1;
+        v.step = 1 << k;
+        v.isc = isc0 * (float)(1 << (2 * k));
+        v.cur = k % 2 ? pong : ping;
+        v.nxt = last ? nullptr : (k % 2 ? ping : pong);
+        v.out3 = last && colors_out ? b.out3 : nullptr;
+        v.weight = last && weight_out ? b.weight : nullptr;
+        v.rgba = last && rgba_out ? b.rgba : nullptr;
+        const bool staged = lds && v.step <= BDPT_DN_LDS_MAX_STEP;
+        const int btw = staged || !v.rows ? BDPT_DN_BTW : BDPT_DN_ROW_BTW;
+        const int bth = staged || !v.rows ? BDPT_DN_BTH : BDPT_DN_ROW_BTH;
+        const dim3 grid((unsigned)((c->W + btw - 1) / btw), (unsigned)((c->H + bth - 1) / bth), 1);
+        void* kargs[] = {&v};
+        HIPCHK(c, hipLaunchKernel(bdpt_preview_level_table[staged][p->normal_power], grid, block, kargs, 0, c->stream));
+    }
+    HIPCHK(c, hipEventRecord(c->pv_ev[1], c->stream));
+    c->pv_ran = true;
+    if (colors_out) HIPCHK(c, hipMemcpyAsync(colors_out, b.out3, sizeof(bdpt_vec) * np, hipMemcpyDeviceToHost, c->stream));
+    if (weight_out) HIPCHK(c, hipMemcpyAsync(weight_out, b.weight, sizeof(float) * np, hipMemcpyDeviceToHost, c->stream));
+    if (rgba_out) HIPCHK(c, hipMemcpyAsync(rgba_out, b.rgba, 4 * np, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return units_verdict(c);                                 // a frame known to be invalid is an error
+}
+
+int bdpt_last_preview_ms(bdpt_ctx* c, float* ms) {
+    if (!c || !ms) return BDPT_EINVAL;
+    if (!c->pv_ran) return fail(c, BDPT_ESTATE, "bdpt_last_preview_ms: no preview denoised");
+    if (c->cpu) {
+        *ms = c->pv_cpu_ms;
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(c->pv_ev[1]));
+    HIPCHK(c, hipEventElapsedTime(ms, c->pv_ev[0], c->pv_ev[1]));
     return BDPT_OK;
 }
 

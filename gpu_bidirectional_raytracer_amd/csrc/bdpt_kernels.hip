@@ -2127,9 +2127,12 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_denoise_pack_kernel(
     if (i >= count) return;
     int g = id[i];
     if (g >= 0 && !all_materials && sph[g].refl != BDPT_DEV_DIFF) g = -1;
-    const bdpt_dev_vec n = normal[i], c = colors[i];
+    const bdpt_dev_vec n = normal[i];
     guide[i] = make_float4(n.x, n.y, n.z, __int_as_float(g));
-    ping[i] = make_float4(c.x, c.y, c.z, 0.f);
+    if (ping) {                                          // nullptr: the guide records alone
+        const bdpt_dev_vec c = colors[i];
+        ping[i] = make_float4(c.x, c.y, c.z, 0.f);
+    }
 }
 
 // 1.f / x, correctly rounded, for x >= 1 or NaN (1 + a product that is non-negative or NaN): one
@@ -2280,6 +2283,9 @@ extern "C" const void* bdpt_denoise_level_table[2][7] = {
 // operation, fp32 without contraction, dot() as (x + y) + z, every reciprocal through rcp_rn
 // (library division outside [2^-125, 2^125): cz = 0, a denormal sw), denormals kept.
 
+// clampc of bdpt_preview_denoise: a record's count, 0 or inside [2^-20, 2^40]
+__device__ __forceinline__ float pv_clampc(float w) { return w == 0.f ? 0.f : fminf(fmaxf(w, 0x1p-20f), 0x1p40f); }
+
 // History records from planes: guide = {position, id} (either pair of pointers may be null).
 extern "C" __global__ __launch_bounds__(256) void bdpt_history_pack_kernel(
     const int* __restrict__ id, const bdpt_dev_vec* __restrict__ position, const bdpt_dev_vec* __restrict__ colors,
@@ -2370,7 +2376,13 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_reproject_kernel(bdpt_rep
         const float rt = rcp_rn(tot);
         o = mk((n * c.x + m * h.x) * rt, (n * c.y + m * h.y) * rt, (n * c.z + m * h.z) * rt);
     }
-    if (v.next) v.next[i] = make_float4(o.x, o.y, o.z, tot);
+    if (v.next) v.next[i] = make_float4(o.x, o.y, o.z, v.clamp_next ? pv_clampc(tot) : tot);
+    if (v.dn_guide) {                                    // the denoiser's guide record of the pixel
+        int g = id1;
+        if (g >= 0 && !v.all_materials && v.sph[g].refl != BDPT_DEV_DIFF) g = -1;
+        const bdpt_dev_vec n3 = v.normal[i];
+        v.dn_guide[i] = make_float4(n3.x, n3.y, n3.z, __int_as_float(g));
+    }
     if (v.out3) {
         bdpt_dev_vec ov;
         ov.x = o.x; ov.y = o.y; ov.z = o.z;
@@ -2379,4 +2391,169 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_reproject_kernel(bdpt_rep
     if (v.weight) v.weight[i] = tot;
     if (v.rgba) v.rgba[i] = bdpt_dev_to_rgba(o.x, o.y, o.z, v.gamma_thr);
 }
+// ---------------------------------------------------------------------------------------------
+// The reprojected preview, denoised with per-pixel sample counts (include/bdpt.h
+// bdpt_preview_denoise; no reference counterpart).  Host sequence on the context's
+// stream: bdpt_aov_kernel once, bdpt_reproject_kernel writing its {o, clampc(tot)} record into the
+// ping buffer and the guide record next to it, then one level kernel per level, ping-pong.  The
+// level kernels are the denoiser's with the count in the colour record's .w: the same 32-byte
+// records, tiles and LDS staging.  Numerics as above; a_p + a_q lies in [2^-20, 2^41], inside the
+// fast reciprocal's range, and sw / su is the library division.
+
+// one used tap (a_q > 0); a centre without a count (a_p == 0) stops nothing: wc = 1.f
+template <int NP>
+__device__ __forceinline__ void pv_tap(float hw, float isc, float c2, f3 n_p, f3 c_p, float a_p, float4 gq, float4 cq,
+                                       float& su, float& sw, f3& sc) {
+    const float d = dot(n_p, mk(gq.x, gq.y, gq.z));
+    float wn = d > 0.f ? d : 0.f;
+#pragma unroll
+    for (int r = 0; r < NP; r++) wn = wn * wn;
+    const f3 q = mk(cq.x, cq.y, cq.z);
+    const f3 dc = sub(q, c_p);
+    const float e2 = dot(dc, dc);
+    const float a_q = cq.w;
+    float wc = 1.f;
+    if (a_p != 0.f) {
+        const float g = ((a_p * a_q) * rcp_rn_inrange(a_p + a_q)) * c2;
+        wc = rcp_rn_ge1(1.f + (e2 * isc) * g);           // the product is non-negative or NaN
+    }
+    const float u = (hw * wn) * wc;
+    const float w = u * a_q;
+    su = su + u;
+    sw = sw + w;
+    sc = add(sc, smul(w, q));
+}
+
+__device__ __forceinline__ void pv_store(const bdpt_preview_args& v, int i, f3 o, float a) {
+    if (v.nxt) v.nxt[i] = make_float4(o.x, o.y, o.z, a);
+    if (v.out3) {
+        bdpt_dev_vec ov;
+        ov.x = o.x; ov.y = o.y; ov.z = o.z;
+        v.out3[i] = ov;
+    }
+    if (v.weight) v.weight[i] = a;
+    if (v.rgba) v.rgba[i] = bdpt_dev_to_rgba(o.x, o.y, o.z, v.gamma_thr);
+}
+
+// the centre's result from the sums; `used`: at least one tap counted
+__device__ __forceinline__ void pv_finish(const bdpt_preview_args& v, int i, bool used, f3 c_p, float a_p, float su,
+                                          float sw, f3 sc) {
+    if (!used) {
+        pv_store(v, i, c_p, a_p);
+        return;
+    }
+    pv_store(v, i, smul(rcp_rn(sw), sc), pv_clampc(sw / su));
+}
+
+// One level, taps straight from L1 / L2 (bdpt_denoise_level_t with counts).
+template <int NP>
+__global__ __launch_bounds__(256) void bdpt_preview_level_t(bdpt_preview_args v) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = v.rows ? (int)blockIdx.x * BDPT_DN_ROW_BTW + lane
+                         : (int)blockIdx.x * BDPT_DN_BTW + wave * 8 + (lane & 7);
+    const int y = v.rows ? (int)blockIdx.y * BDPT_DN_ROW_BTH + wave
+                         : (int)blockIdx.y * BDPT_DN_BTH + (lane >> 3);
+    if (x >= v.W || y >= v.H) return;                    // (no cross-lane operation below)
+    const int i = y * v.W + x;
+    const float4 gp = v.guide[i], cp4 = v.cur[i];
+    const f3 c_p = mk(cp4.x, cp4.y, cp4.z);
+    const float a_p = cp4.w;
+    const int gid = __float_as_int(gp.w);
+    if (gid < 0) {                                       // copied through, colour and count
+        pv_store(v, i, c_p, a_p);
+        return;
+    }
+    const f3 n_p = mk(gp.x, gp.y, gp.z);
+    constexpr float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
+    float su = 0.f, sw = 0.f;
+    f3 sc = mk(0.f, 0.f, 0.f);
+    bool used = false;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        const int qy = y + (j - 2) * v.step;
+        if (qy < 0 || qy >= v.H) continue;
+        // the row's ten loads are issued together; a tap outside the frame reads the centre
+        // (always a valid address) and is not used
+        float4 gq[5], cq[5];
+        bool in[5];
+#pragma unroll
+        for (int t = 0; t < 5; t++) {
+            const int qx = x + (t - 2) * v.step;
+            in[t] = qx >= 0 && qx < v.W;
+            const int q = in[t] ? qy * v.W + qx : i;
+            gq[t] = v.guide[q];
+            cq[t] = v.cur[q];
+        }
+#pragma unroll
+        for (int t = 0; t < 5; t++)
+            if (in[t] && __float_as_int(gq[t].w) == gid && cq[t].w > 0.f) {
+                pv_tap<NP>(hk[j] * hk[t], v.isc, v.c2, n_p, c_p, a_p, gq[t], cq[t], su, sw, sc);
+                used = true;
+            }
+    }
+    pv_finish(v, i, used, c_p, a_p, su, sw, sc);
+}
+
+// The same level with the 32 x 8 tile and its halo staged in LDS (bdpt_denoise_level_lds_t with
+// counts): steps 1 and 2 only; positions outside the frame hold the id -2.
+template <int NP>
+__global__ __launch_bounds__(256) void bdpt_preview_level_lds_t(bdpt_preview_args v) {
+    __shared__ float4 sg[BDPT_DN_LDS_W * BDPT_DN_LDS_H], scol[BDPT_DN_LDS_W * BDPT_DN_LDS_H];
+    const int halo = 2 * v.step;                         // <= 4 (the host launches steps 1 and 2 only)
+    const int rw = BDPT_DN_BTW + 2 * halo, rh = BDPT_DN_BTH + 2 * halo;
+    const int bx0 = (int)blockIdx.x * BDPT_DN_BTW - halo, by0 = (int)blockIdx.y * BDPT_DN_BTH - halo;
+    for (int k = threadIdx.x; k < rw * rh; k += 256) {   // rw * rh <= BDPT_DN_LDS_W * BDPT_DN_LDS_H
+        const int ry = k / rw, rx = k - ry * rw;
+        const int gx = bx0 + rx, gy = by0 + ry;
+        float4 g = make_float4(0.f, 0.f, 0.f, __int_as_float(-2)), c = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (gx >= 0 && gx < v.W && gy >= 0 && gy < v.H) {
+            g = v.guide[gy * v.W + gx];
+            c = v.cur[gy * v.W + gx];
+        }
+        sg[k] = g;
+        scol[k] = c;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lx = wave * 8 + (lane & 7), ly = lane >> 3;
+    const int x = (int)blockIdx.x * BDPT_DN_BTW + lx, y = (int)blockIdx.y * BDPT_DN_BTH + ly;
+    if (x >= v.W || y >= v.H) return;
+    const int i = y * v.W + x, li = (ly + halo) * rw + lx + halo;
+    const float4 gp = sg[li], cp4 = scol[li];
+    const f3 c_p = mk(cp4.x, cp4.y, cp4.z);
+    const float a_p = cp4.w;
+    const int gid = __float_as_int(gp.w);
+    if (gid < 0) {
+        pv_store(v, i, c_p, a_p);
+        return;
+    }
+    const f3 n_p = mk(gp.x, gp.y, gp.z);
+    constexpr float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
+    float su = 0.f, sw = 0.f;
+    f3 sc = mk(0.f, 0.f, 0.f);
+    bool used = false;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+#pragma unroll
+        for (int t = 0; t < 5; t++) {
+            const int q = li + (j - 2) * v.step * rw + (t - 2) * v.step;
+            const float4 gq = sg[q];
+            if (__float_as_int(gq.w) != gid) continue;
+            const float4 cq = scol[q];
+            if (!(cq.w > 0.f)) continue;
+            pv_tap<NP>(hk[j] * hk[t], v.isc, v.c2, n_p, c_p, a_p, gq, cq, su, sw, sc);
+            used = true;
+        }
+    }
+    pv_finish(v, i, used, c_p, a_p, su, sw, sc);
+}
+
+// host-side launch table: [LDS staging][normal_power]
+#define BDPT_PV(NP) (const void*)&bdpt_preview_level_t<NP>
+#define BDPT_PVL(NP) (const void*)&bdpt_preview_level_lds_t<NP>
+extern "C" const void* bdpt_preview_level_table[2][7] = {
+    {BDPT_PV(0), BDPT_PV(1), BDPT_PV(2), BDPT_PV(3), BDPT_PV(4), BDPT_PV(5), BDPT_PV(6)},
+    {BDPT_PVL(0), BDPT_PVL(1), BDPT_PVL(2), BDPT_PVL(3), BDPT_PVL(4), BDPT_PVL(5), BDPT_PVL(6)}};
+#undef BDPT_PV
+#undef BDPT_PVL
 #endif  // BDPT_JIT

@@ -5,7 +5,7 @@
  *
  *   smallpt [<width> <height> <scene.scn>] [--spp N] [--batch B] [--keys KEYS] [--out F.ppm]
  *           [--device D | --gpus N | --devices D0,D1,...] [--tile ROWS] [--seed S] [--dat PATH]
- *           [--denoise [--denoise-levels N] [--denoise-sigma S] [--denoise-all]]
+ *           [--denoise [--denoise-levels N] [--denoise-sigma S] [--denoise-all] [--denoise-count N]]
  *           [--reproject [--reproject-history N] [--reproject-tol T]]
  *
  * Without positional arguments the built-in CornellSpheres scene is used (smallpt_cpu.c:400).
@@ -29,6 +29,9 @@
  * --out is written from the preview's pixels (bdpt_reproject: history weight capped at
  * --reproject-history, default 64; plane test --reproject-tol, default 0.01); one device (or the
  * CPU) only.  The accumulation itself is unchanged.
+ * --reproject --denoise together write --out from the denoised preview (bdpt_preview_denoise: the
+ * reprojected frame filtered with per-pixel sample counts; the --denoise-* options apply,
+ * --denoise-all to both stages of that call, and --denoise-count N sets count_ref, default 8).
  */
 #include "smallpt_app.h"
 
@@ -43,6 +46,7 @@ int main(int argc, char **argv)
     const char *ckpt = NULL, *resume = NULL;
     int denoise = 0;
     bdpt_denoise_params dn = {4, 5, 0.5f, BDPT_DENOISE_DIFFUSE};
+    float count_ref = 8.f;
     h.rp.materials = BDPT_DENOISE_DIFFUSE;
     h.rp.max_history = 64.f;
     h.rp.plane_tol = 0.01f;
@@ -68,6 +72,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[a], "--denoise-levels") && a + 1 < argc) dn.levels = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--denoise-sigma") && a + 1 < argc) dn.sigma_color = strtof(argv[++a], NULL);
         else if (!strcmp(argv[a], "--denoise-all")) dn.materials = BDPT_DENOISE_ALL;
+        else if (!strcmp(argv[a], "--denoise-count") && a + 1 < argc) count_ref = strtof(argv[++a], NULL);
         else if (!strcmp(argv[a], "--reproject")) h.reuse_history = 1;
         else if (!strcmp(argv[a], "--reproject-history") && a + 1 < argc) h.rp.max_history = strtof(argv[++a], NULL);
         else if (!strcmp(argv[a], "--reproject-tol") && a + 1 < argc) h.rp.plane_tol = strtof(argv[++a], NULL);
@@ -82,8 +87,8 @@ int main(int argc, char **argv)
         fprintf(stderr, "--denoise needs one device (--device D, or -1 for the CPU)\n");
         return 1;
     }
-    if (h.reuse_history && (ndev || denoise)) {
-        fprintf(stderr, "--reproject needs one device (--device D, or -1 for the CPU) and no --denoise\n");
+    if (h.reuse_history && ndev) {
+        fprintf(stderr, "--reproject needs one device (--device D, or -1 for the CPU)\n");
         return 1;
     }
     if (npos == 3) {
@@ -155,7 +160,11 @@ int main(int argc, char **argv)
         for (int done = 0; done < spp; done += batch)
             update_rendering(&h, spp - done < batch ? spp - done : batch);
     }
-    if (out)
+    if (out && denoise && h.reuse_history) {
+        bdpt_preview_params pv = {h.rp, dn.levels, dn.normal_power, dn.sigma_color, count_ref};
+        pv.rp.materials = dn.materials;
+        rc = save_denoised_preview_ppm(&h, out, p6, &pv);
+    } else if (out)
         rc = denoise ? save_denoised_ppm(&h, out, p6, &dn)
                      : h.reuse_history ? save_preview_ppm(&h, out, p6) : save_ppm(&h, out, p6);
     if (ckpt) {

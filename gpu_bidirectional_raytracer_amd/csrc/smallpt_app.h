@@ -134,6 +134,20 @@ __attribute__((unused)) static int save_preview_ppm(host *h, const char *path, i
     return rc;
 }
 
+/* --reproject --denoise: the same file from the denoised preview's pixels (bdpt_preview_denoise) */
+__attribute__((unused)) static int save_denoised_preview_ppm(host *h, const char *path, int binary,
+                                                             const bdpt_preview_params *pv)
+{
+    unsigned char *rgba = malloc(4 * (size_t)h->width * h->height);
+    int rc = rgba ? bdpt_preview_denoise(h->ctx, pv, NULL, NULL, rgba) : BDPT_ENOMEM;
+    if (rc == BDPT_OK)
+        rc = binary ? bdpt_save_ppm_binary(path, rgba, h->width, h->height)
+                    : bdpt_save_ppm(path, rgba, h->width, h->height);
+    report(h, rc, "Denoised preview SavePPM");
+    free(rgba);
+    return rc;
+}
+
 /* what a checkpoint carries besides the frame: the pass schedule and the host counters */
 typedef struct {
     bdpt_pass_state ps;

@@ -391,6 +391,58 @@ int  bdpt_reproject(bdpt_ctx *ctx, const bdpt_reproject_params *params, bdpt_vec
                     float *weight_out, unsigned char *rgba_out);
 int  bdpt_last_reproject_ms(bdpt_ctx *ctx, float *ms);
 
+/* ---- the reprojected preview, denoised with per-pixel sample counts (no reference counterpart;
+ * DESIGN.md 4f) ----
+ * One call: the reprojected frame in, the filtered frame out.  An a-trous filter as bdpt_denoise's
+ * in which every record carries a sample count: a tap is weighted by its count, and the colour
+ * stopping is scaled by how much the two counts say the pixels may differ.  fp32, no contraction,
+ * in the order written; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; 1/x is the correctly rounded
+ * reciprocal and a / b the correctly rounded IEEE division; denormals are kept; a tap that is not
+ * used is skipped, not weighted by zero.  The GPU, the CPU backend and the tests' numpy statement
+ * form the same bits.
+ *   input     (o[p], tot[p]) = out and weight_out of bdpt_reproject under rp, exactly as defined
+ *             there, from the history present or none.
+ *   guides    id[p], n[p]: the unjittered first hit under the current camera, as for bdpt_denoise.
+ *   eligible  as for bdpt_denoise with materials = rp.materials (one setting for both stages).
+ *   levels == 0   colors_out = o, weight_out = tot, rgba_out = the RGBA of o: bit for bit the
+ *             outputs of bdpt_reproject.
+ *   clamp     for levels >= 1 a record's count is a = clampc(W): 0 when W == 0, otherwise
+ *             fminf(fmaxf(W, 0x1p-20f), 0x1p40f).  It is applied when a record is written: at entry
+ *             to tot, and to every level's output count.  a_p*a_q and a_p + a_q then stay inside
+ *             [2^-40, 2^80], so absurd uploaded weights or max_history = +inf cannot form 0*inf.
+ *   level k   = 0 .. levels-1, step s = 2^k, h and isc_k as for bdpt_denoise, c2 = 2.f / count_ref.
+ *             An ineligible pixel is copied through, colour and count.  For an eligible centre p:
+ *             su = sw = +0, sc = (+0, +0, +0); for j = 0..4 (rows, outer), for i = 0..4 (columns), a
+ *             tap q is used iff it is inside the frame, id[q] == id[p] and a_q > 0; a used tap adds
+ *               d  = dot(n_p, n_q);  wn = max(d, 0), then wn = wn*wn normal_power times
+ *               dc = cur[q] - cur[p];  e2 = dot(dc, dc)
+ *               g  = ((a_p*a_q) * (1/(a_p + a_q))) * c2;  wc = 1 / (1 + (e2*isc_k)*g)
+ *                    (a_p == 0: wc = 1.f; the centre itself is then not a used tap)
+ *               u  = ((h[j]*h[i]) * wn) * wc;  w = u * a_q
+ *               su = su + u;  sw = sw + w;  sc = sc + w*cur[q]
+ *             No tap used: out = cur[p], count a_p (= 0).  Otherwise out = sc * (1/sw) and the new
+ *             count is clampc(sw / su).  Level k+1 reads level k's colours and counts.
+ * Why: a_q-weighting is the inverse-variance combination of means of a_q samples; two pixels of one
+ * true colour differ with variance proportional to 1/a_p + 1/a_q, hence the stopping term scaled by
+ * a_p*a_q/(a_p + a_q), normalised so that two pixels of count_ref passes each give g == 1; the
+ * carried count is the u-weighted mean count (never more than a tap had); sw / su is a true
+ * division so that uniform counts stay exactly uniform -- with 8 passes everywhere, no history and
+ * count_ref = 8 the call returns bdpt_denoise's bits.
+ *   levels 0..8, normal_power 0..6, sigma_color > 0 (+inf allowed), count_ref > 0 and finite, rp as
+ *   bdpt_reproject checks it.  Defaults: levels 4, normal_power 5, sigma_color 0.5, count_ref 8.
+ * colors_out, weight_out: W*H of the last level; rgba_out through the toInt thresholds and alpha of
+ * bdpt_read_pixels.  Any may be NULL, not all.  Synchronous, ordered after whatever is queued, and
+ * like bdpt_reproject it writes nothing but its own buffers: the history, accumulation, counters,
+ * pixels, tables, VLPs, path timing, the auto stream mode's measurements and shards are untouched.
+ * BDPT_EINVAL: anything out of range, all outputs NULL, a multi-device context.  BDPT_ESTATE: no
+ * camera set.  bdpt_last_preview_ms: device time of the last successful call's kernels alone (HIP
+ * events; wall time on the CPU backend), BDPT_ESTATE before the first. */
+typedef struct { bdpt_reproject_params rp; int levels; int normal_power;
+                 float sigma_color; float count_ref; } bdpt_preview_params;
+int  bdpt_preview_denoise(bdpt_ctx *ctx, const bdpt_preview_params *params, bdpt_vec *colors_out,
+                          float *weight_out, unsigned char *rgba_out);
+int  bdpt_last_preview_ms(bdpt_ctx *ctx, float *ms);
+
 /* ---- optional display: HIP-GL interop ----
  * The caller owns the window, its OpenGL context (current on the calling thread) and a
  * pixel-unpack buffer of at least 4*W*H bytes (glGenBuffers + glBufferData(GL_PIXEL_UNPACK_BUFFER,
