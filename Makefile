@@ -116,7 +116,7 @@ endif
 ASAN_FLAGS := -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -g -O1 -ffp-contract=off
 ASAN_DIR   := tests/native/_asan
 asan: $(ASAN_DIR)/smallpt_asan $(ASAN_DIR)/oracle_asan $(ASAN_DIR)/aov_asan $(ASAN_DIR)/denoise_asan $(ASAN_DIR)/reproject_asan \
-      $(ASAN_DIR)/preview_asan
+      $(ASAN_DIR)/preview_asan $(ASAN_DIR)/noise_asan
 
 $(ASAN_DIR):
 	mkdir -p $(ASAN_DIR)
@@ -129,8 +129,9 @@ $(ASAN_DIR)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h |
 
 # (asan_cpu_abi_denoise.cpp = asan_cpu_abi.cpp + the bdpt_denoise entry point smallpt --denoise calls;
 # asan_cpu_abi_reproject.cpp = that + the history entry points smallpt --reproject calls;
-# asan_cpu_abi_preview.cpp = that + bdpt_preview_denoise, which smallpt --reproject --denoise calls)
-$(ASAN_DIR)/asan_cpu_abi.o: tests/native/asan_cpu_abi_preview.cpp tests/native/asan_cpu_abi_reproject.cpp tests/native/asan_cpu_abi_denoise.cpp tests/native/asan_cpu_abi.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h | $(ASAN_DIR)
+# asan_cpu_abi_preview.cpp = that + bdpt_preview_denoise, which smallpt --reproject --denoise calls;
+# asan_cpu_abi_noise.cpp = that + the noise estimate's entry points smallpt --until calls)
+$(ASAN_DIR)/asan_cpu_abi.o: tests/native/asan_cpu_abi_noise.cpp tests/native/asan_cpu_abi_preview.cpp tests/native/asan_cpu_abi_reproject.cpp tests/native/asan_cpu_abi_denoise.cpp tests/native/asan_cpu_abi.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h | $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -std=c++17 -c $< -o $@
 
 $(ASAN_DIR)/bdpt_oracle.o: oracle/bdpt_oracle.c include/bdpt.h | $(ASAN_DIR)
@@ -157,6 +158,10 @@ $(ASAN_DIR)/reproject_asan: tests/native/reproject_asan.cpp $(CSRC)/bdpt_cpu.h i
 
 # the CPU backend's denoised preview (bdpt_cpu_preview_denoise) driven directly; tests/test_preview_asan.py
 $(ASAN_DIR)/preview_asan: tests/native/preview_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
+	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
+
+# the CPU backend's noise estimate (bdpt_cpu_noise_*) driven directly; tests/test_noise_asan.py
+$(ASAN_DIR)/noise_asan: tests/native/noise_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
 	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
 
 clean:

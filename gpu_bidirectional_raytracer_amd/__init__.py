@@ -19,7 +19,7 @@ import numpy as np
 
 from ._lib import (BDPT_OK, CHOICES, COUNTER_CAP, DEFAULT_DAT, DIFF, FEATURES, KEY_DOWN, KEY_LEFT, KEY_PAGE_DOWN,
                    KEY_PAGE_UP, KEY_RIGHT, KEY_UP, LIGHT_POINTS, LITE, RAND_N, REFR, SCENE_DIR, SPEC,
-                   DENOISE_MATERIALS, AovBuffers, BdptError, Camera, DenoiseParams, LightPath, PassState, PreviewParams,
+                   DENOISE_MATERIALS, AovBuffers, BdptError, Camera, DenoiseParams, LightPath, NoiseParams, NoiseSummary, PassState, PreviewParams,
                    RandState, ReprojectParams, Sphere, Vec, lib)
 
 __all__ = [
@@ -571,6 +571,64 @@ class Renderer:
         self._chk(lib.bdpt_last_preview_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
+    # -- per-tile noise estimate (no reference counterpart; include/bdpt.h bdpt_noise_estimate)
+    def noise_mark(self) -> None:
+        """Take the frame as it stands (colours and per-pixel counts) as the mark the next
+        noise_estimate() measures against."""
+        self._chk(lib.bdpt_noise_mark(self._h))
+
+    def noise_clear(self) -> None:
+        self._chk(lib.bdpt_noise_clear(self._h))
+
+    def noise_tiles(self) -> Tuple[int, int]:
+        """(tiles_x, tiles_y) of the 32 x 8 tile grid."""
+        tx, ty = ctypes.c_int(), ctypes.c_int()
+        self._chk(lib.bdpt_noise_tiles(self._h, ctypes.byref(tx), ctypes.byref(ty)))
+        return tx.value, ty.value
+
+    def noise_read_mark(self) -> Tuple[np.ndarray, np.ndarray]:
+        """The mark's colours [H, W, 3] float32 and counts [H, W] uint32 (0: no mark)."""
+        col = np.empty((self.height, self.width, 3), np.float32)
+        cnt = np.empty((self.height, self.width), np.uint32)
+        self._chk(lib.bdpt_noise_read_mark(self._h, _ptr(col), _ptr(cnt)))
+        return col, cnt
+
+    def noise_write_mark(self, colors, counter) -> None:
+        col = np.ascontiguousarray(colors, np.float32).reshape(self.height, self.width, 3)
+        cnt = np.ascontiguousarray(counter, np.uint32).reshape(self.height, self.width)
+        self._chk(lib.bdpt_noise_write_mark(self._h, _ptr(col), _ptr(cnt)))
+
+    def noise_estimate(self, dark: float = 0.01, threshold: float = 0.05, remark: bool = False,
+                       pixels: bool = False) -> dict:
+        """How noisy the frame is, from how far the running mean has moved since the mark: per
+        pixel (|B - A| summed over the channels) * sqrt(mn / (cnt - mn)) / sqrt(max(B's channel sum,
+        dark)), valid where the samples since the mark are at least half the marked ones; averaged
+        over 32 x 8 tiles.  remark=True lets every pixel whose count has doubled since its mark (or
+        that has none) take the present frame as its mark afterwards.  Returns the summary
+        (valid_pixels, pending_pixels, tiles_x, tiles_y, valid_tiles, tiles_over, mean, max_tile)
+        with tile_error float32 and tile_valid uint32 as [tiles_y, tiles_x] arrays, and with
+        pixels=True error as [H, W] float32 (-1 where not valid).  Changes nothing of the context
+        but the mark."""
+        prm = NoiseParams(float(dark), float(threshold), int(bool(remark)))
+        tx, ty = self.noise_tiles()
+        err = np.empty((self.height, self.width), np.float32) if pixels else None
+        te = np.empty((ty, tx), np.float32)
+        tv = np.empty((ty, tx), np.uint32)
+        sm = NoiseSummary()
+        self._chk(lib.bdpt_noise_estimate(self._h, ctypes.byref(prm), _ptr(err) if pixels else None, _ptr(te),
+                                          _ptr(tv), ctypes.byref(sm)))
+        out = {name: getattr(sm, name) for name, _ in NoiseSummary._fields_}
+        out["tile_error"], out["tile_valid"] = te, tv
+        if pixels:
+            out["error"] = err
+        return out
+
+    def last_noise_ms(self) -> float:
+        """Device time (ms) of the last noise_estimate call's kernel alone."""
+        ms = ctypes.c_float()
+        self._chk(lib.bdpt_last_noise_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
     def device_buffers(self) -> Tuple[int, int, int]:
         c, n, p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         self._chk(lib.bdpt_device_buffers(self._h, ctypes.byref(c), ctypes.byref(n), ctypes.byref(p)))
@@ -660,6 +718,28 @@ class SmallPT:
             self.UpdateRendering2()
         if self.flag > 1:
             self.UpdateRendering(npass)
+
+    def RenderUntil(self, threshold: float = 0.05, max_passes: int = 4096, batch: int = 8,
+                    dark: float = 0.01, pixels: bool = False) -> dict:
+        """Render until the frame is good enough instead of a fixed number of passes (no reference
+        counterpart): IdleFunc(batch), then Renderer.noise_estimate(remark=True), repeated.  Stops
+        as converged when some pixel is valid, none is pending and no tile's error is over
+        `threshold`; as not converged once current_sample >= max_passes.  Returns the last
+        estimate's dict (pixels=True: with its per-pixel `error`) with `passes` (current_sample)
+        and `converged`.  The frame is exactly what
+        the same IdleFunc(batch) calls render.  ReInit and ReInitScene clear the mark through the
+        calls they make."""
+        if batch < 1:
+            raise ValueError("batch must be >= 1")
+        while True:
+            self.IdleFunc(batch)
+            est = self.renderer.noise_estimate(dark=dark, threshold=threshold, remark=True, pixels=pixels)
+            converged = est["valid_pixels"] > 0 and est["pending_pixels"] == 0 and est["tiles_over"] == 0
+            if converged or self.current_sample >= max_passes:
+                break
+        est["passes"] = self.current_sample
+        est["converged"] = bool(converged)
+        return est
 
     def ReInit(self, realloc: bool = True) -> None:          # smallpt_cpu.c:373-387
         if realloc:

@@ -73,6 +73,21 @@ class PreviewParams(ctypes.Structure):
                 ("sigma_color", ctypes.c_float), ("count_ref", ctypes.c_float)]
 
 
+class NoiseParams(ctypes.Structure):
+    """bdpt_noise_params."""
+    _fields_ = [("dark", ctypes.c_float), ("threshold", ctypes.c_float), ("remark", ctypes.c_int)]
+
+
+class NoiseSummary(ctypes.Structure):
+    """bdpt_noise_summary."""
+    _fields_ = [("valid_pixels", ctypes.c_longlong), ("pending_pixels", ctypes.c_longlong),
+                ("tiles_x", ctypes.c_int), ("tiles_y", ctypes.c_int), ("valid_tiles", ctypes.c_int),
+                ("tiles_over", ctypes.c_int), ("mean", ctypes.c_double), ("max_tile", ctypes.c_float)]
+
+
+NOISE_TW, NOISE_TH = 32, 8                                  # BDPT_NOISE_TW / BDPT_NOISE_TH
+
+
 class RandState(ctypes.Structure):
     _fields_ = [("state", ctypes.c_int * 31), ("f", ctypes.c_int), ("r", ctypes.c_int)]
 
@@ -157,6 +172,13 @@ _SIGS = [
     ("bdpt_last_reproject_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_preview_denoise", ctypes.c_int, [_P, ctypes.POINTER(PreviewParams), _P, _P, _P]),
     ("bdpt_last_preview_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
+    ("bdpt_noise_mark", ctypes.c_int, [_P]),
+    ("bdpt_noise_clear", ctypes.c_int, [_P]),
+    ("bdpt_noise_tiles", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    ("bdpt_noise_read_mark", ctypes.c_int, [_P, _P, _P]),
+    ("bdpt_noise_write_mark", ctypes.c_int, [_P, _P, _P]),
+    ("bdpt_noise_estimate", ctypes.c_int, [_P, ctypes.POINTER(NoiseParams), _P, _P, _P, ctypes.POINTER(NoiseSummary)]),
+    ("bdpt_last_noise_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_gl_register_pbo", ctypes.c_int, [_P, ctypes.c_uint]),
     ("bdpt_gl_publish", ctypes.c_int, [_P]),
     ("bdpt_gl_unregister", ctypes.c_int, [_P]),

@@ -163,6 +163,10 @@ struct bdpt_cpu_ctx {
     std::vector<bdpt_vec> hc, gpos;
     std::vector<float> hm;
     std::vector<int> gid;
+    // mark of bdpt_noise_estimate (include/bdpt.h): one 16-byte record per pixel, allocated on
+    // first use; empty while no mark was ever stored
+    struct NoiseMark { bdpt_vec c; unsigned n; };
+    std::vector<NoiseMark> mark;
 };
 
 extern "C" void bdpt_gamma_thresholds(float thr[256]);
@@ -185,9 +189,20 @@ bdpt_cpu_ctx* bdpt_cpu_create(const bdpt_sphere* spheres, unsigned n, int W, int
 
 void bdpt_cpu_destroy(bdpt_cpu_ctx* c) { delete c; }
 
-void bdpt_cpu_set_scene(bdpt_cpu_ctx* c, const bdpt_sphere* spheres, unsigned n) { c->scene.load(spheres, n); }
-void bdpt_cpu_set_camera(bdpt_cpu_ctx* c, const bdpt_camera* cam) { c->cam = *cam; c->cam_set = true; }
-void bdpt_cpu_reset_accum(bdpt_cpu_ctx* c) { std::fill(c->counter.begin(), c->counter.end(), 0u); }
+// (the calls that rewrite the accumulation other than path passes clear the noise estimate's mark)
+void bdpt_cpu_set_scene(bdpt_cpu_ctx* c, const bdpt_sphere* spheres, unsigned n) {
+    c->scene.load(spheres, n);
+    bdpt_cpu_noise_clear(c);
+}
+void bdpt_cpu_set_camera(bdpt_cpu_ctx* c, const bdpt_camera* cam) {
+    c->cam = *cam;
+    c->cam_set = true;
+    bdpt_cpu_noise_clear(c);
+}
+void bdpt_cpu_reset_accum(bdpt_cpu_ctx* c) {
+    std::fill(c->counter.begin(), c->counter.end(), 0u);
+    bdpt_cpu_noise_clear(c);
+}
 void bdpt_cpu_set_shard(bdpt_cpu_ctx* c, int shard, int nshards, int band_rows) {
     c->shard = shard; c->nshards = nshards; c->band_rows = band_rows;
 }
@@ -843,4 +858,96 @@ void bdpt_cpu_write_radiance(bdpt_cpu_ctx* c, const bdpt_vec* colors, const unsi
     memcpy(c->colors.data(), colors, sizeof(bdpt_vec) * c->colors.size());
     memcpy(c->counter.data(), counter, sizeof(unsigned) * c->counter.size());
     bdpt_cpu_update_pixels(c);
+    bdpt_cpu_noise_clear(c);
+}
+
+// Per-tile noise estimate (include/bdpt.h bdpt_noise_estimate): a plain restatement
+// of the definition there.  fp32, no contraction, in exactly this order; the HIP kernel
+// (bdpt_noise_kernel) forms the same bits.
+bool bdpt_cpu_noise_stored(const bdpt_cpu_ctx* c) { return !c->mark.empty(); }
+void bdpt_cpu_noise_clear(bdpt_cpu_ctx* c) {
+    for (auto& m : c->mark) m.n = 0u;                     // nothing while no mark was ever stored
+}
+void bdpt_cpu_noise_write_mark(bdpt_cpu_ctx* c, const bdpt_vec* colors, const unsigned* counter) {
+    c->mark.resize(c->colors.size());
+    for (size_t i = 0; i < c->mark.size(); i++) c->mark[i] = {colors[i], counter[i]};
+}
+void bdpt_cpu_noise_mark(bdpt_cpu_ctx* c) { bdpt_cpu_noise_write_mark(c, c->colors.data(), c->counter.data()); }
+void bdpt_cpu_noise_read_mark(const bdpt_cpu_ctx* c, bdpt_vec* colors, unsigned* counter) {
+    for (size_t i = 0; i < c->mark.size(); i++) {
+        if (colors) colors[i] = c->mark[i].c;
+        if (counter) counter[i] = c->mark[i].n;
+    }
+}
+
+void bdpt_cpu_noise_estimate(bdpt_cpu_ctx* c, const bdpt_noise_params* p, float* error_out, float* tile_sum,
+                             float* tile_error, unsigned* tile_valid, unsigned* tile_pending) {
+    const int W = c->W, H = c->H;
+    const int tx = (W + BDPT_NOISE_TW - 1) / BDPT_NOISE_TW, ty = (H + BDPT_NOISE_TH - 1) / BDPT_NOISE_TH;
+    if (p->remark && c->mark.empty()) c->mark.assign((size_t)W * H, {bdpt_vec{0.f, 0.f, 0.f}, 0u});
+    const bool stored = !c->mark.empty();
+    for (int by = 0; by < ty; by++)
+        for (int bx = 0; bx < tx; bx++) {
+            float v[BDPT_NOISE_TW * BDPT_NOISE_TH];
+            unsigned valid = 0, pending = 0;
+            for (int k = 0; k < BDPT_NOISE_TW * BDPT_NOISE_TH; k++) {
+                const int x = bx * BDPT_NOISE_TW + k % BDPT_NOISE_TW, y = by * BDPT_NOISE_TH + k / BDPT_NOISE_TW;
+                v[k] = 0.f;
+                if (x >= W || y >= H) continue;
+                const size_t i = (size_t)y * W + x;
+                const bdpt_vec B = c->colors[i];
+                const unsigned cnt = c->counter[i], mn = stored ? c->mark[i].n : 0u;
+                const bool ok = mn > 0u && cnt > mn && 2ull * (cnt - mn) >= mn;
+                float e = -1.0f;
+                if (ok) {
+                    const bdpt_vec A = c->mark[i].c;
+                    const float a = (float)mn, n = (float)cnt;
+                    const float dx = B.x - A.x, dy = B.y - A.y, dz = B.z - A.z;
+                    const float e1 = (fabsf(dx) + fabsf(dy)) + fabsf(dz);
+                    const float s = a / (n - a);
+                    const float f = sqrtf(s);
+                    const float lum = (B.x + B.y) + B.z;
+                    const float den = sqrtf(fmaxf(lum, p->dark));
+                    e = (e1 * f) / den;
+                    v[k] = e;
+                    valid++;
+                } else if (cnt > 0u && cnt < BDPT_COUNTER_CAP) {
+                    pending++;
+                }
+                if (error_out) error_out[i] = e;
+                if (p->remark && cnt > 0u && cnt < BDPT_COUNTER_CAP && (unsigned long long)cnt >= 2ull * mn)
+                    c->mark[i] = {B, cnt};
+            }
+            for (int m = BDPT_NOISE_TW * BDPT_NOISE_TH; m > 1; m /= 2)   // adjacent pairs, eight rounds
+                for (int k = 0; k < m / 2; k++) v[k] = v[2 * k] + v[2 * k + 1];
+            const int t = by * tx + bx;
+            if (tile_sum) tile_sum[t] = v[0];
+            if (tile_error) tile_error[t] = valid ? v[0] / (float)valid : 0.f;
+            if (tile_valid) tile_valid[t] = valid;
+            if (tile_pending) tile_pending[t] = pending;
+        }
+}
+
+// The frame's summary from the tile arrays in row-major order: the one statement of it, shared by
+// both backends (and the sanitizer build's context layer).
+void bdpt_noise_summarize(const float* tile_sum, const float* tile_error, const unsigned* tile_valid,
+                          const unsigned* tile_pending, int tiles_x, int tiles_y, float threshold,
+                          bdpt_noise_summary* out) {
+    bdpt_noise_summary s;
+    memset(&s, 0, sizeof s);
+    s.tiles_x = tiles_x;
+    s.tiles_y = tiles_y;
+    double sum = 0.;
+    float m = 0.f;
+    for (int t = 0; t < tiles_x * tiles_y; t++) {
+        s.valid_pixels += tile_valid[t];
+        s.pending_pixels += tile_pending[t];
+        s.valid_tiles += tile_valid[t] > 0u;
+        sum += (double)tile_sum[t];
+        if (tile_error[t] > m) m = tile_error[t];
+        s.tiles_over += tile_error[t] > threshold;
+    }
+    s.mean = s.valid_pixels ? sum / (double)s.valid_pixels : 0.;
+    s.max_tile = m;
+    *out = s;
 }

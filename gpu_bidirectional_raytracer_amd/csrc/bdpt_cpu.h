@@ -35,6 +35,20 @@ void bdpt_cpu_reproject(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, b
 // count-weighted denoising of the reprojected preview (include/bdpt.h bdpt_preview_denoise)
 void bdpt_cpu_preview_denoise(const bdpt_cpu_ctx* c, const bdpt_preview_params* p, bdpt_vec* colors_out,
                               float* weight_out, unsigned char* rgba_out);
+// per-tile noise estimate (include/bdpt.h bdpt_noise_estimate); the caller has checked the parameters.
+// tile_sum / tile_error / tile_valid / tile_pending: S_t, E_t, c_t and the pending count per tile,
+// tiles_x * tiles_y each; any output may be NULL
+bool bdpt_cpu_noise_stored(const bdpt_cpu_ctx* c);                          // a mark was ever stored
+void bdpt_cpu_noise_mark(bdpt_cpu_ctx* c);
+void bdpt_cpu_noise_clear(bdpt_cpu_ctx* c);
+void bdpt_cpu_noise_read_mark(const bdpt_cpu_ctx* c, bdpt_vec* colors, unsigned* counter);
+void bdpt_cpu_noise_write_mark(bdpt_cpu_ctx* c, const bdpt_vec* colors, const unsigned* counter);
+void bdpt_cpu_noise_estimate(bdpt_cpu_ctx* c, const bdpt_noise_params* p, float* error_out, float* tile_sum,
+                             float* tile_error, unsigned* tile_valid, unsigned* tile_pending);
+// the frame's summary from the tile arrays: host code shared by both backends
+void bdpt_noise_summarize(const float* tile_sum, const float* tile_error, const unsigned* tile_valid,
+                          const unsigned* tile_pending, int tiles_x, int tiles_y, float threshold,
+                          bdpt_noise_summary* out);
 bool bdpt_cpu_rand_ready(const bdpt_cpu_ctx* c);
 bool bdpt_cpu_camera_set(const bdpt_cpu_ctx* c);
 void bdpt_cpu_read_radiance(const bdpt_cpu_ctx* c, bdpt_vec* colors, unsigned* counter);

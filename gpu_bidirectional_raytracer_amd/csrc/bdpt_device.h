@@ -246,6 +246,25 @@ struct bdpt_reproject_args {
 #define BDPT_RP_ROW_BTW 64
 #define BDPT_RP_ROW_BTH 4
 
+// bdpt_noise_kernel (include/bdpt.h bdpt_noise_estimate): one 256-thread workgroup per
+// BDPT_NOISE_BTW x BDPT_NOISE_BTH tile (the path kernel's workgroup tile), thread index = slot.
+struct bdpt_noise_args {
+    int W, H, tiles_x;
+    int live;                       // 0: the mark is cleared (every mn reads 0, whatever is stored)
+    int remark;
+    float dark;
+    const bdpt_dev_vec* colors;
+    const unsigned* counter;
+    uint4* mark;                    // {mc.x, mc.y, mc.z, mn} per pixel; nullptr: none allocated
+    float* error;                   // W*H plane, or nullptr
+    float* tile_sum;                // S_t, E_t, c_t and the pending count per tile
+    float* tile_error;
+    unsigned* tile_valid;
+    unsigned* tile_pending;
+};
+#define BDPT_NOISE_BTW 32
+#define BDPT_NOISE_BTH 8
+
 // Units' pass ranges: unit_passes (P) passes each, except (taper) the launch's last <= P passes,
 // which are split in halves -- P = 8: ..., 8, 4, 2, 1, 1 -- so that the launch drains over short
 // units (the tiles' last ranges are what runs while the chip empties).  Range r starts at the

@@ -60,6 +60,9 @@ extern "C" __global__ void bdpt_history_pack_kernel(const int*, const bdpt_dev_v
                                                     const float*, float4*, float4*, int);
 extern "C" __global__ void bdpt_reproject_kernel(bdpt_reproject_args);
 extern "C" const void* bdpt_preview_level_table[2][7];   // [LDS staging][normal_power]
+extern "C" __global__ void bdpt_noise_mark_kernel(const bdpt_dev_vec*, const unsigned*, uint4*, int);
+extern "C" __global__ void bdpt_noise_kernel(bdpt_noise_args);
+static_assert(BDPT_NOISE_BTW == BDPT_NOISE_TW && BDPT_NOISE_BTH == BDPT_NOISE_TH, "the kernel's tile is the ABI's");
 
 // gamma thresholds (host, once): see bdpt_util.c
 extern "C" void bdpt_gamma_thresholds(float thr[256]);
@@ -226,6 +229,15 @@ struct bdpt_ctx {
     hipEvent_t pv_ev[2] = {nullptr, nullptr};    // around the kernels of the last call
     bool pv_ran = false;
     float pv_cpu_ms = 0.f;              // CPU backend: wall time of the last call
+    // noise estimate (bdpt_noise_estimate): the mark's 16-byte records and the results of a call
+    // (the per-pixel plane, then S, E, c and the pending count per tile), each made on first use.
+    // mark_live = false is the cleared mark: the kernel then reads every count as 0.
+    uint4* d_mark = nullptr;
+    bool mark_live = false;
+    float* d_noise = nullptr;
+    hipEvent_t nz_ev[2] = {nullptr, nullptr};    // around the kernel of the last estimate
+    bool nz_ran = false;
+    float nz_cpu_ms = 0.f;              // CPU backend: wall time of the last estimate
     unsigned gl_pbo = 0;
 };
 enum { kReduceNone = 0, kReduceRccl = 1, kReducePeer = 2 };
@@ -355,7 +367,8 @@ static void release(bdpt_ctx* c) {
     void* bufs[] = {c->d_params, c->d_rand, c->d_rndp, c->d_scp, c->d_srec, c->d_lp, c->d_sph, c->d_lights, c->d_geom, c->d_lightrec, c->d_colors,
                     c->d_counter, c->d_pixels, c->d_thr, c->d_rbuf, c->d_rmask, c->d_poolctr, c->d_uflags, c->d_uerr, c->d_bvh_nodes,
                     c->d_bvh_geom, c->d_big_geom, c->d_mat, c->d_bvh_ids, c->d_big_ids,
-                    c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc, c->d_aov, c->d_dn, c->d_hist};
+                    c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc, c->d_aov, c->d_dn, c->d_hist,
+                    c->d_mark, c->d_noise};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : c->aov_ev)
@@ -365,6 +378,8 @@ static void release(bdpt_ctx* c) {
     for (hipEvent_t e : c->rp_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->pv_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->nz_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& s : c->ring) {
         for (hipEvent_t e : s.kev) (void)hipEventDestroy(e);
@@ -953,8 +968,11 @@ void bdpt_destroy(bdpt_ctx* c) {
     delete c;
 }
 
+// (set_scene, set_camera, reset_accum and write_radiance rewrite the accumulation or what it is
+// an accumulation of: they clear the noise estimate's mark -- a flag here, the CPU backend's own)
 static int one_set_scene(bdpt_ctx* c, const bdpt_sphere* spheres, unsigned n) {
     if (!c || (n > 0 && !spheres)) return BDPT_EINVAL;
+    c->mark_live = false;
     if (c->cpu) {
         c->spheres.assign(spheres, spheres + n);
         bdpt_cpu_set_scene(c->cpu, spheres, n);
@@ -967,6 +985,7 @@ static int one_set_scene(bdpt_ctx* c, const bdpt_sphere* spheres, unsigned n) {
 
 static int one_set_camera(bdpt_ctx* c, const bdpt_camera* cam) {
     if (!c || !cam) return BDPT_EINVAL;
+    c->mark_live = false;
     if (c->cpu) bdpt_cpu_set_camera(c->cpu, cam);
     c->cam = *cam;
     c->cam_set = true;
@@ -975,6 +994,7 @@ static int one_set_camera(bdpt_ctx* c, const bdpt_camera* cam) {
 
 static int one_reset_accum(bdpt_ctx* c) {
     if (!c) return BDPT_EINVAL;
+    c->mark_live = false;
     if (c->cpu) {
         bdpt_cpu_reset_accum(c->cpu);
         return BDPT_OK;
@@ -2778,11 +2798,185 @@ int bdpt_last_preview_ms(bdpt_ctx* c, float* ms) {
     return BDPT_OK;
 }
 
+// ---- per-tile noise estimate (include/bdpt.h bdpt_noise_estimate) ---------------
+// On the context's stream, after the last fold: bdpt_noise_kernel reads colours, counters and the
+// mark's records, writes the tile arrays (and the per-pixel plane, and with remark the records of
+// the pixels that take the mark); then the read-back, and the summary on the host.  Only d_mark and
+// d_noise are written; nothing of the path passes' state is touched.
+static int nz_check(bdpt_ctx* c, const char* who) {
+    if (!c) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "%s: multi-device contexts keep no mark", who);
+    return BDPT_OK;
+}
+
+static int mark_alloc(bdpt_ctx* c) {
+    if (c->d_mark) return BDPT_OK;
+    const size_t bytes = sizeof(uint4) * (size_t)c->W * c->H;
+    if (hipMalloc(&c->d_mark, bytes) != hipSuccess) {
+        c->d_mark = nullptr;
+        return fail(c, BDPT_ENOMEM, "bdpt_noise: mark records (%zu B)", bytes);
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_mark, 0, bytes, c->stream));
+    c->mark_live = false;
+    return BDPT_OK;
+}
+
+int bdpt_noise_tiles(const bdpt_ctx* c, int* tiles_x, int* tiles_y) {
+    if (!c || c->multi) return BDPT_EINVAL;
+    if (tiles_x) *tiles_x = (c->W + BDPT_NOISE_TW - 1) / BDPT_NOISE_TW;
+    if (tiles_y) *tiles_y = (c->H + BDPT_NOISE_TH - 1) / BDPT_NOISE_TH;
+    return BDPT_OK;
+}
+
+int bdpt_noise_mark(bdpt_ctx* c) {
+    if (int rc = nz_check(c, "bdpt_noise_mark")) return rc;
+    if (c->cpu) {
+        bdpt_cpu_noise_mark(c->cpu);
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = mark_alloc(c)) return rc;
+    if (int rc = join_fold(c)) return rc;
+    const size_t np = (size_t)c->W * c->H;
+    hipLaunchKernelGGL(bdpt_noise_mark_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream,
+                       (const bdpt_dev_vec*)c->d_colors, (const unsigned*)c->d_counter, c->d_mark, (int)np);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mark_live = true;
+    return units_verdict(c);                                 // a frame known to be invalid is an error
+}
+
+int bdpt_noise_clear(bdpt_ctx* c) {
+    if (int rc = nz_check(c, "bdpt_noise_clear")) return rc;
+    if (c->cpu) bdpt_cpu_noise_clear(c->cpu);
+    c->mark_live = false;
+    return BDPT_OK;
+}
+
+int bdpt_noise_read_mark(bdpt_ctx* c, bdpt_vec* colors, unsigned* counter) {
+    if (int rc = nz_check(c, "bdpt_noise_read_mark")) return rc;
+    if (!colors && !counter) return fail(c, BDPT_EINVAL, "bdpt_noise_read_mark: no output buffer");
+    if (!(c->cpu ? bdpt_cpu_noise_stored(c->cpu) : c->d_mark != nullptr))
+        return fail(c, BDPT_ESTATE, "bdpt_noise_read_mark: no mark was ever stored");
+    if (c->cpu) {
+        bdpt_cpu_noise_read_mark(c->cpu, colors, counter);
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t np = (size_t)c->W * c->H;
+    std::vector<uint4> rec(np);
+    HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_mark, sizeof(uint4) * np, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < np; i++) {
+        if (colors) memcpy(&colors[i], &rec[i], sizeof(bdpt_vec));
+        if (counter) counter[i] = c->mark_live ? rec[i].w : 0u;
+    }
+    return BDPT_OK;
+}
+
+int bdpt_noise_write_mark(bdpt_ctx* c, const bdpt_vec* colors, const unsigned* counter) {
+    if (int rc = nz_check(c, "bdpt_noise_write_mark")) return rc;
+    if (!colors || !counter) return fail(c, BDPT_EINVAL, "bdpt_noise_write_mark: NULL argument");
+    if (c->cpu) {
+        bdpt_cpu_noise_write_mark(c->cpu, colors, counter);
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = mark_alloc(c)) return rc;
+    const size_t np = (size_t)c->W * c->H;
+    std::vector<uint4> rec(np);
+    for (size_t i = 0; i < np; i++) {
+        memcpy(&rec[i], &colors[i], sizeof(bdpt_vec));
+        rec[i].w = counter[i];
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_mark, rec.data(), sizeof(uint4) * np, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mark_live = true;
+    return BDPT_OK;
+}
+
+int bdpt_noise_estimate(bdpt_ctx* c, const bdpt_noise_params* p, float* error_out, float* tile_error,
+                        unsigned* tile_valid, bdpt_noise_summary* summary) {
+    if (int rc = nz_check(c, "bdpt_noise_estimate")) return rc;
+    if (!p) return fail(c, BDPT_EINVAL, "bdpt_noise_estimate: no parameters");
+    if (!(p->dark > 0.f)) return fail(c, BDPT_EINVAL, "bdpt_noise_estimate: dark must be > 0");
+    if (!(p->threshold >= 0.f)) return fail(c, BDPT_EINVAL, "bdpt_noise_estimate: threshold must be >= 0");
+    if (!error_out && !tile_error && !tile_valid && !summary)
+        return fail(c, BDPT_EINVAL, "bdpt_noise_estimate: no output buffer");
+    const size_t np = (size_t)c->W * c->H;
+    const int tx = (c->W + BDPT_NOISE_TW - 1) / BDPT_NOISE_TW, ty = (c->H + BDPT_NOISE_TH - 1) / BDPT_NOISE_TH;
+    const size_t nt = (size_t)tx * ty;
+    std::vector<float> S(nt), E(nt);
+    std::vector<unsigned> cv(nt), pend(nt);
+    if (c->cpu) {
+        const auto t0 = std::chrono::steady_clock::now();
+        bdpt_cpu_noise_estimate(c->cpu, p, error_out, S.data(), E.data(), cv.data(), pend.data());
+        c->nz_cpu_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    } else {
+        HIPCHK(c, hipSetDevice(c->device));
+        if (p->remark)
+            if (int rc = mark_alloc(c)) return rc;
+        const size_t bytes = sizeof(float) * (np + 4 * nt);
+        if (!c->d_noise && hipMalloc(&c->d_noise, bytes) != hipSuccess) {
+            c->d_noise = nullptr;
+            return fail(c, BDPT_ENOMEM, "bdpt_noise_estimate: result buffers (%zu B)", bytes);
+        }
+        for (hipEvent_t& e : c->nz_ev)
+            if (!e) HIPCHK(c, hipEventCreate(&e));
+        if (int rc = join_fold(c)) return rc;
+        bdpt_noise_args v;
+        memset(&v, 0, sizeof(v));
+        v.W = c->W; v.H = c->H; v.tiles_x = tx;
+        v.live = c->mark_live;
+        v.remark = p->remark != 0;
+        v.dark = p->dark;
+        v.colors = c->d_colors;
+        v.counter = c->d_counter;
+        v.mark = c->d_mark;
+        v.error = error_out ? c->d_noise : nullptr;
+        v.tile_sum = c->d_noise + np;
+        v.tile_error = v.tile_sum + nt;
+        v.tile_valid = (unsigned*)(v.tile_error + nt);
+        v.tile_pending = v.tile_valid + nt;
+        HIPCHK(c, hipEventRecord(c->nz_ev[0], c->stream));
+        hipLaunchKernelGGL(bdpt_noise_kernel, dim3((unsigned)tx, (unsigned)ty, 1), dim3(256), 0, c->stream, v);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->nz_ev[1], c->stream));
+        if (v.remark) c->mark_live = true;
+        if (error_out) HIPCHK(c, hipMemcpyAsync(error_out, v.error, sizeof(float) * np, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(S.data(), v.tile_sum, sizeof(float) * nt, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(E.data(), v.tile_error, sizeof(float) * nt, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cv.data(), v.tile_valid, sizeof(unsigned) * nt, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(pend.data(), v.tile_pending, sizeof(unsigned) * nt, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (int rc = units_verdict(c)) return rc;             // a frame known to be invalid is an error
+    }
+    c->nz_ran = true;
+    if (tile_error) memcpy(tile_error, E.data(), sizeof(float) * nt);
+    if (tile_valid) memcpy(tile_valid, cv.data(), sizeof(unsigned) * nt);
+    if (summary) bdpt_noise_summarize(S.data(), E.data(), cv.data(), pend.data(), tx, ty, p->threshold, summary);
+    return BDPT_OK;
+}
+
+int bdpt_last_noise_ms(bdpt_ctx* c, float* ms) {
+    if (!c || !ms) return BDPT_EINVAL;
+    if (!c->nz_ran) return fail(c, BDPT_ESTATE, "bdpt_last_noise_ms: no estimate made");
+    if (c->cpu) {
+        *ms = c->nz_cpu_ms;
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(c->nz_ev[1]));
+    HIPCHK(c, hipEventElapsedTime(ms, c->nz_ev[0], c->nz_ev[1]));
+    return BDPT_OK;
+}
+
 // ---- checkpoint / resume of the accumulation ----------------------------------
 // Upload colors/counter (the counterpart of bdpt_read_radiance) and recompute the pixels.  A
 // multi-device context gives each device only the pixels of its own bands (zeros elsewhere), so
 // the assembled frame is the uploaded one.
 static int one_write_radiance(bdpt_ctx* c, const bdpt_vec* colors, const unsigned* counter, bool masked) {
+    c->mark_live = false;
     if (c->cpu) {
         bdpt_cpu_write_radiance(c->cpu, colors, counter);
         return BDPT_OK;

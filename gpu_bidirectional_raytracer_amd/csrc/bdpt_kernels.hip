@@ -2556,4 +2556,86 @@ extern "C" const void* bdpt_preview_level_table[2][7] = {
     {BDPT_PVL(0), BDPT_PVL(1), BDPT_PVL(2), BDPT_PVL(3), BDPT_PVL(4), BDPT_PVL(5), BDPT_PVL(6)}};
 #undef BDPT_PV
 #undef BDPT_PVL
+
+// ---------------------------------------------------------------------------------------------
+// Per-tile noise estimate from two frames (include/bdpt.h bdpt_noise_estimate; no
+// reference counterpart).  One workgroup per 32 x 8 tile, thread index = slot, so a wave covers two
+// frame rows of 32 pixels: its loads and stores are two contiguous runs each.  Memory bound: 12 + 4
+// + 16 B read per pixel, 16 B written where a pixel takes the mark, 4 B with the per-pixel plane.
+// The adjacent-pair tree of the definition runs as an xor butterfly in the wave's lanes (strides
+// 1 .. 32: fp32 addition is commutative, so every lane, lane 0 among them, holds the value of the
+// tree over the wave's 64 slots), the four wave partials meet in LDS as (p0 + p1) + (p2 + p3): the
+// tree's last two rounds.  Counts are a ballot and a popcount per wave.  No atomics; the frame's
+// summary is formed on the host from the tile arrays.  a / b is the compiler's correctly rounded
+// division (denormals kept), the roots are bdpt_sqrt_rn.
+extern "C" __global__ __launch_bounds__(256) void bdpt_noise_mark_kernel(const bdpt_dev_vec* __restrict__ colors,
+                                                                         const unsigned* __restrict__ counter,
+                                                                         uint4* __restrict__ mark, int np) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= np) return;
+    const bdpt_dev_vec c = colors[i];
+    mark[i] = make_uint4(__float_as_uint(c.x), __float_as_uint(c.y), __float_as_uint(c.z), counter[i]);
+}
+
+extern "C" __global__ __launch_bounds__(256) void bdpt_noise_kernel(bdpt_noise_args v) {
+    __shared__ float part[4];
+    __shared__ unsigned nvalid[4], npending[4];
+    const int k = (int)threadIdx.x, lane = k & 63, wave = k >> 6;
+    const int x = (int)blockIdx.x * BDPT_NOISE_BTW + (k & (BDPT_NOISE_BTW - 1));
+    const int y = (int)blockIdx.y * BDPT_NOISE_BTH + k / BDPT_NOISE_BTW;
+    float e = 0.f;                                       // an invalid slot adds +0
+    bool ok = false, pending = false;
+    if (x < v.W && y < v.H) {                            // (no return: the reduction below needs every lane)
+        const int i = y * v.W + x;
+        const bdpt_dev_vec B = v.colors[i];
+        const unsigned cnt = v.counter[i];
+        uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+        if (v.mark) rec = v.mark[i];
+        const unsigned mn = v.live ? rec.w : 0u;
+        // 2*(cnt - mn) >= mn without the overflow: cnt - mn >= ceil(mn / 2)
+        ok = mn > 0u && cnt > mn && cnt - mn >= (mn >> 1) + (mn & 1u);
+        const bool growing = cnt > 0u && cnt < BDPT_DEV_COUNTER_CAP;
+        pending = growing && !ok;
+        float pe = -1.0f;
+        if (ok) {
+            const float a = (float)mn, n = (float)cnt;
+            const float dx = B.x - __uint_as_float(rec.x), dy = B.y - __uint_as_float(rec.y),
+                        dz = B.z - __uint_as_float(rec.z);
+            const float e1 = (fabsf(dx) + fabsf(dy)) + fabsf(dz);
+            const float s = a / (n - a);
+            const float f = bdpt_sqrt_rn(s);
+            const float lum = (B.x + B.y) + B.z;
+            const float den = bdpt_sqrt_rn(fmaxf(lum, v.dark));
+            pe = (e1 * f) / den;
+            e = pe;
+        }
+        if (v.error) v.error[i] = pe;
+        if (v.remark) {                                  // cnt >= 2*mn as (cnt >> 1) >= mn
+            const bool take = growing && (cnt >> 1) >= mn;
+            // a cleared mark becomes live again with this call: a pixel that does not take it
+            // keeps its colour and stores the count 0 it was read with
+            if (take) v.mark[i] = make_uint4(__float_as_uint(B.x), __float_as_uint(B.y), __float_as_uint(B.z), cnt);
+            else if (!v.live) v.mark[i] = make_uint4(rec.x, rec.y, rec.z, 0u);
+        }
+    }
+    float s = e;
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) s = s + __shfl_xor(s, m, 64);
+    const unsigned long long bv = __builtin_amdgcn_ballot_w64(ok), bp = __builtin_amdgcn_ballot_w64(pending);
+    if (lane == 0) {
+        part[wave] = s;
+        nvalid[wave] = (unsigned)__popcll(bv);
+        npending[wave] = (unsigned)__popcll(bp);
+    }
+    __syncthreads();
+    if (k == 0) {
+        const float S = (part[0] + part[1]) + (part[2] + part[3]);
+        const unsigned c = (nvalid[0] + nvalid[1]) + (nvalid[2] + nvalid[3]);
+        const int t = (int)blockIdx.y * v.tiles_x + (int)blockIdx.x;
+        v.tile_sum[t] = S;
+        v.tile_error[t] = c ? S / (float)c : 0.f;
+        v.tile_valid[t] = c;
+        v.tile_pending[t] = (npending[0] + npending[1]) + (npending[2] + npending[3]);
+    }
+}
 #endif  // BDPT_JIT

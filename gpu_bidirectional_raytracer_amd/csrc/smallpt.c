@@ -7,6 +7,7 @@
  *           [--device D | --gpus N | --devices D0,D1,...] [--tile ROWS] [--seed S] [--dat PATH]
  *           [--denoise [--denoise-levels N] [--denoise-sigma S] [--denoise-all] [--denoise-count N]]
  *           [--reproject [--reproject-history N] [--reproject-tol T]]
+ *           [--until E [--max-spp N]]
  *
  * Without positional arguments the built-in CornellSpheres scene is used (smallpt_cpu.c:400).
  * Like the reference, width/height get +1 (smallpt_cpu.c:409-410).  The first frame runs the
@@ -32,6 +33,11 @@
  * --reproject --denoise together write --out from the denoised preview (bdpt_preview_denoise: the
  * reprojected frame filtered with per-pixel sample counts; the --denoise-* options apply,
  * --denoise-all to both stages of that call, and --denoise-count N sets count_ref, default 8).
+ * --until E renders until the frame is good enough instead of a fixed --spp, at the start and after
+ * each key of --keys: batches of --batch passes, after each a noise estimate (bdpt_noise_estimate
+ * with remark, threshold E), until some pixel is valid, none is pending and no tile is over E, or
+ * until --max-spp passes (default 4096) are rendered; one report line per render on stderr.  One
+ * device (or the CPU) only.
  */
 #include "smallpt_app.h"
 
@@ -47,6 +53,8 @@ int main(int argc, char **argv)
     int denoise = 0;
     bdpt_denoise_params dn = {4, 5, 0.5f, BDPT_DENOISE_DIFFUSE};
     float count_ref = 8.f;
+    int until = 0, max_spp = 4096;
+    bdpt_noise_params nz = {0.01f, 0.05f, 1};
     h.rp.materials = BDPT_DENOISE_DIFFUSE;
     h.rp.max_history = 64.f;
     h.rp.plane_tol = 0.01f;
@@ -76,6 +84,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[a], "--reproject")) h.reuse_history = 1;
         else if (!strcmp(argv[a], "--reproject-history") && a + 1 < argc) h.rp.max_history = strtof(argv[++a], NULL);
         else if (!strcmp(argv[a], "--reproject-tol") && a + 1 < argc) h.rp.plane_tol = strtof(argv[++a], NULL);
+        else if (!strcmp(argv[a], "--until") && a + 1 < argc) { until = 1; nz.threshold = strtof(argv[++a], NULL); }
+        else if (!strcmp(argv[a], "--max-spp") && a + 1 < argc) max_spp = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--checkpoint") && a + 1 < argc) ckpt = argv[++a];
         else if (!strcmp(argv[a], "--resume") && a + 1 < argc) resume = argv[++a];
         else if (npos < 3) pos[npos++] = argv[a];
@@ -89,6 +99,14 @@ int main(int argc, char **argv)
     }
     if (h.reuse_history && ndev) {
         fprintf(stderr, "--reproject needs one device (--device D, or -1 for the CPU)\n");
+        return 1;
+    }
+    if (until && ndev) {
+        fprintf(stderr, "--until needs one device (--device D, or -1 for the CPU): not --gpus / --devices\n");
+        return 1;
+    }
+    if (until && (batch < 1 || !(nz.threshold >= 0.f))) {
+        fprintf(stderr, "--until: a threshold >= 0 and --batch >= 1\n");
         return 1;
     }
     if (npos == 3) {
@@ -153,12 +171,21 @@ int main(int argc, char **argv)
         if (n >= 0) h.n = (unsigned)bdpt_get_scene(h.ctx, h.spheres, (unsigned)(n > 0 ? n : 0));
         fprintf(stderr, "Resumed at pass %d\n", h.current_sample);
     }
-    for (int done = 0; done < spp; done += batch)
-        update_rendering(&h, spp - done < batch ? spp - done : batch);
-    for (const char *k = keys; *k; k++) {
-        key(&h, (unsigned char)*k);
+    int until_failed = 0;
+    if (until) {
+        if (render_until(&h, &nz, max_spp, batch) < 0) until_failed = 1;
+    } else {
         for (int done = 0; done < spp; done += batch)
             update_rendering(&h, spp - done < batch ? spp - done : batch);
+    }
+    for (const char *k = keys; *k; k++) {
+        key(&h, (unsigned char)*k);
+        if (until) {
+            if (render_until(&h, &nz, max_spp, batch) < 0) until_failed = 1;
+        } else {
+            for (int done = 0; done < spp; done += batch)
+                update_rendering(&h, spp - done < batch ? spp - done : batch);
+        }
     }
     if (out && denoise && h.reuse_history) {
         bdpt_preview_params pv = {h.rp, dn.levels, dn.normal_power, dn.sigma_color, count_ref};
@@ -176,5 +203,5 @@ int main(int argc, char **argv)
     }
     bdpt_destroy(h.ctx);
     if (npos == 3) bdpt_free_scene(h.spheres); else free(h.spheres);
-    return rc == BDPT_OK ? 0 : 1;
+    return rc == BDPT_OK && !until_failed ? 0 : 1;
 }

@@ -148,6 +148,29 @@ __attribute__((unused)) static int save_denoised_preview_ppm(host *h, const char
     return rc;
 }
 
+/* --until E: passes in batches until the noise estimate says the frame is good enough
+ * (bdpt_noise_estimate with remark after every batch: some pixel valid, none pending, no tile over
+ * the threshold) or max_spp passes are rendered; one report line on stderr.  Returns 1 when
+ * converged, 0 when not, -1 on an error. */
+__attribute__((unused)) static int render_until(host *h, const bdpt_noise_params *np, int max_spp, int batch)
+{
+    bdpt_noise_summary s;
+    int converged = 0;
+    memset(&s, 0, sizeof s);
+    const int first = h->current_sample;
+    do {
+        update_rendering(h, batch);
+        const int rc = bdpt_noise_estimate(h->ctx, np, NULL, NULL, NULL, &s);
+        report(h, rc, "Noise estimate");
+        if (rc != BDPT_OK) return -1;
+        converged = s.valid_pixels > 0 && s.pending_pixels == 0 && s.tiles_over == 0;
+    } while (!converged && h->current_sample < max_spp);
+    fprintf(stderr, "Until %g: %d passes (%d in this render), %s, worst tile %.9g, mean %.17g\n", (double)np->threshold,
+            h->current_sample, h->current_sample - first, converged ? "converged" : "not converged",
+            (double)s.max_tile, s.mean);
+    return converged;
+}
+
 /* what a checkpoint carries besides the frame: the pass schedule and the host counters */
 typedef struct {
     bdpt_pass_state ps;

@@ -443,6 +443,66 @@ int  bdpt_preview_denoise(bdpt_ctx *ctx, const bdpt_preview_params *params, bdpt
                           float *weight_out, unsigned char *rgba_out);
 int  bdpt_last_preview_ms(bdpt_ctx *ctx, float *ms);
 
+/* ---- per-tile noise estimate from two frames (no reference counterpart) ----
+ * How noisy the frame is, so that a caller can stop when it is good enough.  The path kernel keeps
+ * no sum of squares; the estimate is the half-buffer one: a context-owned mark holds the frame as
+ * it stood some passes ago, and how far the running mean has moved since, scaled by the two sample
+ * counts, estimates the error of the present mean.  fp32, no contraction, in the order written;
+ * a / b is the correctly rounded IEEE division and sqrtf the correctly rounded root; denormals are
+ * kept; non-finite radiance is not special.  The GPU, the CPU backend and the tests' numpy statement
+ * form the same bits.
+ *   mark      per pixel a colour mc[p] and a count mn[p] (unsigned; 0: no mark), one 16-byte record,
+ *             allocated on first use.  bdpt_noise_mark sets mc = colors, mn = counter for every
+ *             pixel, as they stand after whatever is queued; bdpt_noise_clear sets every mn to 0.
+ *             Every call that rewrites the accumulation other than path passes clears the mark too:
+ *             bdpt_reset_accum, bdpt_set_scene, bdpt_set_camera, bdpt_write_radiance (and with it
+ *             bdpt_load_checkpoint).  Clearing is a flag; it costs nothing while no mark was ever
+ *             stored.  The mark is not part of a checkpoint.
+ *   pixel p   A = mc[p], B = colors[p], mn = mn[p], cnt = counter[p].  Valid iff mn > 0, cnt > mn and
+ *             2*(cnt - mn) >= mn as integers (the fresh samples are at least half the marked ones).
+ *               a = (float)mn;  n = (float)cnt;  d = B - A
+ *               e1 = (|d.x| + |d.y|) + |d.z|;  s = a / (n - a);  f = sqrtf(s)
+ *               lum = (B.x + B.y) + B.z;  den = sqrtf(fmaxf(lum, dark));  e = (e1 * f) / den
+ *             (Dammertz et al.'s per-pixel term; sqrt(a/(n-a)) scales |B-A| to the standard error of
+ *             B, and is 1 for n = 2a.)  An invalid pixel contributes +0 to sums and reads -1.0f in
+ *             the per-pixel plane.
+ *   re-mark   (remark != 0) after its estimate is formed from the old mark, a pixel with
+ *             0 < cnt < 30000 and cnt >= 2*mn (mn == 0 included) takes the mark: mc = B, mn = cnt.
+ *   tile      BDPT_NOISE_TW x BDPT_NOISE_TH (the path kernel's workgroup tile) anchored at (0, 0);
+ *             tiles_x = ceil(W/32), tiles_y = ceil(H/8).  Slot k = (y % 8)*32 + (x % 32); slots
+ *             outside the frame are invalid.  v[k] = e or +0; eight rounds of v = v[0::2] + v[1::2]
+ *             (adjacent pairs) leave S_t; c_t = the number of valid slots;
+ *             E_t = c_t ? S_t / (float)c_t : +0.
+ *   summary   on the host, from the tile arrays in row-major order: valid_pixels = sum c_t;
+ *             valid_tiles = tiles with c_t > 0; mean = (sum (double)S_t) / valid_pixels (a double; 0
+ *             when there is none); max_tile: m = 0, if (E_t > m) m = E_t; tiles_over = tiles with
+ *             E_t > threshold; pending_pixels = pixels with 0 < cnt < 30000 that are not valid.
+ * bdpt_noise_estimate: error_out W*H (or NULL), tile_error and tile_valid tiles_x*tiles_y each (or
+ * NULL), summary (or NULL); not all four NULL.  An estimate without any mark is valid: it reports
+ * no valid pixel, and with remark it takes the first mark.  bdpt_noise_read_mark /
+ * bdpt_noise_write_mark: the mark's colours and counts (either may be NULL on read), for tests and
+ * resuming.  bdpt_last_noise_ms: device time of the last estimate's kernel alone (HIP events; wall
+ * time on the CPU backend).  All calls are synchronous, ordered after whatever the context has
+ * queued, and write nothing but the mark and their own buffers: accumulation, counters, pixels,
+ * tables, VLPs, path timing, the auto stream mode's measurements, shards and the reprojection
+ * history are untouched.
+ * BDPT_EINVAL: NULL parameters, dark not > 0 (NaN rejected), threshold negative or NaN, all outputs
+ * NULL, a multi-device context.  BDPT_ESTATE: bdpt_noise_read_mark while no mark was ever stored;
+ * bdpt_last_noise_ms before the first estimate.  Defaults: dark 0.01, threshold 0.05, remark 0. */
+#define BDPT_NOISE_TW 32
+#define BDPT_NOISE_TH 8
+typedef struct { float dark; float threshold; int remark; } bdpt_noise_params;
+typedef struct { long long valid_pixels, pending_pixels; int tiles_x, tiles_y, valid_tiles, tiles_over;
+                 double mean; float max_tile; } bdpt_noise_summary;
+int  bdpt_noise_mark(bdpt_ctx *ctx);
+int  bdpt_noise_clear(bdpt_ctx *ctx);
+int  bdpt_noise_tiles(const bdpt_ctx *ctx, int *tiles_x, int *tiles_y);
+int  bdpt_noise_read_mark(bdpt_ctx *ctx, bdpt_vec *colors, unsigned *counter);
+int  bdpt_noise_write_mark(bdpt_ctx *ctx, const bdpt_vec *colors, const unsigned *counter);
+int  bdpt_noise_estimate(bdpt_ctx *ctx, const bdpt_noise_params *params, float *error_out,
+                         float *tile_error, unsigned *tile_valid, bdpt_noise_summary *summary);
+int  bdpt_last_noise_ms(bdpt_ctx *ctx, float *ms);
+
 /* ---- optional display: HIP-GL interop ----
  * The caller owns the window, its OpenGL context (current on the calling thread) and a
  * pixel-unpack buffer of at least 4*W*H bytes (glGenBuffers + glBufferData(GL_PIXEL_UNPACK_BUFFER,
