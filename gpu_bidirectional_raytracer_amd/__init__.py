@@ -274,6 +274,13 @@ class Renderer:
         bits = int(lib.bdpt_last_kernel_features(self._h))
         return [name for bit, name in sorted(FEATURES.items()) if bits & bit]
 
+    def path_lds(self) -> dict:
+        """{static, dynamic, limit} in bytes: the LDS of the last path_passes call's largest launch
+        (refused or not) and what the device allows a workgroup (bdpt_path_lds)."""
+        st, dy, lim = ctypes.c_uint(), ctypes.c_uint(), ctypes.c_uint()
+        self._chk(lib.bdpt_path_lds(self._h, ctypes.byref(st), ctypes.byref(dy), ctypes.byref(lim)))
+        return {"static": st.value, "dynamic": dy.value, "limit": lim.value}
+
     @property
     def num_devices(self) -> int:
         return int(lib.bdpt_num_devices(self._h))

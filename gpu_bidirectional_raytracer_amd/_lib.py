@@ -135,6 +135,7 @@ _SIGS = [
     ("bdpt_scene_has_bvh", ctypes.c_int, [_P]),
     ("bdpt_last_traversal", ctypes.c_int, [_P]),
     ("bdpt_last_kernel_features", ctypes.c_int, [_P]),
+    ("bdpt_path_lds", ctypes.c_int, [_P] + [ctypes.POINTER(ctypes.c_uint)] * 3),
     ("bdpt_zero_exit_safe", ctypes.c_int, [ctypes.POINTER(Sphere), ctypes.c_uint]),
     ("bdpt_light_pass", ctypes.c_int, [_P, ctypes.c_int]),
     ("bdpt_generate_rand", ctypes.c_int, [_P, ctypes.c_uint]),

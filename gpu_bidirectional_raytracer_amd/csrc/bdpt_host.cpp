@@ -125,6 +125,12 @@ struct bdpt_ctx {
     int last_streams = 1;               // S of the last path-pass launch
     bool last_bvh = false;              // the last path-pass launch traversed the BVH
     int cus = 256;                      // compute units (auto stream count)
+    // LDS per workgroup the device allows (hipDeviceAttributeMaxSharedMemoryPerBlock), the static
+    // LDS of the path kernels looked at so far (by function), and the figures of the last
+    // bdpt_path_passes call's largest launch, refused or not (bdpt_path_lds)
+    size_t lds_limit = 0;
+    std::vector<std::pair<const void*, size_t>> lds_static;
+    size_t last_lds_static = 0, last_lds_dynamic = 0;
     bdpt_dev_vec* d_rbuf = nullptr;     // pass-stream radiance, 2 halves of rbuf_cap: [npass][nloc]
     unsigned* d_rmask = nullptr;        // pixel pools: 4 words per launched pixel (stored passes), 2 halves
     unsigned* d_poolctr = nullptr;      // pixel pools: claimed pixels per pass and eighth, a line each,
@@ -901,6 +907,9 @@ int bdpt_create(bdpt_ctx** out, const bdpt_sphere* spheres, unsigned n, int W, i
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
             c->cus = cus;
+        int lds = 0;
+        CK(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+        c->lds_limit = (size_t)lds;
     }
     for (auto& s : c->ring) {
         CK(hipEventCreate(&s.ev0));
@@ -1346,6 +1355,52 @@ static void path_lds_table(const bdpt_path_args& a, bool bvh, size_t* tab, size_
     *ids = bvh ? a.big_n : 0;
 }
 
+// Static LDS of the function a launch runs (HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES: the camera basis,
+// the sincos table, the claim words), asked once per function.
+static int path_kernel_static_lds(bdpt_ctx* c, const bdpt_plan& plan, const bdpt_launch& L, const path_kernels& k,
+                                  size_t* stat) {
+    const hipFunction_t jf = k.jf[L.kernel];
+    const void* key = jf ? (const void*)jf : (const void*)bdpt_path_kernel_table[L.st * 18 + plan.kidx];
+    for (const auto& e : c->lds_static)
+        if (e.first == key) {
+            *stat = e.second;
+            return BDPT_OK;
+        }
+    if (jf) {
+        int v = 0;
+        HIPCHK(c, hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, jf));
+        *stat = (size_t)v;
+    } else {
+        hipFuncAttributes at;
+        HIPCHK(c, hipFuncGetAttributes(&at, key));
+        *stat = at.sharedSizeBytes;
+    }
+    c->lds_static.emplace_back(key, *stat);
+    return BDPT_OK;
+}
+
+// Every launch of the call must fit the device's LDS per workgroup, static part included
+// (bdpt_plan.h bdpt_path_lds_fits): checked for all of them before anything of the call is issued.
+static int check_path_lds(bdpt_ctx* c, const bdpt_plan& plan, const path_kernels& k, size_t tab, size_t ids,
+                          const bdpt_path_env& env, int npass, unsigned n) {
+    c->last_lds_static = c->last_lds_dynamic = 0;
+    int launches = 0;
+    for (int p0 = 0; launches < plan.launches; p0 += plan.chunk, launches++) {
+        const bdpt_launch L = bdpt_plan_launch(plan, p0, npass, k.jf[BDPT_KERNEL_POOL] != nullptr,
+                                               k.jf[BDPT_KERNEL_UNITS] != nullptr, k.jf[BDPT_KERNEL_STREAMS] != nullptr,
+                                               k.jf[BDPT_KERNEL_FUSED] != nullptr, k.use_srec, c->jit_zero_exit, tab, ids, env);
+        size_t stat = 0;
+        if (int rc = path_kernel_static_lds(c, plan, L, k, &stat)) return rc;
+        if (L.smem + stat > c->last_lds_static + c->last_lds_dynamic) {
+            c->last_lds_static = stat;
+            c->last_lds_dynamic = L.smem;
+        }
+    }
+    if (!bdpt_path_lds_fits(c->last_lds_dynamic, c->last_lds_static, c->lds_limit))
+        return fail(c, BDPT_EINVAL, "bdpt_path_passes: scene too large for LDS (%u spheres)", n);
+    return BDPT_OK;
+}
+
 // A call between begin_call and end_call.
 struct path_call {
     bdpt_ctx::call_slot* cs = nullptr;
@@ -1494,8 +1549,6 @@ static int launch_path_kernel(bdpt_ctx* c, const bdpt_plan& plan, const bdpt_lau
     }
     a.streams = L.streams;
     if (L.unitsl) a.unit_passes = L.unit_passes;
-    if (L.smem > 160 * 1024)
-        return fail(c, BDPT_EINVAL, "bdpt_path_passes: scene too large for LDS (%u spheres)", a.n);
     const hipFunction_t jf = k.jf[L.kernel];
     c->last_specialized = jf != nullptr;
     c->last_features = L.features;
@@ -1598,6 +1651,7 @@ static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int
     if (int rc = resolve_path_kernels(c, plan, npass, a, k)) return rc;
     size_t tab = 0, ids = 0;
     path_lds_table(a, plan.bvh, &tab, &ids);
+    if (int rc = check_path_lds(c, plan, k, tab, ids, env, npass, a.n)) return rc;
 
     if (int rc = begin_call(c, plan, env, k, call)) return rc;
     for (int p0 = 0; call.launches < plan.launches; p0 += plan.chunk) {
@@ -1776,6 +1830,14 @@ int bdpt_frame_size(const bdpt_ctx* c, int* W, int* H) {
 }
 
 int bdpt_last_kernel_features(const bdpt_ctx* c) { return c ? c->last_features : BDPT_EINVAL; }
+
+int bdpt_path_lds(const bdpt_ctx* c, unsigned* static_bytes, unsigned* dynamic_bytes, unsigned* limit_bytes) {
+    if (!c) return BDPT_EINVAL;
+    if (static_bytes) *static_bytes = (unsigned)c->last_lds_static;
+    if (dynamic_bytes) *dynamic_bytes = (unsigned)c->last_lds_dynamic;
+    if (limit_bytes) *limit_bytes = (unsigned)c->lds_limit;
+    return BDPT_OK;
+}
 
 static int one_device_buffers(bdpt_ctx* c, void** colors, void** counter, void** pixels) {
     if (!c) return BDPT_EINVAL;

@@ -283,6 +283,18 @@ inline size_t bdpt_path_smem(size_t tab, size_t slots, size_t ids, int pad) {
 inline size_t bdpt_path_tab(bool bvh, size_t n, size_t n_vac, size_t big_n) {
     return bvh ? big_n : 4 * n + n_vac;
 }
+// A workgroup's LDS is the launch's dynamic part (bdpt_path_smem) plus what the kernel declares
+// itself (`stat`: the camera basis, the sincos table, the claim words; the launched function's
+// HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES): the launch fits when the sum is within the device's
+// limit per workgroup.  A launch that does not fit fails in the runtime, so the host refuses it.
+inline bool bdpt_path_lds_fits(size_t dyn, size_t stat, size_t limit) { return dyn + stat <= limit; }
+// The largest scene the brute-force kernels take: n spheres of which n_emit emit (the non-emitters'
+// list has n - n_emit entries), `slots` staged passes; 0 when not even an empty table fits.
+inline size_t bdpt_path_max_spheres(size_t n_emit, size_t slots, int pad, size_t stat, size_t limit) {
+    const size_t fixed = bdpt_path_smem(0, slots, 0, pad) + stat;
+    if (fixed > limit) return 0;
+    return ((limit - fixed) / 16 + n_emit) / 5;          // 16 B x (4 n + n - n_emit) <= limit - fixed
+}
 
 // Which kernel a launch runs: the precompiled instance or one of the specialised builds.
 enum bdpt_launch_kernel {

@@ -184,6 +184,13 @@ int  bdpt_last_traversal(const bdpt_ctx *ctx);
                                                units of (tile, range of passes) in range order,
                                                running mean in registers, no radiance buffer   */
 int  bdpt_last_kernel_features(const bdpt_ctx *ctx);
+/* LDS of the last bdpt_path_passes call's largest launch, in bytes, whether it ran or was refused:
+ * what the launched kernel declares itself (static), what the launch adds for the scene tables and
+ * the staged passes (dynamic), and what the device allows a workgroup (limit).  A call whose
+ * static + dynamic exceeds the limit fails with BDPT_EINVAL before anything is launched; such a
+ * scene still renders with BDPT_TRAVERSE_BVH when it has a tree.  Zeros before the first call and
+ * on the CPU backend.  Any pointer may be NULL. */
+int  bdpt_path_lds(const bdpt_ctx *ctx, unsigned *static_bytes, unsigned *dynamic_bytes, unsigned *limit_bytes);
 /* The black-surface exit rule (BDPT_FEAT_ZERO_EXIT): 1 if ending a path at a black non-emitter is
  * provably exact for this scene -- every term the reference adds after the black hit is finite,
  * so 0 * term = +0 leaves the radiance bit-identical -- else 0.  Pure host function: the

@@ -240,6 +240,23 @@ static void lds() {
     const bdpt_plan p = bdpt_plan_call(frame(97, 65, 0, 20), chosen(D), env);
     const bdpt_launch l = bdpt_plan_launch(p, 0, 20, false, false, true, false, true, true, 44, 0, env);
     CHECK(l.streams == 10 && l.slots == 2 && l.smem == 16 * (44 + 6 + 5 + 1024) + 4 * 2);
+    // static LDS counts: 17688 dynamic + 6152 static fit 23840 exactly and no less
+    CHECK(bdpt_path_lds_fits(17688, 6152, 23840) && !bdpt_path_lds_fits(17688, 6152, 23839));
+    CHECK(bdpt_path_lds_fits(160 * 1024, 0, 160 * 1024) && !bdpt_path_lds_fits(160 * 1024, 8, 160 * 1024));
+    // the largest brute-force scene: one emitter, 2 staged passes, 160 KiB, by hand:
+    // 163840 - 6152 static - 16 * (6 + 5 + 1024) - 8 = 141120 = 16 * 8820; 5 n - 1 <= 8820 -> n = 1764
+    CHECK(bdpt_path_max_spheres(1, 2, 0, 6152, 160 * 1024) == 1764);
+    for (size_t stat : {(size_t)0, (size_t)2056, (size_t)6152, (size_t)8200})
+        for (size_t slots : {(size_t)1, (size_t)2, (size_t)128})
+            for (size_t ne : {(size_t)0, (size_t)1, (size_t)3}) {
+                const size_t lim = 160 * 1024, n = bdpt_path_max_spheres(ne, slots, 0, stat, lim);
+                CHECK(n > 1500 && n < 1900);
+                CHECK(bdpt_path_lds_fits(bdpt_path_smem(bdpt_path_tab(false, n, n - ne, 0), slots, 0, 0), stat, lim));
+                CHECK(!bdpt_path_lds_fits(bdpt_path_smem(bdpt_path_tab(false, n + 1, n + 1 - ne, 0), slots, 0, 0), stat, lim));
+            }
+    CHECK(bdpt_path_max_spheres(0, 1, 0, 160 * 1024, 160 * 1024) == 0);      // nothing fits
+    // the BVH kernel stages the brute-force list and its ids: 16 + 4 bytes per entry
+    CHECK(bdpt_path_smem(bdpt_path_tab(true, 5000, 4990, 40), 1, 40, 0) == 16 * (40 + 3 + 5 + 1024) + 4 * 41);
 }
 
 int main() {
