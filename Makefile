@@ -20,7 +20,7 @@ LIB      ?= $(PKG)/libbdpt.so
 HOST     := $(PKG)/smallpt
 ORACLE   := oracle/liboracle.so
 
-CHECKS   := tests/native/hw_exact_check
+CHECKS   := tests/native/hw_exact_check tests/native/leaf_check tests/native/leaf_check_coarse
 
 all: $(LIB) $(HOST) $(ORACLE) $(CHECKS)
 
@@ -28,14 +28,23 @@ all: $(LIB) $(HOST) $(ORACLE) $(CHECKS)
 tests/native/hw_exact_check: tests/native/hw_exact_check.hip $(CSRC)/bdpt_math.h
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -ffp-contract=off -o $@ $<
 
+# the leaf device functions against plain statements, run by tests/test_gpu_leaf.py; the second
+# binary checks bdpt_sincos_tab with the 256-entry table
+LEAF_DEPS := tests/native/leaf_check.hip $(CSRC)/bdpt_leaf.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_device.h
+tests/native/leaf_check: $(LEAF_DEPS)
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -ffp-contract=off -pthread -o $@ $<
+
+tests/native/leaf_check_coarse: $(LEAF_DEPS)
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -ffp-contract=off -pthread -DBDPT_SC_COARSE=1 -o $@ $<
+
 $(BUILD):
 	mkdir -p $(BUILD)
 
-$(BUILD)/bdpt_kernels.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h | $(BUILD)
+$(BUILD)/bdpt_kernels.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the path kernel's sources as strings, for scene-specialised kernels compiled at run time
-$(CSRC)/bdpt_jit_src.h: tools/embed_jit_sources.py $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h
+$(CSRC)/bdpt_jit_src.h: tools/embed_jit_sources.py $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h
 	python3 tools/embed_jit_sources.py $@
 
 $(BUILD)/bdpt_host.o: $(CSRC)/bdpt_host.cpp $(CSRC)/bdpt_device.h $(CSRC)/bdpt_plan.h $(CSRC)/bdpt_bvh.h $(CSRC)/bdpt_cpu.h $(CSRC)/bdpt_jit_src.h include/bdpt.h | $(BUILD)

@@ -471,6 +471,9 @@ uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
 }
 
 std::string hexf(float v) {                     // exact float literal
+    // %a prints "inf" / "nan", which are no literals: rad * rad overflows from rad = 1.85e19 on
+    if (std::isinf(v)) return v < 0.f ? "(-__builtin_inff())" : "__builtin_inff()";
+    if (v != v) return "__builtin_nanf(\"\")";
     char b[48];
     snprintf(b, sizeof b, "%af", (double)v);
     return b;
@@ -1283,9 +1286,11 @@ static int settle_stream_mode(bdpt_ctx* c) {
 }
 
 // The pass-stream radiance buffer and the pools' mask (two halves each), grown to the plan's
-// largest launch; the in-kernel fold needs neither.
-static int ensure_radiance_buffers(bdpt_ctx* c, const bdpt_plan& plan, int npass) {
-    if (plan.S <= 1 || plan.want_units) return BDPT_OK;
+// largest launch; the in-kernel fold needs neither.  `units`: the units build resolved -- a plan
+// that wants units without it (specialisation off, or a build that failed) launches the plain
+// pass-stream kernel, which writes the buffer.
+static int ensure_radiance_buffers(bdpt_ctx* c, const bdpt_plan& plan, int npass, bool units) {
+    if (plan.S <= 1 || units) return BDPT_OK;
     const size_t lanes = (size_t)plan.lanes;
     const size_t need = (size_t)(npass < plan.chunk ? npass : plan.chunk) * lanes;
     if (need <= c->rbuf_cap && lanes <= c->rmask_lanes) return BDPT_OK;
@@ -1641,7 +1646,6 @@ static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int
     c->last_bvh = plan.bvh;
     path_args_plan(c, plan, a);
 
-    if (int rc = ensure_radiance_buffers(c, plan, npass)) return rc;
     while (call.cs->kev.size() < 2 * (size_t)plan.launches) {   // per launch {before, after}
         hipEvent_t e;
         HIPCHK(c, hipEventCreate(&e));
@@ -1649,6 +1653,7 @@ static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int
     }
     path_kernels k;
     if (int rc = resolve_path_kernels(c, plan, npass, a, k)) return rc;
+    if (int rc = ensure_radiance_buffers(c, plan, npass, k.jf[BDPT_KERNEL_UNITS] != nullptr)) return rc;
     size_t tab = 0, ids = 0;
     path_lds_table(a, plan.bvh, &tab, &ids);
     if (int rc = check_path_lds(c, plan, k, tab, ids, env, npass, a.n)) return rc;

@@ -24,6 +24,9 @@ LIGHTPATH_DTYPE = np.dtype([("hp", "<f4", 3), ("rad", "<f4", 3), ("nl", "<f4", 3
 CAMERA_DTYPE = np.dtype([("orig", "<f4", 3), ("target", "<f4", 3), ("dir", "<f4", 3),
                          ("x", "<f4", 3), ("y", "<f4", 3)])
 STAT_NAMES = ("samples", "segments", "closest", "shadow", "sphere_tests", "diffuse", "rng_reads", "refr")
+# the range counters (oracle/bdpt_oracle.c RG_*): events per site, returned only when asked for
+RANGE_NAMES = ("norm_camera", "norm_normal", "norm_refr", "norm_nee", "norm_vlp", "norm_tangent", "norm_light",
+               "nee_in", "nee_out", "cam_w_out", "det_tiny", "det_neg_denormal", "second_root")
 
 
 def _load():
@@ -42,6 +45,10 @@ def _load():
     lib.oracle_path_span.argtypes = [P, ctypes.c_uint, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_long,
                                      ctypes.c_long, P, P, P, ctypes.c_int, P, P, P, ctypes.c_int, P]
     lib.oracle_path_span.restype = None
+    lib.oracle_path_span_range.argtypes = lib.oracle_path_span.argtypes + [P]
+    lib.oracle_path_span_range.restype = None
+    lib.oracle_light_pass_range.argtypes = lib.oracle_light_pass.argtypes + [P]
+    lib.oracle_light_pass_range.restype = None
     lib.oracle_update_camera.argtypes = [P, ctypes.c_int, ctypes.c_int]
     lib.oracle_update_camera.restype = None
     lib.oracle_key_camera.argtypes = [P, ctypes.c_int]
@@ -90,9 +97,14 @@ def fnv1_64(a) -> int:
 
 
 def light_pass(spheres: np.ndarray, rnd: np.ndarray, current_sample: int = 0,
-               lp: np.ndarray | None = None) -> np.ndarray:
+               lp: np.ndarray | None = None, ranges: bool = False):
+    """The light paths; with ranges=True (lp, range counters of the pass as a dict)."""
     sp = np.ascontiguousarray(spheres.astype(SPHERE_DTYPE, copy=False))
     lp = np.zeros(LIGHT_POINTS, LIGHTPATH_DTYPE) if lp is None else lp.copy()
+    if ranges:
+        rg = np.zeros(len(RANGE_NAMES), np.uint64)
+        lib.oracle_light_pass_range(_p(sp), len(sp), _p(rnd), current_sample, _p(lp), _p(rg))
+        return lp, dict(zip(RANGE_NAMES, (int(v) for v in rg)))
     lib.oracle_light_pass(_p(sp), len(sp), _p(rnd), current_sample, _p(lp))
     return lp
 
@@ -131,9 +143,10 @@ def special_key(cam: np.ndarray, key: str) -> bool:
 
 
 def path_passes(spheres, rnd, cam, width, height, lp, sid, vlp, colors=None, counter=None,
-                pixels=None, rows=None, nthreads: int = 0, stats: bool = False, span=None):
+                pixels=None, rows=None, nthreads: int = 0, stats: bool = False, span=None,
+                ranges: bool = False):
     """npass x RadiancePathTracingKernel over rows [y0, y1) (or the row-major pixel range
-    span = (p0, p1)) -> (colors, counter, pixels[, stats])."""
+    span = (p0, p1)) -> (colors, counter, pixels[, stats][, range counters])."""
     sp = np.ascontiguousarray(spheres.astype(SPHERE_DTYPE, copy=False))
     cam = camera_array(cam)
     sid = np.ascontiguousarray(sid, np.uint32)
@@ -144,12 +157,21 @@ def path_passes(spheres, rnd, cam, width, height, lp, sid, vlp, colors=None, cou
     y0, y1 = (0, height) if rows is None else rows
     st = np.zeros(8, np.uint64)
     p0, p1 = (y0 * width, y1 * width) if span is None else span
-    lib.oracle_path_span(_p(sp), len(sp), _p(rnd), _p(cam), width, height, p0, p1, _p(lp),
-                         _p(sid), _p(vlp), len(sid), _p(colors), _p(counter), _p(pixels),
-                         nthreads, _p(st) if stats else None)
+    if ranges:
+        rg = np.zeros(len(RANGE_NAMES), np.uint64)
+        lib.oracle_path_span_range(_p(sp), len(sp), _p(rnd), _p(cam), width, height, p0, p1, _p(lp),
+                                   _p(sid), _p(vlp), len(sid), _p(colors), _p(counter), _p(pixels),
+                                   nthreads, _p(st) if stats else None, _p(rg))
+    else:
+        lib.oracle_path_span(_p(sp), len(sp), _p(rnd), _p(cam), width, height, p0, p1, _p(lp),
+                             _p(sid), _p(vlp), len(sid), _p(colors), _p(counter), _p(pixels),
+                             nthreads, _p(st) if stats else None)
+    out = (colors, counter, pixels)
     if stats:
-        return colors, counter, pixels, dict(zip(STAT_NAMES, (int(v) for v in st)))
-    return colors, counter, pixels
+        out += (dict(zip(STAT_NAMES, (int(v) for v in st))),)
+    if ranges:
+        out += (dict(zip(RANGE_NAMES, (int(v) for v in rg))),)
+    return out
 
 
 def to_int(x: float) -> int:

@@ -113,7 +113,38 @@ static inline float sphere_intersect(const Sphere *s, const Ray *r)
     return t > EPSILON ? t : 0.f;
 }
 
-typedef struct { uint64_t segments, closest, shadow, sphere_tests, samples, diffuse, rng_reads, refr; } ostats;
+typedef struct { uint64_t segments, closest, shadow, sphere_tests, samples, diffuse, rng_reads, refr;
+                 uint64_t *rg; /* range counters (below), or NULL */ } ostats;
+
+/* Range counters: an optional second statistics block (oracle.RANGE_NAMES, same order), counted per
+ * site only when a caller asks (st->rg).  They let a test scene prove that it reaches the inputs on
+ * which the HIP kernels leave their fast paths: a squared length outside [2^-96, 2^126) passed to a
+ * normalisation (csrc/bdpt_kernels.hip rcp_sqrt_rn), an NEE term s = a / b with a or b outside
+ * [2^-60, 2^60] (counted where the kernel divides: at wi > 0, before the shadow ray), the camera's w
+ * outside [2^-125, 2^125) (rcp_rn), sphere tests whose det is in (0, 2^-96) or a negative denormal,
+ * and sphere tests answered by the second root.  Counting recomputes from the same operands and
+ * never feeds a value back: no float of the render changes. */
+enum { RG_NORM_CAMERA, RG_NORM_NORMAL, RG_NORM_REFR, RG_NORM_NEE, RG_NORM_VLP, RG_NORM_TANGENT,
+       RG_NORM_LIGHT, RG_NEE_IN, RG_NEE_OUT, RG_CAM_W_OUT, RG_DET_TINY, RG_DET_NEG_DENORMAL,
+       RG_SECOND_ROOT, RG_N };
+
+static inline void rg_norm(const ostats *st, int site, float d2)
+{
+    if (st && st->rg && !(d2 >= 0x1p-96f && d2 < 0x1p126f)) st->rg[site]++;
+}
+
+static inline void rg_sphere(const ostats *st, const Sphere *s, const Ray *r)
+{
+    if (!st || !st->rg) return;
+    Vec op = vsub(s->p, r->o);
+    float b = vdot(op, r->d);
+    float det = b * b - vdot(op, op) + s->rad * s->rad;
+    if (det > 0.f && det < 0x1p-96f) st->rg[RG_DET_TINY]++;
+    if (det < 0.f && det > -0x1p-126f) st->rg[RG_DET_NEG_DENORMAL]++;
+    if (det < 0.f) return;
+    det = sqrtf(det);
+    if (!(b - det > EPSILON) && b + det > EPSILON) st->rg[RG_SECOND_ROOT]++;
+}
 
 static inline int intersect(const Sphere *sp, unsigned n, const Ray *r, float *t, unsigned *id,
                             ostats *st)
@@ -122,6 +153,7 @@ static inline int intersect(const Sphere *sp, unsigned n, const Ray *r, float *t
     if (st) { st->closest++; st->sphere_tests += n; }
     for (unsigned i = n; i--;) {
         const float d = sphere_intersect(&sp[i], r);
+        rg_sphere(st, &sp[i], r);
         if (d != 0.f && d < *t) { *t = d; *id = i; }
     }
     return *t < inf;
@@ -131,7 +163,7 @@ static inline int intersect_p(const Sphere *sp, unsigned n, const Ray *r, float 
 {
     if (st) st->shadow++;
     for (unsigned i = n; i--;) {
-        if (st) st->sphere_tests++;
+        if (st) { st->sphere_tests++; rg_sphere(st, &sp[i], r); }
         const float d = sphere_intersect(&sp[i], r);
         if (d != 0.f && d < maxt) return 1;
     }
@@ -143,7 +175,7 @@ static inline int intersect_p_vacuum(const Sphere *sp, unsigned n, const Ray *r,
 {
     if (st) st->shadow++;
     for (unsigned i = n; i--;) {
-        if (st) st->sphere_tests++;
+        if (st) { st->sphere_tests++; rg_sphere(st, &sp[i], r); }
         const float d = sphere_intersect(&sp[i], r);
         if (d != 0.f && d < maxt && viszero(sp[i].e)) return 1;
     }
@@ -161,13 +193,15 @@ static inline Vec uniform_sample_sphere(float u1, float u2)
 }
 
 /* Cosine-weighted hemisphere direction about w (device.cu:190-212, 357-380, 676-699). */
-static inline Vec cosine_dir(Vec w, float u_phi, float u_r2)
+static inline Vec cosine_dir(Vec w, float u_phi, float u_r2, const ostats *st, int site)
 {
     float r1 = 2.f * FLOAT_PI * u_phi;
     float r2 = u_r2;
     float r2s = sqrtf(r2);
     Vec a = fabsf(w.x) > .1f ? vinit(0.f, 1.f, 0.f) : vinit(1.f, 0.f, 0.f);
-    Vec u = vnorm(vxcross(a, w));
+    Vec u = vxcross(a, w);
+    rg_norm(st, site, vdot(u, u));
+    u = vnorm(u);
     Vec v = vxcross(w, u);
     u = vsmul(o_cosf(r1) * r2s, u);
     v = vsmul(o_sinf(r1) * r2s, v);
@@ -191,28 +225,43 @@ static inline void vec_multiply(Vec *io, Vec m)
  * `rnd` must already hold the MT table for seed current_sample*5 (the kernel is re-run per
  * light with the same seed, so one table serves all lights).  lp[] must be pre-initialised
  * (zeros: survey Appendix A.4); entries a light does not write keep their previous value. */
+void oracle_light_pass_range(const Sphere *sp, unsigned n, const float *rnd, int current_sample,
+                             LightPath *lp, uint64_t *range_out /* RG_N, or NULL */);
+
 void oracle_light_pass(const Sphere *sp, unsigned n, const float *rnd, int current_sample,
                        LightPath *lp)
 {
+    oracle_light_pass_range(sp, n, rnd, current_sample, lp, NULL);
+}
+
+/* The same, with the range counters of the pass (every normalisation counts as RG_NORM_LIGHT). */
+void oracle_light_pass_range(const Sphere *sp, unsigned n, const float *rnd, int current_sample,
+                             LightPath *lp, uint64_t *range_out)
+{
+    uint64_t rg[RG_N] = {0};
+    ostats sto = {0, 0, 0, 0, 0, 0, 0, 0, rg};
+    ostats *st = range_out ? &sto : NULL;
     for (unsigned li = 0; li < n; li++) {
         const Sphere light = sp[li];
         if (viszero(light.e)) continue;
-#pragma omp parallel for schedule(static)
+#pragma omp parallel for schedule(static) if (!range_out)
         for (int ind = 0; ind < BDPT_LIGHT_POINTS; ind++) {
             /* GetRayKernel, seed_id = 0 (smallpt_cpu.c:330) */
             unsigned i = (unsigned)(current_sample * 5 + ind * 4) % (RAND_N - 4u);
             unsigned j = i + 2;
             Vec usp = uniform_sample_sphere(rnd[j], rnd[i]);
             Vec spt = vadd(vsmul(light.rad, usp), light.p);
-            Vec normal = vnorm(vsub(spt, light.p));
+            Vec normal = vsub(spt, light.p);
+            rg_norm(st, RG_NORM_LIGHT, vdot(normal, normal));
+            normal = vnorm(normal);
             Ray ray;
             ray.o = spt;
-            ray.d = cosine_dir(normal, rnd[i + 1], rnd[j + 1]);
+            ray.d = cosine_dir(normal, rnd[i + 1], rnd[j + 1], st, RG_NORM_LIGHT);
 
             /* RadianceLightTracingKernel */
             Vec thr = vsmul(0.25f, light.e);                      /* :248,268 e * (1./4)    */
             float t; unsigned id = 0;
-            if (!intersect(sp, n, &ray, &t, &id, NULL)) {         /* escaped: :279-292      */
+            if (!intersect(sp, n, &ray, &t, &id, st)) {           /* escaped: :279-292      */
                 Vec nor = vsmul((float)(-1. / light.rad), vsub(ray.o, light.p));
                 lp[ind].hp = ray.o;
                 lp[ind].rad = vsmul(0.5f, light.e);
@@ -222,7 +271,9 @@ void oracle_light_pass(const Sphere *sp, unsigned n, const float *rnd, int curre
             const Sphere *obj = &sp[id];
             if (!viszero(obj->e)) continue;                       /* :296-298               */
             Vec hit = vadd(ray.o, vsmul(t, ray.d));
-            Vec nrm = vnorm(vsub(hit, obj->p));
+            Vec nrm = vsub(hit, obj->p);
+            rg_norm(st, RG_NORM_LIGHT, vdot(nrm, nrm));
+            nrm = vnorm(nrm);
             const float dp = vdot(nrm, ray.d);
             Vec nl = vsmul(-1.f * (dp > 0 ? 1 : -1), nrm);
             if (obj->refl == BDPT_DIFF) {                         /* :314-337               */
@@ -234,6 +285,7 @@ void oracle_light_pass(const Sphere *sp, unsigned n, const float *rnd, int curre
             /* SPEC / REFR: throughput changes but DEPTH=1 ends the loop with no store. */
         }
     }
+    if (range_out) memcpy(range_out, rg, sizeof rg);
 }
 
 /* ---------------------------------------------------------------------------------------- */
@@ -265,12 +317,17 @@ static Vec sample_lights(const Sphere *sp, unsigned n, const float *rnd, Vec hit
         Vec spt = vadd(vsmul(light->rad, usp), light->p);
         Ray sr; sr.o = hit;
         sr.d = vsub(spt, hit);
+        rg_norm(st, RG_NORM_NEE, vdot(sr.d, sr.d));
         const float len = sqrtf(vdot(sr.d, sr.d));
         sr.d = vsmul(1.f / len, sr.d);
         float wo = vdot(sr.d, usp);
         if (wo > 0.f) continue;
         wo = -wo;
         const float wi = vdot(sr.d, nl);
+        if (st && st->rg && wi > 0.f) {
+            const float na = (4.f * FLOAT_PI * light->rad * light->rad) * wi * wo, nb = len * len;
+            st->rg[na >= 0x1p-60f && na <= 0x1p60f && nb >= 0x1p-60f && nb <= 0x1p60f ? RG_NEE_IN : RG_NEE_OUT]++;
+        }
         if (wi > 0.f && !intersect_p(sp, n, &sr, len - EPSILON, st)) {
             const float s = (4.f * FLOAT_PI * light->rad * light->rad) * wi * wo / (len * len);
             result = vadd(result, vsmul(s, light->e));
@@ -281,6 +338,7 @@ static Vec sample_lights(const Sphere *sp, unsigned n, const float *rnd, Vec hit
         const LightPath *v = &lp[vlp];
         Ray sr; sr.o = hit;
         sr.d = vsub(v->hp, hit);
+        rg_norm(st, RG_NORM_VLP, vdot(sr.d, sr.d));
         const float len = sqrtf(vdot(sr.d, sr.d));
         sr.d = vsmul(1.f / len, sr.d);
         float wo = vdot(sr.d, v->nl);
@@ -322,9 +380,11 @@ static Vec path_sample(const Sphere *sp, unsigned n, const float *rnd, const Cam
     rdir = vadd(rdir, vsmul(ky, cp->uy));
     rdir = vadd(rdir, vsmul(kz, cp->ud));
     const float w = (cp->tx * kx + cp->ty * ky + cp->tz * kz) + 1;
+    if (st && st->rg && !(fabsf(w) >= 0x1p-125f && fabsf(w) < 0x1p125f)) st->rg[RG_CAM_W_OUT]++;
     rdir = vsmul((float)(1. / w), rdir);
     Ray cur;
     cur.o = vadd(rdir, cam->orig);
+    rg_norm(st, RG_NORM_CAMERA, vdot(rdir, rdir));
     cur.d = vnorm(rdir);
 
     Vec rad = vinit(0.f, 0.f, 0.f), thr = vinit(1.f, 1.f, 1.f);
@@ -338,7 +398,9 @@ static Vec path_sample(const Sphere *sp, unsigned n, const float *rnd, const Cam
         if (!intersect(sp, n, &cur, &t, &id, st)) break;
         const Sphere *obj = &sp[id];
         Vec hit = vadd(cur.o, vsmul(t, cur.d));
-        Vec normal = vnorm(vsub(hit, obj->p));
+        Vec normal = vsub(hit, obj->p);
+        rg_norm(st, RG_NORM_NORMAL, vdot(normal, normal));
+        normal = vnorm(normal);
         const float dp = vdot(normal, cur.d);
         Vec nl = vsmul(-1.f * (dp > 0 ? 1 : -1), normal);
         if (!viszero(obj->e)) {
@@ -352,7 +414,7 @@ static Vec path_sample(const Sphere *sp, unsigned n, const float *rnd, const Cam
             Vec ld = sample_lights(sp, n, rnd, hit, nl, j + 2, lp, vlp, st);
             rad = vadd(rad, vmul(ld, thr));
             cur.o = hit;
-            cur.d = cosine_dir(nl, rnd[j], rnd[j + 1]);
+            cur.d = cosine_dir(nl, rnd[j], rnd[j + 1], st, RG_NORM_TANGENT);
         } else if (obj->refl == BDPT_SPEC) {
             specular = 1;
             Vec nd = vsub(cur.d, vsmul(2.f * vdot(normal, cur.d), normal));
@@ -373,7 +435,9 @@ static Vec path_sample(const Sphere *sp, unsigned n, const float *rnd, const Cam
             }
             if (st) { st->refr++; st->rng_reads += 1; }
             const float kq = (float)(into ? 1 : -1) * (ddn * nnt + sqrtf(cos2t));
-            Vec td = vnorm(vsub(vsmul(nnt, cur.d), vsmul(kq, normal)));
+            Vec td = vsub(vsmul(nnt, cur.d), vsmul(kq, normal));
+            rg_norm(st, RG_NORM_REFR, vdot(td, td));
+            td = vnorm(td);
             const float a = nt - nc, b = nt + nc;
             const float R0 = a * a / (b * b);
             const float c = 1 - (into ? -ddn : vdot(td, normal));
@@ -403,6 +467,11 @@ void oracle_path_span(const Sphere *sp, unsigned n, const float *rnd, const Came
                       const unsigned *sid, const int *vlp, int npass,
                       Vec *colors, unsigned *counter, unsigned char *pixels,
                       int nthreads, uint64_t *stats_out);
+void oracle_path_span_range(const Sphere *sp, unsigned n, const float *rnd, const Camera *cam,
+                            int W, int H, long pix0, long pix1, const LightPath *lp,
+                            const unsigned *sid, const int *vlp, int npass,
+                            Vec *colors, unsigned *counter, unsigned char *pixels,
+                            int nthreads, uint64_t *stats_out, uint64_t *range_out);
 
 void oracle_path_passes(const Sphere *sp, unsigned n, const float *rnd, const Camera *cam,
                         int W, int H, int y0, int y1, const LightPath *lp,
@@ -423,8 +492,20 @@ void oracle_path_span(const Sphere *sp, unsigned n, const float *rnd, const Came
                       Vec *colors, unsigned *counter, unsigned char *pixels,
                       int nthreads, uint64_t *stats_out)
 {
+    oracle_path_span_range(sp, n, rnd, cam, W, H, pix0, pix1, lp, sid, vlp, npass, colors, counter,
+                           pixels, nthreads, stats_out, NULL);
+}
+
+/* The same, with the range counters (RG_N x uint64, see above) in `range_out` when non-NULL. */
+void oracle_path_span_range(const Sphere *sp, unsigned n, const float *rnd, const Camera *cam,
+                            int W, int H, long pix0, long pix1, const LightPath *lp,
+                            const unsigned *sid, const int *vlp, int npass,
+                            Vec *colors, unsigned *counter, unsigned char *pixels,
+                            int nthreads, uint64_t *stats_out, uint64_t *range_out)
+{
     const campre cp = camera_pre(cam);
-    ostats tot = {0, 0, 0, 0, 0, 0, 0, 0};
+    ostats tot = {0, 0, 0, 0, 0, 0, 0, 0, NULL};
+    uint64_t rtot[RG_N] = {0};
     if (pix0 < 0) pix0 = 0;
     if (pix1 > (long)W * H) pix1 = (long)W * H;
 #ifdef _OPENMP
@@ -434,8 +515,9 @@ void oracle_path_span(const Sphere *sp, unsigned n, const float *rnd, const Came
 #endif
 #pragma omp parallel
     {
-        ostats loc = {0, 0, 0, 0, 0, 0, 0, 0};
-        ostats *st = stats_out ? &loc : NULL;
+        uint64_t rloc[RG_N] = {0};
+        ostats loc = {0, 0, 0, 0, 0, 0, 0, 0, range_out ? rloc : NULL};
+        ostats *st = stats_out || range_out ? &loc : NULL;
 #pragma omp for schedule(dynamic, 16)
         for (long pix = pix0; pix < pix1; pix++) {
             const int x = (int)(pix % W), y = (int)(pix / W);
@@ -466,9 +548,10 @@ void oracle_path_span(const Sphere *sp, unsigned n, const float *rnd, const Came
                 pixels[4 * pix + 3] = 0;
             }
         }
-        if (stats_out) {
+        if (st) {
 #pragma omp critical
             {
+                for (int k = 0; k < RG_N; k++) rtot[k] += rloc[k];
                 tot.segments += loc.segments; tot.closest += loc.closest; tot.shadow += loc.shadow;
                 tot.sphere_tests += loc.sphere_tests; tot.samples += loc.samples;
                 tot.diffuse += loc.diffuse; tot.rng_reads += loc.rng_reads; tot.refr += loc.refr;
@@ -480,6 +563,7 @@ void oracle_path_span(const Sphere *sp, unsigned n, const float *rnd, const Came
         stats_out[3] = tot.shadow; stats_out[4] = tot.sphere_tests; stats_out[5] = tot.diffuse;
         stats_out[6] = tot.rng_reads; stats_out[7] = tot.refr;
     }
+    if (range_out) memcpy(range_out, rtot, sizeof rtot);
 }
 
 /* vnorm (vec.h:22) as it compiles in the reference's host C files (display_func.c is C, so
