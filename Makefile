@@ -40,14 +40,18 @@ tests/native/leaf_check_coarse: $(LEAF_DEPS)
 $(BUILD):
 	mkdir -p $(BUILD)
 
-$(BUILD)/bdpt_kernels.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h | $(BUILD)
+$(BUILD)/bdpt_kernels.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h $(CSRC)/bdpt_frame_kernels.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the path kernel's sources as strings, for scene-specialised kernels compiled at run time
 $(CSRC)/bdpt_jit_src.h: tools/embed_jit_sources.py $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h
 	python3 tools/embed_jit_sources.py $@
 
-$(BUILD)/bdpt_host.o: $(CSRC)/bdpt_host.cpp $(CSRC)/bdpt_device.h $(CSRC)/bdpt_plan.h $(CSRC)/bdpt_bvh.h $(CSRC)/bdpt_cpu.h $(CSRC)/bdpt_jit_src.h include/bdpt.h | $(BUILD)
+CTX_DEPS := $(CSRC)/bdpt_ctx.h $(CSRC)/bdpt_device.h $(CSRC)/bdpt_plan.h $(CSRC)/bdpt_cpu.h include/bdpt.h
+$(BUILD)/bdpt_host.o: $(CSRC)/bdpt_host.cpp $(CTX_DEPS) $(CSRC)/bdpt_bvh.h $(CSRC)/bdpt_jit_src.h | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/bdpt_frame.o: $(CSRC)/bdpt_frame.cpp $(CTX_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/bdpt_bvh.o: $(CSRC)/bdpt_bvh.cpp $(CSRC)/bdpt_bvh.h include/bdpt.h | $(BUILD)
@@ -62,7 +66,7 @@ $(BUILD)/bdpt_util.o: $(CSRC)/bdpt_util.c include/bdpt.h | $(BUILD)
 $(BUILD)/bdpt_ckpt.o: $(CSRC)/bdpt_ckpt.c include/bdpt.h | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(LIB): $(BUILD)/bdpt_kernels.o $(BUILD)/bdpt_host.o $(BUILD)/bdpt_bvh.o $(BUILD)/bdpt_cpu.o $(BUILD)/bdpt_util.o $(BUILD)/bdpt_ckpt.o
+$(LIB): $(BUILD)/bdpt_kernels.o $(BUILD)/bdpt_host.o $(BUILD)/bdpt_frame.o $(BUILD)/bdpt_bvh.o $(BUILD)/bdpt_cpu.o $(BUILD)/bdpt_util.o $(BUILD)/bdpt_ckpt.o
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl
 
@@ -136,11 +140,12 @@ $(ASAN_DIR)/%.o: $(CSRC)/%.c include/bdpt.h | $(ASAN_DIR)
 $(ASAN_DIR)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h | $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -std=c++17 -c $< -o $@
 
-# (asan_cpu_abi_denoise.cpp = asan_cpu_abi.cpp + the bdpt_denoise entry point smallpt --denoise calls;
-# asan_cpu_abi_reproject.cpp = that + the history entry points smallpt --reproject calls;
-# asan_cpu_abi_preview.cpp = that + bdpt_preview_denoise, which smallpt --reproject --denoise calls;
-# asan_cpu_abi_noise.cpp = that + the noise estimate's entry points smallpt --until calls)
-$(ASAN_DIR)/asan_cpu_abi.o: tests/native/asan_cpu_abi_noise.cpp tests/native/asan_cpu_abi_preview.cpp tests/native/asan_cpu_abi_reproject.cpp tests/native/asan_cpu_abi_denoise.cpp tests/native/asan_cpu_abi.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h | $(ASAN_DIR)
+# the HIP-free context layer: every entry point smallpt calls, the frame services included, in
+# tests/native/asan_cpu_abi.cpp.  It used to be a chain of files, each including the one before and
+# adding a service's entry points, with asan_cpu_abi_noise.cpp on top; a tests/ tree that still has
+# the chain (the sanitizer tests as they stood before the layer became one file) builds its top.
+ASAN_ABI_SRC := $(firstword $(wildcard tests/native/asan_cpu_abi_noise.cpp) tests/native/asan_cpu_abi.cpp)
+$(ASAN_DIR)/asan_cpu_abi.o: $(ASAN_ABI_SRC) $(wildcard tests/native/asan_cpu_abi*.cpp) $(CSRC)/bdpt_cpu.h include/bdpt.h | $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -std=c++17 -c $< -o $@
 
 $(ASAN_DIR)/bdpt_oracle.o: oracle/bdpt_oracle.c include/bdpt.h | $(ASAN_DIR)

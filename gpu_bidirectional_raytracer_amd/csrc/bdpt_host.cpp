@@ -5,6 +5,10 @@
 // loadMTGPU/seedMTGPU of src/MersenneTwister_kernel.cu:23-51.  One context = one GPU + one
 // HIP stream.  Every HIP call is checked; failures return BDPT_EHIP with the HIP message in
 // bdpt_last_error() (the reference prints and continues; the host shell decides).
+//
+// Here: contexts, scene upload, run-time compilation, the path passes, multi-device contexts,
+// checkpoints and the display.  The context itself is in bdpt_ctx.h; the frame services (feature
+// buffers, denoiser, reprojection, preview, noise estimate) are in bdpt_frame.cpp.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -23,12 +27,11 @@
 #include <string>
 #include <vector>
 
-#include "../../include/bdpt.h"
-#include "bdpt_device.h"
+#include "bdpt_ctx.h"
 #include "bdpt_bvh.h"
-#include "bdpt_cpu.h"
-#include "bdpt_plan.h"
 #include <chrono>
+
+using namespace bdpt_host;
 
 static_assert(kBvhEmissive == BDPT_DEV_BVH_EMISSIVE, "BVH id flag");
 
@@ -52,220 +55,10 @@ extern "C" __global__ void bdpt_accum_kernel(bdpt_path_args);
 extern "C" __global__ void bdpt_accum_serial_kernel(bdpt_path_args);
 
 extern "C" __global__ void bdpt_frame_add_kernel(float*, const float*, unsigned*, const unsigned*, int);
-extern "C" __global__ void bdpt_aov_kernel(bdpt_path_args, bdpt_aov_args);
-extern "C" __global__ void bdpt_denoise_pack_kernel(const int*, const bdpt_dev_vec*, const bdpt_dev_vec*,
-                                                    const bdpt_dev_sphere*, int, float4*, float4*, int);
-extern "C" const void* bdpt_denoise_level_table[2][7];   // [LDS staging][normal_power]
-extern "C" __global__ void bdpt_history_pack_kernel(const int*, const bdpt_dev_vec*, const bdpt_dev_vec*,
-                                                    const float*, float4*, float4*, int);
-extern "C" __global__ void bdpt_reproject_kernel(bdpt_reproject_args);
-extern "C" const void* bdpt_preview_level_table[2][7];   // [LDS staging][normal_power]
-extern "C" __global__ void bdpt_noise_mark_kernel(const bdpt_dev_vec*, const unsigned*, uint4*, int);
-extern "C" __global__ void bdpt_noise_kernel(bdpt_noise_args);
-static_assert(BDPT_NOISE_BTW == BDPT_NOISE_TW && BDPT_NOISE_BTH == BDPT_NOISE_TH, "the kernel's tile is the ABI's");
 
 // gamma thresholds (host, once): see bdpt_util.c
 extern "C" void bdpt_gamma_thresholds(float thr[256]);
 
-struct bdpt_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    // Pass-stream folds (bdpt_accum_kernel) run on their own stream so that a launch's fold
-    // overlaps the next launch's path kernel (VALU-bound; the fold is a memory stream); pixel
-    // pools fold on `stream` right after their launch instead (bdpt_accum_serial_kernel).  The
-    // radiance buffer is double-buffered: launch L writes half L % 2 after the fold of launch L-2
-    // has read it.  Everything else that touches colors/counter/pixels runs on `stream` after
-    // join_fold() has made it wait for the last concurrent fold.
-    hipStream_t fstream = nullptr;
-    // Pixel pools with overlapped launches: a pooled launch and its serial fold run on
-    // pstream[half of the radiance buffer], so one launch's drain overlaps the next one's start;
-    // the folds stay in order through rb_fold_ev.  Everything queued on `stream` that feeds or
-    // follows the path kernels joins the last fold first (join_fold).
-    hipStream_t pstream[2] = {nullptr, nullptr};
-    hipEvent_t amark = nullptr;         // `stream`'s work before a call, for the pstreams to wait on
-    bool pool_dirty = false;            // overlapped launches used the claim-counter sets
-    unsigned long long* d_prof = nullptr;   // BDPT_PROF=1 (with a -DBDPT_PROF kernel): section cycles
-    hipEvent_t rb_path_ev[2] = {nullptr, nullptr};   // path kernel of the half done (stream)
-    hipEvent_t rb_fold_ev[2] = {nullptr, nullptr};   // fold of the half done (fstream)
-    bool rb_used[2] = {false, false};
-    int rb_next = 0, fold_last = 0;
-    bool fold_pending = false;          // a fold was issued after the last join_fold
-    hipStream_t fold_stream = nullptr;  // the stream of the last fold (fstream or a pstream)
-    // Path-pass calls go through a ring of kRing slots, each with its own events, so a call
-    // never waits for the GPU except on the call issued kRing calls earlier (the reference's
-    // interactive loop issues one pass per call; the pass tables travel in the kernel
-    // arguments).  Timing is folded lazily, in call order.
-    static constexpr int kRing = 4;
-    struct call_slot {
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;   // the whole call
-        std::vector<hipEvent_t> kev;               // per path-kernel launch {before, after}
-        int launches = 0;
-        bool pending = false;                      // issued, not folded yet
-        bool serial_fold = false;                  // its folds ran after its path kernels, in-stream
-    } ring[kRing];
-    long long issued = 0, folded = 0;   // calls issued / folded into the accumulators
-    double acc_ms = 0.0;         // accumulated device time of finished path-pass calls
-    long long acc_launches = 0;
-    float last_ms = 0.f;
-    double acc_kernel_ms = 0.0;    // path kernels alone (no fold kernel)
-    int W = 0, H = 0;
-    std::vector<bdpt_sphere> spheres;
-    std::vector<int> lights;
-    bdpt_camera cam{};
-    bool cam_set = false;
-    bool rand_ready = false;
-    int shard = 0, nshards = 1, band_rows = 8;
-    int streams_req = 0;                // bdpt_set_streams: 0 = auto (measured), -1 = one pass per lane
-    // auto mode: the first ten calls of >= 2 passes each measure one kernel variant (roles 0..9,
-    // the table in bdpt_plan.h); the eleventh decides which one later calls run.
-    bdpt_tuner tuner;
-    // multi-device groups: the peers follow the stream mode devices[0] measured (its decision is
-    // copied when they reach the decision point), so every device of a group runs the same kernels
-    bdpt_ctx* group_leader = nullptr;
-    int last_streams = 1;               // S of the last path-pass launch
-    bool last_bvh = false;              // the last path-pass launch traversed the BVH
-    int cus = 256;                      // compute units (auto stream count)
-    // LDS per workgroup the device allows (hipDeviceAttributeMaxSharedMemoryPerBlock), the static
-    // LDS of the path kernels looked at so far (by function), and the figures of the last
-    // bdpt_path_passes call's largest launch, refused or not (bdpt_path_lds)
-    size_t lds_limit = 0;
-    std::vector<std::pair<const void*, size_t>> lds_static;
-    size_t last_lds_static = 0, last_lds_dynamic = 0;
-    bdpt_dev_vec* d_rbuf = nullptr;     // pass-stream radiance, 2 halves of rbuf_cap: [npass][nloc]
-    unsigned* d_rmask = nullptr;        // pixel pools: 4 words per launched pixel (stored passes), 2 halves
-    unsigned* d_poolctr = nullptr;      // pixel pools: claimed pixels per pass and eighth, a line each,
-                                        // two sets: a pooled launch uses one and zeroes the other
-    int pool_set = 0;                   // the set the next pooled launch uses
-    unsigned* d_uflags = nullptr;       // ordered in-kernel fold (units): per 8x8 wave tile, epoch << 8 | range
-    size_t uflags_cap = 0;
-    unsigned uepoch = 0;                // launches of the units kernel (flag tags)
-    unsigned* d_uerr = nullptr;         // set by a unit whose handover wait timed out
-    bool units_check = false;           // a units launch ran since the last error check
-    int traversal = BDPT_TRAVERSE_AUTO; // bdpt_set_traversal
-    bool has_bvh = false;               // the scene has a BVH (bdpt_bvh.cpp)
-    int bvh_nn = 0, bvh_ns = 0, big_n = 0;
-    float bvh_c[3] = {0.f, 0.f, 0.f}, bvh_r = 0.f, bvh_q = 0.f;
-    float4 *d_bvh_nodes = nullptr, *d_bvh_geom = nullptr, *d_big_geom = nullptr, *d_mat = nullptr;
-    int *d_bvh_ids = nullptr, *d_big_ids = nullptr;
-    size_t rbuf_cap = 0;                // elements
-    size_t rmask_lanes = 0;             // launched pixels the mask halves hold (4 words each)
-    uint4* d_params = nullptr;          // 4096 x {matrix_a, mask_b, mask_c, seed}
-    float* d_rand = nullptr;
-    float* d_rndp = nullptr;            // planar copy of d_rand (bdpt_rand_planar_kernel)
-    // Tables derived from d_rand that only some path kernels read: allocated on first need and
-    // filled before the first launch of a kernel that reads them (ensure_scp / ensure_srec); every
-    // table change (one_generate_rand: the light pass and a checkpoint load come through it) clears
-    // the ready flags.  Each device of a multi-device context owns its own.
-    float2* d_scp = nullptr;            // {sinf, cosf}(2 pi u) per d_rndp entry (bdpt_sincos_planar_kernel)
-    float4* d_srec = nullptr;           // sample records (bdpt_sample_records_kernel, bdpt_device.h)
-    bool scp_ready = false, srec_ready = false;   // they hold the current table's values
-    bdpt_dev_lightpath* d_lp = nullptr;
-    bdpt_dev_sphere* d_sph = nullptr;
-    unsigned sph_cap = 0;
-    int* d_lights = nullptr;
-    float4* d_geom = nullptr;           // per sphere {p, rad^2}; then the n_vac non-emitters' (VLP-only shadow rounds)
-    unsigned n_vac = 0;
-    float4* d_lightrec = nullptr;       // per emitter {p, rad}, {e, (4*pi*rad)*rad}
-    unsigned emis_mask = 0;
-    bdpt_dev_vec* d_colors = nullptr;
-    unsigned* d_counter = nullptr;
-    uchar4* d_pixels = nullptr;
-    float* d_thr = nullptr;
-    uint32_t h_params[4 * BDPT_MT_RNG_COUNT];
-    // scene-specialised path kernels (hipRTC), by compile options; modules live until destroy
-    bool specialize = true;             // bdpt_set_specialize
-    bool last_specialized = false;
-    std::map<std::string, hipFunction_t> jit_fns;
-    std::vector<hipModule_t> jit_mods;
-    char jit_err[256] = {0};            // why the last specialisation fell back (diagnostics)
-    int jit_waves = 0;                  // waves/SIMD bound of the last specialised build
-    bool jit_zero_exit = false;         // the last specialised build has the black-surface exit
-    // jit_path_kernel's answer per [fused / pass streams / pools][paired loads] for the current scene, specialise
-    // switch and JIT environment (jit_env_key): a call then resolves its kernel without rebuilding the option
-    // strings (tens of microseconds per call, which the one-pass-per-call pattern pays every call)
-    struct jit_memo_t {
-        bool valid = false, zero_exit = false;
-        hipFunction_t fn = nullptr;
-        int waves = 0;
-        std::string flags, err;
-    } jit_memo[4][2];
-    int last_features = 0;              // BDPT_FEAT_* of the last path-pass launch
-    unsigned rand_seed = 0;             // seed of the current MT607 table (rand_ready)
-    char err[512] = {0};
-    // multi-device context (bdpt_create_multi): this context renders on devices[0] and owns the
-    // peer contexts of the other devices; the frame is assembled on devices[0] by a sum-reduce
-    bool multi = false;
-    std::vector<bdpt_ctx*> peers;
-    std::vector<void*> comms;           // ncclComm_t per device when the reduce runs on RCCL
-    int reduce_mode = 0;                // kReduce*
-    bool frame_stale = true;            // the assembled frame predates the last change
-    bdpt_dev_vec* d_fcolors = nullptr;  // assembled frame (devices[0])
-    unsigned* d_fcounter = nullptr;
-    uchar4* d_fpixels = nullptr;
-    bdpt_dev_vec* d_ftmp = nullptr;     // peer-copy staging (kReducePeer)
-    unsigned* d_ftmpc = nullptr;
-    char reduce_note[256] = {0};        // the RCCL version and communicator, or why RCCL is not used
-    bdpt_cpu_ctx* cpu = nullptr;        // device == BDPT_DEVICE_CPU: the host backend (bdpt_cpu.cpp)
-    hipGraphicsResource_t gl_res = nullptr;   // registered GL pixel-unpack buffer (bdpt_gl_register_pbo)
-    // first-hit feature buffers (bdpt_render_aov): six output planes of aov_cap pixels each in one
-    // allocation (12 words per pixel), made on the first call and grown when a window needs more
-    float* d_aov = nullptr;
-    size_t aov_cap = 0;
-    hipEvent_t aov_ev[2] = {nullptr, nullptr};   // around the kernel of the last call
-    int aov_traversal = 0;              // BDPT_TRAVERSE_* of the last call (0: none yet)
-    float aov_cpu_ms = 0.f;             // CPU backend: wall time of the last call's loop
-    // denoiser (bdpt_denoise): guide, ping and pong records of the whole frame in one allocation
-    // (3 x 16 B per pixel), made on the first call -- the frame size never changes
-    float4* d_dn = nullptr;
-    hipEvent_t dn_ev[2] = {nullptr, nullptr};    // around the kernels of the last call
-    bool dn_ran = false;
-    float dn_cpu_ms = 0.f;              // CPU backend: wall time of the last call
-    // temporal reprojection (bdpt_reproject): two sets of {guide, colour + weight} records
-    // (2 x 32 B per pixel; set hist_cur is the history, a capture writes the other) and the packed
-    // results of a call (12 + 4 + 4 B per pixel) in one allocation, made on first use
-    float4* d_hist = nullptr;
-    int hist_cur = 0;
-    bool has_hist = false;              // a history is stored (under hist_cam / hist_spheres)
-    bdpt_camera hist_cam{};
-    std::vector<bdpt_sphere> hist_spheres;
-    hipEvent_t rp_ev[2] = {nullptr, nullptr};    // around the kernels of the last capture / reprojection
-    bool rp_ran = false;
-    float rp_cpu_ms = 0.f;              // CPU backend: wall time of the last call
-    // denoised preview (bdpt_preview_denoise): works in d_dn and d_hist's result buffers
-    hipEvent_t pv_ev[2] = {nullptr, nullptr};    // around the kernels of the last call
-    bool pv_ran = false;
-    float pv_cpu_ms = 0.f;              // CPU backend: wall time of the last call
-    // noise estimate (bdpt_noise_estimate): the mark's 16-byte records and the results of a call
-    // (the per-pixel plane, then S, E, c and the pending count per tile), each made on first use.
-    // mark_live = false is the cleared mark: the kernel then reads every count as 0.
-    uint4* d_mark = nullptr;
-    bool mark_live = false;
-    float* d_noise = nullptr;
-    hipEvent_t nz_ev[2] = {nullptr, nullptr};    // around the kernel of the last estimate
-    bool nz_ran = false;
-    float nz_cpu_ms = 0.f;              // CPU backend: wall time of the last estimate
-    unsigned gl_pbo = 0;
-};
-enum { kReduceNone = 0, kReduceRccl = 1, kReducePeer = 2 };
-
-static int fail(bdpt_ctx* c, int code, const char* fmt, ...) {
-    if (c) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(c->err, sizeof(c->err), fmt, ap);
-        va_end(ap);
-    }
-    return code;
-}
-
-#define HIPCHK(ctx, call)                                                                      \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail((ctx), BDPT_EHIP, "%s: %s", #call, hipGetErrorString(e_));            \
-    } while (0)
-
-static int join_fold(bdpt_ctx* c);
 static int upload_scene(bdpt_ctx* c) {
     c->tuner.reset();                                       // re-measure the stream mode
     for (auto& row : c->jit_memo)                           // the specialised kernels change too
@@ -377,16 +170,9 @@ static void release(bdpt_ctx* c) {
                     c->d_mark, c->d_noise};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
-    for (hipEvent_t e : c->aov_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->dn_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->rp_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->pv_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->nz_ev)
-        if (e) (void)hipEventDestroy(e);
+    for (const bdpt_svc_clock& k : c->svc)
+        for (hipEvent_t e : k.ev)
+            if (e) (void)hipEventDestroy(e);
     for (auto& s : c->ring) {
         for (hipEvent_t e : s.kev) (void)hipEventDestroy(e);
         if (s.ev0) (void)hipEventDestroy(s.ev0);
@@ -807,7 +593,7 @@ static hipFunction_t jit_path_kernel(bdpt_ctx* c, bool streams, bool pair = true
 // Make the context's stream wait for the last pass-stream fold (issued on fstream): call before
 // anything on `stream` touches colors/counter/pixels.  Folds run in order on fstream, so the last
 // one covers all.
-static int join_fold(bdpt_ctx* c) {
+int bdpt_host::join_fold(bdpt_ctx* c) {
     if (c->cpu || !c->fold_pending) return BDPT_OK;
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->rb_fold_ev[c->fold_last], 0));
     c->fold_pending = false;
@@ -1189,7 +975,7 @@ static void vnorm3(float v[3]) {
 
 // The frame and camera constants of a launch (the by-value Camera of device.cu:548, as the kernels
 // take it): shared by the path passes and the feature-buffer kernel.
-static void camera_args(const bdpt_ctx* c, const bdpt_camera& cam, bdpt_path_args& a) {
+extern "C++" void bdpt_host::camera_args(const bdpt_ctx* c, const bdpt_camera& cam, bdpt_path_args& a) {
     a.W = c->W; a.H = c->H;
     a.inv_w = (float)(14. / c->W);                       // smallpt_cpu.c:411-412
     a.inv_h = (float)(10.5 / c->H);
@@ -1257,17 +1043,24 @@ static int path_args_base(bdpt_ctx* c, bdpt_path_args& a) {
     return BDPT_OK;
 }
 
+// The BVH fields of a launch that traverses it: the path passes' (path_args_plan) and the
+// feature-buffer kernel's (bdpt_frame.cpp aov_launch).
+extern "C++" void bdpt_host::bvh_args(const bdpt_ctx* c, bdpt_path_args& a) {
+    a.bvh_nodes = c->d_bvh_nodes; a.bvh_geom = c->d_bvh_geom; a.bvh_ids = c->d_bvh_ids;
+    a.big_geom = c->d_big_geom; a.big_ids = c->d_big_ids;
+    a.bvh_nn = c->bvh_nn; a.bvh_ns = c->bvh_ns; a.big_n = c->big_n;
+    for (int k = 0; k < 3; k++) a.bvh_c[k] = c->bvh_c[k];
+    a.bvh_r = c->bvh_r;
+    a.bvh_q = c->bvh_q;
+}
+
 // The plan's part of the arguments: the shard's grid and, for a plan that traverses it, the BVH.
 static void path_args_plan(const bdpt_ctx* c, const bdpt_plan& plan, bdpt_path_args& a) {
     a.tiles_per_band = plan.tiles_per_band;
     a.nloc = (int)plan.lanes;
     if (!plan.bvh) return;
-    a.bvh_nodes = c->d_bvh_nodes; a.bvh_geom = c->d_bvh_geom; a.bvh_ids = c->d_bvh_ids;
-    a.big_geom = c->d_big_geom; a.big_ids = c->d_big_ids; a.mat = c->d_mat;
-    a.bvh_nn = c->bvh_nn; a.bvh_ns = c->bvh_ns; a.big_n = c->big_n;
-    for (int k = 0; k < 3; k++) a.bvh_c[k] = c->bvh_c[k];
-    a.bvh_r = c->bvh_r;
-    a.bvh_q = c->bvh_q;
+    bvh_args(c, a);
+    a.mat = c->d_mat;
 }
 
 // Auto stream mode with every role's call issued: a group peer takes the decision of devices[0]
@@ -1671,7 +1464,7 @@ static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int
 // After the stream has drained: did a unit's handover wait time out in a units launch since the
 // last check?  Reported once by whichever call looks first (synchronize, the timing calls, the
 // read-backs); the error word is then cleared, so later launches report only their own timeouts.
-static int units_verdict(bdpt_ctx* c) {
+extern "C++" int bdpt_host::units_verdict(bdpt_ctx* c) {
     if (!c->units_check) return BDPT_OK;
     unsigned e = 0;
     HIPCHK(c, hipMemcpy(&e, c->d_uerr, sizeof e, hipMemcpyDeviceToHost));
@@ -2283,759 +2076,6 @@ int bdpt_update_pixels(bdpt_ctx* c) {
     if (!c) return BDPT_EINVAL;
     if (!c->multi) return one_update_pixels(c);
     return assemble(c);
-}
-
-// ---- first-hit feature buffers (include/bdpt.h bdpt_render_aov) -----------------------------
-// One launch of bdpt_aov_kernel over the window on the context's stream (so it runs after the
-// table generation, light pass and scene upload queued there; it reads nothing the path passes
-// write), then the wanted planes are read back through the same stream.  Nothing of the path
-// passes' state is touched: not the accumulation, not the timing ring, not the stream choice.
-// Capacity of d_aov, the kernel's arguments and its launch on the context's stream (between the
-// two events, if given); the caller has checked the window, the camera and the table.  *v holds
-// the output planes on return.  Shared with bdpt_denoise, whose guides are these planes.
-static int aov_launch(bdpt_ctx* c, const bdpt_camera& cam, int x0, int y0, int w, int h, int jitter, unsigned sid,
-                      bdpt_aov_args* vout, bool* bvh_out, hipEvent_t ev0, hipEvent_t ev1) {
-    const size_t np = (size_t)w * (size_t)h;
-    if (np > c->aov_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));           // an earlier call's copies are done anyway
-        if (c->d_aov) HIPCHK(c, hipFree(c->d_aov));
-        c->d_aov = nullptr;
-        c->aov_cap = 0;
-        if (hipMalloc(&c->d_aov, 12 * sizeof(float) * np) != hipSuccess)
-            return fail(c, BDPT_ENOMEM, "bdpt_render_aov: output planes (%zu B)", 12 * sizeof(float) * np);
-        c->aov_cap = np;
-    }
-    bdpt_path_args a;
-    memset(&a, 0, sizeof(a));
-    a.n = (unsigned)c->spheres.size();
-    a.geom = c->d_geom;
-    a.rnd = c->d_rand;
-    camera_args(c, cam, a);
-    const bool bvh = c->has_bvh && c->traversal != BDPT_TRAVERSE_BRUTE;
-    if (bvh) {
-        a.bvh_nodes = c->d_bvh_nodes; a.bvh_geom = c->d_bvh_geom; a.bvh_ids = c->d_bvh_ids;
-        a.big_geom = c->d_big_geom; a.big_ids = c->d_big_ids;
-        a.bvh_nn = c->bvh_nn; a.bvh_ns = c->bvh_ns; a.big_n = c->big_n;
-        for (int k = 0; k < 3; k++) a.bvh_c[k] = c->bvh_c[k];
-        a.bvh_r = c->bvh_r;
-        a.bvh_q = c->bvh_q;
-    }
-    bdpt_aov_args v;
-    memset(&v, 0, sizeof(v));
-    v.x0 = x0; v.y0 = y0; v.w = w; v.h = h;
-    v.jitter = jitter != 0;
-    v.sid = sid;
-    v.bvh = bvh;
-    v.rows = !bvh;
-    if (const char* e = getenv("BDPT_AOV_TILE")) {            // experiments: 8 = 8x8 wave tiles, 64 = rows
-        if (atoi(e) == 8) v.rows = 0;
-        if (atoi(e) == 64) v.rows = 1;
-    }
-    float* base = c->d_aov;
-    v.id = (int*)base;
-    v.t = base + c->aov_cap;
-    v.dp = base + 2 * c->aov_cap;
-    v.position = (bdpt_dev_vec*)(base + 3 * c->aov_cap);
-    v.normal = (bdpt_dev_vec*)(base + 6 * c->aov_cap);
-    v.dir = (bdpt_dev_vec*)(base + 9 * c->aov_cap);
-    const int btw = v.rows ? BDPT_AOV_ROW_BTW : BDPT_AOV_BVH_BTW, bth = v.rows ? BDPT_AOV_ROW_BTH : BDPT_AOV_BVH_BTH;
-    const dim3 grid((unsigned)((w + btw - 1) / btw), (unsigned)((h + bth - 1) / bth), 1), block(256);
-    if (ev0) HIPCHK(c, hipEventRecord(ev0, c->stream));
-    hipLaunchKernelGGL(bdpt_aov_kernel, grid, block, 0, c->stream, a, v);
-    HIPCHK(c, hipGetLastError());
-    if (ev1) HIPCHK(c, hipEventRecord(ev1, c->stream));
-    *vout = v;
-    *bvh_out = bvh;
-    return BDPT_OK;
-}
-
-int bdpt_render_aov(bdpt_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid,
-                    const bdpt_aov_buffers* out) {
-    if (!c) return BDPT_EINVAL;
-    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_render_aov: multi-device contexts render no feature buffers");
-    if (!out) return fail(c, BDPT_EINVAL, "bdpt_render_aov: no output buffers");
-    if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 > c->W - w || y0 > c->H - h)
-        return fail(c, BDPT_EINVAL, "bdpt_render_aov: window %d,%d %dx%d is empty or outside the %dx%d frame", x0, y0,
-                    w, h, c->W, c->H);
-    if (sid >= (unsigned)BDPT_RAND_N) return fail(c, BDPT_EINVAL, "bdpt_render_aov: sid %u >= RAND_N", sid);
-    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_render_aov: camera not set");
-    if (jitter && !c->rand_ready)
-        return fail(c, BDPT_ESTATE, "bdpt_render_aov: jitter needs a random table (run the light pass first)");
-    if (c->cpu) {
-        const auto t0 = std::chrono::steady_clock::now();
-        bdpt_cpu_render_aov(c->cpu, x0, y0, w, h, jitter, sid, out);
-        c->aov_cpu_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        c->aov_traversal = BDPT_TRAVERSE_BRUTE;
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t np = (size_t)w * (size_t)h;
-    for (hipEvent_t& e : c->aov_ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
-    bdpt_aov_args v;
-    bool bvh = false;
-    if (int rc = aov_launch(c, c->cam, x0, y0, w, h, jitter, sid, &v, &bvh, c->aov_ev[0], c->aov_ev[1])) return rc;
-    c->aov_traversal = bvh ? BDPT_TRAVERSE_BVH : BDPT_TRAVERSE_BRUTE;
-    auto back = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    };
-    HIPCHK(c, back(out->id, v.id, sizeof(int) * np));
-    HIPCHK(c, back(out->t, v.t, sizeof(float) * np));
-    HIPCHK(c, back(out->dp, v.dp, sizeof(float) * np));
-    HIPCHK(c, back(out->position, v.position, sizeof(bdpt_vec) * np));
-    HIPCHK(c, back(out->normal, v.normal, sizeof(bdpt_vec) * np));
-    HIPCHK(c, back(out->dir, v.dir, sizeof(bdpt_vec) * np));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BDPT_OK;
-}
-
-int bdpt_pick(bdpt_ctx* c, int x, int y, int jitter, unsigned sid, int* id, float* t) {
-    bdpt_aov_buffers out;
-    memset(&out, 0, sizeof(out));
-    out.id = id;
-    out.t = t;
-    return bdpt_render_aov(c, x, y, 1, 1, jitter, sid, &out);
-}
-
-int bdpt_last_aov_traversal(const bdpt_ctx* c) {
-    if (!c) return BDPT_EINVAL;
-    return c->aov_traversal ? c->aov_traversal : BDPT_ESTATE;
-}
-
-int bdpt_last_aov_ms(bdpt_ctx* c, float* ms) {
-    if (!c || !ms) return BDPT_EINVAL;
-    if (!c->aov_traversal) return fail(c, BDPT_ESTATE, "bdpt_last_aov_ms: no feature buffers rendered");
-    if (c->cpu) {
-        *ms = c->aov_cpu_ms;
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipEventSynchronize(c->aov_ev[1]));
-    HIPCHK(c, hipEventElapsedTime(ms, c->aov_ev[0], c->aov_ev[1]));
-    return BDPT_OK;
-}
-
-// ---- edge-avoiding wavelet denoiser (include/bdpt.h bdpt_denoise) --------------
-// On the context's stream, after the last fold (the colours are the folds' output): the unjittered
-// whole-frame bdpt_aov_kernel, bdpt_denoise_pack_kernel (guide records + the first ping buffer),
-// one level kernel per level (ping-pong), the last of which writes the packed results, then the
-// read-back.  The packed results go where the feature planes were: the pack kernel has consumed
-// them, and 16 B of a pixel's 48 B there hold its float3 and its RGBA.  Only d_aov and d_dn are
-// written; nothing of the path passes' state is touched.
-int bdpt_denoise(bdpt_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out, unsigned char* rgba_out) {
-    if (!c) return BDPT_EINVAL;
-    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_denoise: multi-device contexts are not denoised (upload the assembled frame to a one-device context)");
-    if (!p) return fail(c, BDPT_EINVAL, "bdpt_denoise: no parameters");
-    if (!colors_out && !rgba_out) return fail(c, BDPT_EINVAL, "bdpt_denoise: no output buffer");
-    if (p->levels < 1 || p->levels > 8) return fail(c, BDPT_EINVAL, "bdpt_denoise: levels %d outside 1..8", p->levels);
-    if (p->normal_power < 0 || p->normal_power > 6)
-        return fail(c, BDPT_EINVAL, "bdpt_denoise: normal_power %d outside 0..6", p->normal_power);
-    if (!(p->sigma_color > 0.f)) return fail(c, BDPT_EINVAL, "bdpt_denoise: sigma_color must be > 0");
-    if (p->materials != BDPT_DENOISE_DIFFUSE && p->materials != BDPT_DENOISE_ALL)
-        return fail(c, BDPT_EINVAL, "bdpt_denoise: materials %d", p->materials);
-    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_denoise: camera not set");
-    if (c->cpu) {
-        const auto t0 = std::chrono::steady_clock::now();
-        bdpt_cpu_denoise(c->cpu, p, colors_out, rgba_out);
-        c->dn_cpu_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        c->dn_ran = true;
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t np = (size_t)c->W * c->H;
-    if (!c->d_dn && hipMalloc(&c->d_dn, 3 * sizeof(float4) * np) != hipSuccess) {
-        c->d_dn = nullptr;
-        return fail(c, BDPT_ENOMEM, "bdpt_denoise: guide, ping and pong buffers (%zu B)", 3 * sizeof(float4) * np);
-    }
-    for (hipEvent_t& e : c->dn_ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
-    if (int rc = join_fold(c)) return rc;
-    HIPCHK(c, hipEventRecord(c->dn_ev[0], c->stream));
-    bdpt_aov_args av;
-    bool bvh = false;
-    if (int rc = aov_launch(c, c->cam, 0, 0, c->W, c->H, 0, 0u, &av, &bvh, nullptr, nullptr)) return rc;
-    float4 *guide = c->d_dn, *ping = c->d_dn + np, *pong = c->d_dn + 2 * np;
-    const dim3 block(256);
-    hipLaunchKernelGGL(bdpt_denoise_pack_kernel, dim3((unsigned)((np + 255) / 256)), block, 0, c->stream,
-                       (const int*)av.id, (const bdpt_dev_vec*)av.normal, (const bdpt_dev_vec*)c->d_colors,
-                       (const bdpt_dev_sphere*)c->d_sph, (int)(p->materials == BDPT_DENOISE_ALL), guide, ping, (int)np);
-    HIPCHK(c, hipGetLastError());
-    bdpt_dev_vec* d_out3 = (bdpt_dev_vec*)c->d_aov;           // 3 of a pixel's 12 words there
-    uchar4* d_rgba = (uchar4*)(c->d_aov + 3 * c->aov_cap);    // the 4th
-    bdpt_denoise_args v;
-    memset(&v, 0, sizeof(v));
-    v.W = c->W; v.H = c->H;
-    v.normal_power = p->normal_power;
-    v.guide = guide;
-    v.gamma_thr = c->d_thr;
-    // tile shape and LDS staging: the measured choice; the environment overrides
-    // it for experiments (BDPT_DENOISE_TILE = 8 / 64, BDPT_DENOISE_LDS = 0 / 1)
-    v.rows = 1;
-    bool lds = true;
-    if (const char* e = getenv("BDPT_DENOISE_TILE")) v.rows = atoi(e) == 64;
-    if (const char* e = getenv("BDPT_DENOISE_LDS")) lds = atoi(e) == 1;
-    const float isc0 = 1.0f / (p->sigma_color * p->sigma_color);
-    for (int k = 0; k < p->levels; k++) {
-        const bool last = k == p->levels - 1;
-        v.step = 1 << k;
-        v.isc = isc0 * (float)(1 << (2 * k));
-        v.cur = k % 2 ? pong : ping;
-        v.nxt = last ? nullptr : (k % 2 ? ping : pong);
-        v.out3 = last && colors_out ? d_out3 : nullptr;
-        v.rgba = last && rgba_out ? d_rgba : nullptr;
-        const bool staged = lds && v.step <= BDPT_DN_LDS_MAX_STEP;
-        const int btw = staged || !v.rows ? BDPT_DN_BTW : BDPT_DN_ROW_BTW;
-        const int bth = staged || !v.rows ? BDPT_DN_BTH : BDPT_DN_ROW_BTH;
-        const dim3 grid((unsigned)((c->W + btw - 1) / btw), (unsigned)((c->H + bth - 1) / bth), 1);
-        void* kargs[] = {&v};
-        HIPCHK(c, hipLaunchKernel(bdpt_denoise_level_table[staged][p->normal_power], grid, block, kargs, 0, c->stream));
-    }
-    HIPCHK(c, hipEventRecord(c->dn_ev[1], c->stream));
-    c->dn_ran = true;
-    if (colors_out)
-        HIPCHK(c, hipMemcpyAsync(colors_out, d_out3, sizeof(bdpt_vec) * np, hipMemcpyDeviceToHost, c->stream));
-    if (rgba_out) HIPCHK(c, hipMemcpyAsync(rgba_out, d_rgba, 4 * np, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return units_verdict(c);                                 // a frame known to be invalid is an error
-}
-
-int bdpt_last_denoise_ms(bdpt_ctx* c, float* ms) {
-    if (!c || !ms) return BDPT_EINVAL;
-    if (!c->dn_ran) return fail(c, BDPT_ESTATE, "bdpt_last_denoise_ms: no frame denoised");
-    if (c->cpu) {
-        *ms = c->dn_cpu_ms;
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipEventSynchronize(c->dn_ev[1]));
-    HIPCHK(c, hipEventElapsedTime(ms, c->dn_ev[0], c->dn_ev[1]));
-    return BDPT_OK;
-}
-
-// ---- temporal reprojection (include/bdpt.h bdpt_reproject) ---------------------
-// On the context's stream, after the last fold: the unjittered whole-frame bdpt_aov_kernel under
-// the current camera, (capture) bdpt_history_pack_kernel writing the next history's guide records
-// from its planes, then bdpt_reproject_kernel, which reads the history's records and writes the
-// packed results or the next history's colour records; then the read-back.  Only d_aov and d_hist
-// are written; nothing of the path passes' state is touched.
-static bool hist_present(const bdpt_ctx* c) {
-    if (c->cpu) return bdpt_cpu_history_present(c->cpu);
-    return c->has_hist && c->hist_spheres.size() == c->spheres.size() &&
-           memcmp(c->hist_spheres.data(), c->spheres.data(), sizeof(bdpt_sphere) * c->spheres.size()) == 0;
-}
-
-static int rp_check(bdpt_ctx* c, const bdpt_reproject_params* p, const char* who) {
-    if (c->multi) return fail(c, BDPT_EINVAL, "%s: multi-device contexts keep no history", who);
-    if (!p) return fail(c, BDPT_EINVAL, "%s: no parameters", who);
-    if (p->materials != BDPT_DENOISE_DIFFUSE && p->materials != BDPT_DENOISE_ALL)
-        return fail(c, BDPT_EINVAL, "%s: materials %d", who, p->materials);
-    if (!(p->max_history > 0.f)) return fail(c, BDPT_EINVAL, "%s: max_history must be > 0", who);
-    if (!(p->plane_tol >= 0.f)) return fail(c, BDPT_EINVAL, "%s: plane_tol must be >= 0", who);
-    return BDPT_OK;
-}
-
-// d_hist: float4[4][np] (set s: guide at 2 s, colour + weight at 2 s + 1), then out3, weight, rgba
-struct hist_bufs {
-    float4 *guide[2], *col[2];
-    bdpt_dev_vec* out3;
-    float* weight;
-    uchar4* rgba;
-};
-static int hist_alloc(bdpt_ctx* c, hist_bufs* b) {
-    const size_t np = (size_t)c->W * c->H, bytes = (4 * sizeof(float4) + sizeof(bdpt_dev_vec) + sizeof(float) + 4) * np;
-    if (!c->d_hist && hipMalloc(&c->d_hist, bytes) != hipSuccess) {
-        c->d_hist = nullptr;
-        return fail(c, BDPT_ENOMEM, "bdpt_reproject: history and result buffers (%zu B)", bytes);
-    }
-    for (int s = 0; s < 2; s++) {
-        b->guide[s] = c->d_hist + 2 * s * np;
-        b->col[s] = c->d_hist + (2 * s + 1) * np;
-    }
-    b->out3 = (bdpt_dev_vec*)(c->d_hist + 4 * np);
-    b->weight = (float*)(b->out3 + np);
-    b->rgba = (uchar4*)(b->weight + np);
-    return BDPT_OK;
-}
-
-// bdpt_reproject_kernel's arguments but for its outputs: the current view's first hit (av), the
-// frame, and the history present, if any
-static void rp_args(bdpt_ctx* c, const bdpt_reproject_params* p, const bdpt_aov_args& av, const hist_bufs& b,
-                    bdpt_reproject_args* vout) {
-    bdpt_reproject_args v;
-    memset(&v, 0, sizeof(v));
-    v.W = c->W; v.H = c->H;
-    v.all_materials = p->materials == BDPT_DENOISE_ALL;
-    v.max_history = p->max_history;
-    v.plane_tol = p->plane_tol;
-    v.id = av.id; v.t = av.t; v.position = av.position; v.normal = av.normal;
-    v.sph = c->d_sph;
-    v.colors = c->d_colors;
-    v.counter = c->d_counter;
-    v.gamma_thr = c->d_thr;
-    if (hist_present(c)) {
-        bdpt_path_args ha;                                    // C0 as the kernels' camera constants
-        memset(&ha, 0, sizeof(ha));
-        camera_args(c, c->hist_cam, ha);
-        memcpy(v.ux, ha.ux, sizeof(v.ux)); memcpy(v.uy, ha.uy, sizeof(v.uy)); memcpy(v.ud, ha.ud, sizeof(v.ud));
-        memcpy(v.o, ha.orig, sizeof(v.o));
-        v.hw = (float)ha.half_w; v.hh = (float)ha.half_h;
-        v.sx = 1.f / ha.inv_w; v.sy = 1.f / ha.inv_h;
-        v.hguide = b.guide[c->hist_cur];
-        v.hcol = b.col[c->hist_cur];
-    }
-    // wave tile: the measured choice; BDPT_REPROJECT_TILE = 8 / 64 overrides it
-    v.rows = 1;
-    if (const char* e = getenv("BDPT_REPROJECT_TILE")) v.rows = atoi(e) != 8;
-    *vout = v;
-}
-
-static int rp_run(bdpt_ctx* c, const bdpt_reproject_params* p, bool capture, bdpt_vec* colors_out,
-                  float* weight_out, unsigned char* rgba_out) {
-    if (c->cpu) {
-        const auto t0 = std::chrono::steady_clock::now();
-        if (capture) bdpt_cpu_history_capture(c->cpu, p);
-        else bdpt_cpu_reproject(c->cpu, p, colors_out, weight_out, rgba_out);
-        c->rp_cpu_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        c->rp_ran = true;
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t np = (size_t)c->W * c->H;
-    hist_bufs b;
-    if (int rc = hist_alloc(c, &b)) return rc;
-    for (hipEvent_t& e : c->rp_ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
-    if (int rc = join_fold(c)) return rc;
-    HIPCHK(c, hipEventRecord(c->rp_ev[0], c->stream));
-    bdpt_aov_args av;
-    bool bvh = false;
-    if (int rc = aov_launch(c, c->cam, 0, 0, c->W, c->H, 0, 0u, &av, &bvh, nullptr, nullptr)) return rc;
-    const int nxt = c->hist_cur ^ 1;
-    bdpt_reproject_args v;
-    rp_args(c, p, av, b, &v);
-
-    if (capture) {
-        hipLaunchKernelGGL(bdpt_history_pack_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream,
-                           (const int*)av.id, (const bdpt_dev_vec*)av.position, (const bdpt_dev_vec*)nullptr,
-                           (const float*)nullptr, b.guide[nxt], (float4*)nullptr, (int)np);
-        HIPCHK(c, hipGetLastError());
-        v.next = b.col[nxt];
-    } else {
-        v.out3 = colors_out ? b.out3 : nullptr;
-        v.weight = weight_out ? b.weight : nullptr;
-        v.rgba = rgba_out ? b.rgba : nullptr;
-    }
-    const int btw = v.rows ? BDPT_RP_ROW_BTW : BDPT_RP_BTW, bth = v.rows ? BDPT_RP_ROW_BTH : BDPT_RP_BTH;
-    const dim3 grid((unsigned)((c->W + btw - 1) / btw), (unsigned)((c->H + bth - 1) / bth), 1);
-    hipLaunchKernelGGL(bdpt_reproject_kernel, grid, dim3(256), 0, c->stream, v);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->rp_ev[1], c->stream));
-    c->rp_ran = true;
-    if (capture) {
-        c->hist_cur = nxt;
-        c->has_hist = true;
-        c->hist_cam = c->cam;
-        c->hist_spheres = c->spheres;
-    }
-    if (colors_out) HIPCHK(c, hipMemcpyAsync(colors_out, b.out3, sizeof(bdpt_vec) * np, hipMemcpyDeviceToHost, c->stream));
-    if (weight_out) HIPCHK(c, hipMemcpyAsync(weight_out, b.weight, sizeof(float) * np, hipMemcpyDeviceToHost, c->stream));
-    if (rgba_out) HIPCHK(c, hipMemcpyAsync(rgba_out, b.rgba, 4 * np, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return units_verdict(c);                                 // a frame known to be invalid is an error
-}
-
-int bdpt_reproject(bdpt_ctx* c, const bdpt_reproject_params* p, bdpt_vec* colors_out, float* weight_out,
-                   unsigned char* rgba_out) {
-    if (!c) return BDPT_EINVAL;
-    if (int rc = rp_check(c, p, "bdpt_reproject")) return rc;
-    if (!colors_out && !weight_out && !rgba_out) return fail(c, BDPT_EINVAL, "bdpt_reproject: no output buffer");
-    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_reproject: camera not set");
-    return rp_run(c, p, false, colors_out, weight_out, rgba_out);
-}
-
-int bdpt_history_capture(bdpt_ctx* c, const bdpt_reproject_params* p) {
-    if (!c) return BDPT_EINVAL;
-    if (int rc = rp_check(c, p, "bdpt_history_capture")) return rc;
-    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_history_capture: camera not set");
-    return rp_run(c, p, true, nullptr, nullptr, nullptr);
-}
-
-int bdpt_history_clear(bdpt_ctx* c) {
-    if (!c) return BDPT_EINVAL;
-    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_history_clear: multi-device contexts keep no history");
-    if (c->cpu) bdpt_cpu_history_clear(c->cpu);
-    c->has_hist = false;
-    return BDPT_OK;
-}
-
-int bdpt_history_info(const bdpt_ctx* c, int* present, bdpt_camera* camera) {
-    if (!c || c->multi) return BDPT_EINVAL;
-    if (present) *present = hist_present(c);
-    if (c->cpu) (void)bdpt_cpu_history_stored(c->cpu, camera);
-    else if (c->has_hist && camera) *camera = c->hist_cam;
-    return BDPT_OK;
-}
-
-int bdpt_history_read(bdpt_ctx* c, bdpt_vec* colors, float* weight) {
-    if (!c) return BDPT_EINVAL;
-    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_history_read: multi-device contexts keep no history");
-    if (!colors && !weight) return fail(c, BDPT_EINVAL, "bdpt_history_read: no output buffer");
-    if (!(c->cpu ? bdpt_cpu_history_stored(c->cpu, nullptr) : c->has_hist))
-        return fail(c, BDPT_ESTATE, "bdpt_history_read: no history");
-    if (c->cpu) {
-        bdpt_cpu_history_read(c->cpu, colors, weight);
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t np = (size_t)c->W * c->H;
-    hist_bufs b;
-    if (int rc = hist_alloc(c, &b)) return rc;
-    std::vector<float4> rec(np);
-    HIPCHK(c, hipMemcpyAsync(rec.data(), b.col[c->hist_cur], sizeof(float4) * np, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < np; i++) {
-        if (colors) colors[i] = {rec[i].x, rec[i].y, rec[i].z};
-        if (weight) weight[i] = rec[i].w;
-    }
-    return BDPT_OK;
-}
-
-int bdpt_history_write(bdpt_ctx* c, const bdpt_camera* camera, const bdpt_vec* colors, const float* weight) {
-    if (!c) return BDPT_EINVAL;
-    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_history_write: multi-device contexts keep no history");
-    if (!camera || !colors || !weight) return fail(c, BDPT_EINVAL, "bdpt_history_write: NULL argument");
-    if (c->cpu) {
-        bdpt_cpu_history_write(c->cpu, camera, colors, weight);
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t np = (size_t)c->W * c->H;
-    hist_bufs b;
-    if (int rc = hist_alloc(c, &b)) return rc;
-    if (int rc = join_fold(c)) return rc;
-    // staged in the result buffers, then packed with the guides rendered under `camera`
-    HIPCHK(c, hipMemcpyAsync(b.out3, colors, sizeof(bdpt_vec) * np, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b.weight, weight, sizeof(float) * np, hipMemcpyHostToDevice, c->stream));
-    bdpt_aov_args av;
-    bool bvh = false;
-    if (int rc = aov_launch(c, *camera, 0, 0, c->W, c->H, 0, 0u, &av, &bvh, nullptr, nullptr)) return rc;
-    hipLaunchKernelGGL(bdpt_history_pack_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream,
-                       (const int*)av.id, (const bdpt_dev_vec*)av.position, (const bdpt_dev_vec*)b.out3,
-                       (const float*)b.weight, b.guide[c->hist_cur], b.col[c->hist_cur], (int)np);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->has_hist = true;
-    c->hist_cam = *camera;
-    c->hist_spheres = c->spheres;
-    return BDPT_OK;
-}
-
-int bdpt_last_reproject_ms(bdpt_ctx* c, float* ms) {
-    if (!c || !ms) return BDPT_EINVAL;
-    if (!c->rp_ran) return fail(c, BDPT_ESTATE, "bdpt_last_reproject_ms: no frame reprojected");
-    if (c->cpu) {
-        *ms = c->rp_cpu_ms;
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipEventSynchronize(c->rp_ev[1]));
-    HIPCHK(c, hipEventElapsedTime(ms, c->rp_ev[0], c->rp_ev[1]));
-    return BDPT_OK;
-}
-
-// ---- the reprojected preview, denoised with per-pixel counts (include/bdpt.h
-// bdpt_preview_denoise) ----------------------------------------------------------
-// On the context's stream, after the last fold: bdpt_aov_kernel once, bdpt_reproject_kernel with
-// its {o, clampc(tot)} record going into the denoiser's ping buffer and the guide record into the
-// guide buffer (BDPT_PREVIEW_GUIDE=pack: bdpt_denoise_pack_kernel writes the guide records instead,
-// the alternative that was measured), then one count-aware level kernel per level, the last of
-// which writes the packed results into d_hist's result buffers; then the read-back.  levels == 0 is
-// the reprojection alone.  Only d_aov, d_dn and d_hist's result buffers are written.
-int bdpt_preview_denoise(bdpt_ctx* c, const bdpt_preview_params* p, bdpt_vec* colors_out, float* weight_out,
-                         unsigned char* rgba_out) {
-    if (!c) return BDPT_EINVAL;
-    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: multi-device contexts keep no history");
-    if (!p) return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: no parameters");
-    if (int rc = rp_check(c, &p->rp, "bdpt_preview_denoise")) return rc;
-    if (!colors_out && !weight_out && !rgba_out) return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: no output buffer");
-    if (p->levels < 0 || p->levels > 8) return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: levels %d outside 0..8", p->levels);
-    if (p->normal_power < 0 || p->normal_power > 6)
-        return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: normal_power %d outside 0..6", p->normal_power);
-    if (!(p->sigma_color > 0.f)) return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: sigma_color must be > 0");
-    if (!(p->count_ref > 0.f && p->count_ref < INFINITY))
-        return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: count_ref must be > 0 and finite");
-    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_preview_denoise: camera not set");
-    if (c->cpu) {
-        const auto t0 = std::chrono::steady_clock::now();
-        bdpt_cpu_preview_denoise(c->cpu, p, colors_out, weight_out, rgba_out);
-        c->pv_cpu_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        c->pv_ran = true;
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t np = (size_t)c->W * c->H;
-    hist_bufs b;
-    if (int rc = hist_alloc(c, &b)) return rc;
-    if (!c->d_dn && hipMalloc(&c->d_dn, 3 * sizeof(float4) * np) != hipSuccess) {
-        c->d_dn = nullptr;
-        return fail(c, BDPT_ENOMEM, "bdpt_preview_denoise: guide, ping and pong buffers (%zu B)", 3 * sizeof(float4) * np);
-    }
-    for (hipEvent_t& e : c->pv_ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
-    if (int rc = join_fold(c)) return rc;
-    HIPCHK(c, hipEventRecord(c->pv_ev[0], c->stream));
-    bdpt_aov_args av;
-    bool bvh = false;
-    if (int rc = aov_launch(c, c->cam, 0, 0, c->W, c->H, 0, 0u, &av, &bvh, nullptr, nullptr)) return rc;
-    float4 *guide = c->d_dn, *ping = c->d_dn + np, *pong = c->d_dn + 2 * np;
-    const dim3 block(256);
-    bdpt_reproject_args rv;
-    rp_args(c, &p->rp, av, b, &rv);
-    if (p->levels == 0) {
-        rv.out3 = colors_out ? b.out3 : nullptr;
-        rv.weight = weight_out ? b.weight : nullptr;
-        rv.rgba = rgba_out ? b.rgba : nullptr;
-    } else {
-        bool pack = false;
-        if (const char* e = getenv("BDPT_PREVIEW_GUIDE")) pack = strcmp(e, "pack") == 0;
-        if (pack) {
-            hipLaunchKernelGGL(bdpt_denoise_pack_kernel, dim3((unsigned)((np + 255) / 256)), block, 0, c->stream,
-                               (const int*)av.id, (const bdpt_dev_vec*)av.normal, (const bdpt_dev_vec*)nullptr,
-                               (const bdpt_dev_sphere*)c->d_sph, rv.all_materials, guide, (float4*)nullptr, (int)np);
-            HIPCHK(c, hipGetLastError());
-        } else {
-            rv.dn_guide = guide;
-        }
-        rv.next = ping;
-        rv.clamp_next = 1;
-    }
-    {
-        const int btw = rv.rows ? BDPT_RP_ROW_BTW : BDPT_RP_BTW, bth = rv.rows ? BDPT_RP_ROW_BTH : BDPT_RP_BTH;
-        const dim3 grid((unsigned)((c->W + btw - 1) / btw), (unsigned)((c->H + bth - 1) / bth), 1);
-        hipLaunchKernelGGL(bdpt_reproject_kernel, grid, block, 0, c->stream, rv);
-        HIPCHK(c, hipGetLastError());
-    }
-    bdpt_preview_args v;
-    memset(&v, 0, sizeof(v));
-    v.W = c->W; v.H = c->H;
-    v.guide = guide;
-    v.gamma_thr = c->d_thr;
-    v.c2 = 2.f / p->count_ref;
-    // tile shape and LDS staging: the denoiser's choices and switches
-    v.rows = 1;
-    bool lds = true;
-    if (const char* e = getenv("BDPT_DENOISE_TILE")) v.rows = atoi(e) == 64;
-    if (const char* e = getenv("BDPT_DENOISE_LDS")) lds = atoi(e) == 1;
-    const float isc0 = 1.0f / (p->sigma_color * p->sigma_color);
-    for (int k = 0; k < p->levels; k++) {
-        const bool last = k == p->levels - 1;
-        v.step = 1 << k;
-        v.isc = isc0 * (float)(1 << (2 * k));
-        v.cur = k % 2 ? pong : ping;
-        v.nxt = last ? nullptr : (k % 2 ? ping : pong);
-        v.out3 = last && colors_out ? b.out3 : nullptr;
-        v.weight = last && weight_out ? b.weight : nullptr;
-        v.rgba = last && rgba_out ? b.rgba : nullptr;
-        const bool staged = lds && v.step <= BDPT_DN_LDS_MAX_STEP;
-        const int btw = staged || !v.rows ? BDPT_DN_BTW : BDPT_DN_ROW_BTW;
-        const int bth = staged || !v.rows ? BDPT_DN_BTH : BDPT_DN_ROW_BTH;
-        const dim3 grid((unsigned)((c->W + btw - 1) / btw), (unsigned)((c->H + bth - 1) / bth), 1);
-        void* kargs[] = {&v};
-        HIPCHK(c, hipLaunchKernel(bdpt_preview_level_table[staged][p->normal_power], grid, block, kargs, 0, c->stream));
-    }
-    HIPCHK(c, hipEventRecord(c->pv_ev[1], c->stream));
-    c->pv_ran = true;
-    if (colors_out) HIPCHK(c, hipMemcpyAsync(colors_out, b.out3, sizeof(bdpt_vec) * np, hipMemcpyDeviceToHost, c->stream));
-    if (weight_out) HIPCHK(c, hipMemcpyAsync(weight_out, b.weight, sizeof(float) * np, hipMemcpyDeviceToHost, c->stream));
-    if (rgba_out) HIPCHK(c, hipMemcpyAsync(rgba_out, b.rgba, 4 * np, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return units_verdict(c);                                 // a frame known to be invalid is an error
-}
-
-int bdpt_last_preview_ms(bdpt_ctx* c, float* ms) {
-    if (!c || !ms) return BDPT_EINVAL;
-    if (!c->pv_ran) return fail(c, BDPT_ESTATE, "bdpt_last_preview_ms: no preview denoised");
-    if (c->cpu) {
-        *ms = c->pv_cpu_ms;
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipEventSynchronize(c->pv_ev[1]));
-    HIPCHK(c, hipEventElapsedTime(ms, c->pv_ev[0], c->pv_ev[1]));
-    return BDPT_OK;
-}
-
-// ---- per-tile noise estimate (include/bdpt.h bdpt_noise_estimate) ---------------
-// On the context's stream, after the last fold: bdpt_noise_kernel reads colours, counters and the
-// mark's records, writes the tile arrays (and the per-pixel plane, and with remark the records of
-// the pixels that take the mark); then the read-back, and the summary on the host.  Only d_mark and
-// d_noise are written; nothing of the path passes' state is touched.
-static int nz_check(bdpt_ctx* c, const char* who) {
-    if (!c) return BDPT_EINVAL;
-    if (c->multi) return fail(c, BDPT_EINVAL, "%s: multi-device contexts keep no mark", who);
-    return BDPT_OK;
-}
-
-static int mark_alloc(bdpt_ctx* c) {
-    if (c->d_mark) return BDPT_OK;
-    const size_t bytes = sizeof(uint4) * (size_t)c->W * c->H;
-    if (hipMalloc(&c->d_mark, bytes) != hipSuccess) {
-        c->d_mark = nullptr;
-        return fail(c, BDPT_ENOMEM, "bdpt_noise: mark records (%zu B)", bytes);
-    }
-    HIPCHK(c, hipMemsetAsync(c->d_mark, 0, bytes, c->stream));
-    c->mark_live = false;
-    return BDPT_OK;
-}
-
-int bdpt_noise_tiles(const bdpt_ctx* c, int* tiles_x, int* tiles_y) {
-    if (!c || c->multi) return BDPT_EINVAL;
-    if (tiles_x) *tiles_x = (c->W + BDPT_NOISE_TW - 1) / BDPT_NOISE_TW;
-    if (tiles_y) *tiles_y = (c->H + BDPT_NOISE_TH - 1) / BDPT_NOISE_TH;
-    return BDPT_OK;
-}
-
-int bdpt_noise_mark(bdpt_ctx* c) {
-    if (int rc = nz_check(c, "bdpt_noise_mark")) return rc;
-    if (c->cpu) {
-        bdpt_cpu_noise_mark(c->cpu);
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = mark_alloc(c)) return rc;
-    if (int rc = join_fold(c)) return rc;
-    const size_t np = (size_t)c->W * c->H;
-    hipLaunchKernelGGL(bdpt_noise_mark_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream,
-                       (const bdpt_dev_vec*)c->d_colors, (const unsigned*)c->d_counter, c->d_mark, (int)np);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->mark_live = true;
-    return units_verdict(c);                                 // a frame known to be invalid is an error
-}
-
-int bdpt_noise_clear(bdpt_ctx* c) {
-    if (int rc = nz_check(c, "bdpt_noise_clear")) return rc;
-    if (c->cpu) bdpt_cpu_noise_clear(c->cpu);
-    c->mark_live = false;
-    return BDPT_OK;
-}
-
-int bdpt_noise_read_mark(bdpt_ctx* c, bdpt_vec* colors, unsigned* counter) {
-    if (int rc = nz_check(c, "bdpt_noise_read_mark")) return rc;
-    if (!colors && !counter) return fail(c, BDPT_EINVAL, "bdpt_noise_read_mark: no output buffer");
-    if (!(c->cpu ? bdpt_cpu_noise_stored(c->cpu) : c->d_mark != nullptr))
-        return fail(c, BDPT_ESTATE, "bdpt_noise_read_mark: no mark was ever stored");
-    if (c->cpu) {
-        bdpt_cpu_noise_read_mark(c->cpu, colors, counter);
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t np = (size_t)c->W * c->H;
-    std::vector<uint4> rec(np);
-    HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_mark, sizeof(uint4) * np, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < np; i++) {
-        if (colors) memcpy(&colors[i], &rec[i], sizeof(bdpt_vec));
-        if (counter) counter[i] = c->mark_live ? rec[i].w : 0u;
-    }
-    return BDPT_OK;
-}
-
-int bdpt_noise_write_mark(bdpt_ctx* c, const bdpt_vec* colors, const unsigned* counter) {
-    if (int rc = nz_check(c, "bdpt_noise_write_mark")) return rc;
-    if (!colors || !counter) return fail(c, BDPT_EINVAL, "bdpt_noise_write_mark: NULL argument");
-    if (c->cpu) {
-        bdpt_cpu_noise_write_mark(c->cpu, colors, counter);
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = mark_alloc(c)) return rc;
-    const size_t np = (size_t)c->W * c->H;
-    std::vector<uint4> rec(np);
-    for (size_t i = 0; i < np; i++) {
-        memcpy(&rec[i], &colors[i], sizeof(bdpt_vec));
-        rec[i].w = counter[i];
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_mark, rec.data(), sizeof(uint4) * np, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->mark_live = true;
-    return BDPT_OK;
-}
-
-int bdpt_noise_estimate(bdpt_ctx* c, const bdpt_noise_params* p, float* error_out, float* tile_error,
-                        unsigned* tile_valid, bdpt_noise_summary* summary) {
-    if (int rc = nz_check(c, "bdpt_noise_estimate")) return rc;
-    if (!p) return fail(c, BDPT_EINVAL, "bdpt_noise_estimate: no parameters");
-    if (!(p->dark > 0.f)) return fail(c, BDPT_EINVAL, "bdpt_noise_estimate: dark must be > 0");
-    if (!(p->threshold >= 0.f)) return fail(c, BDPT_EINVAL, "bdpt_noise_estimate: threshold must be >= 0");
-    if (!error_out && !tile_error && !tile_valid && !summary)
-        return fail(c, BDPT_EINVAL, "bdpt_noise_estimate: no output buffer");
-    const size_t np = (size_t)c->W * c->H;
-    const int tx = (c->W + BDPT_NOISE_TW - 1) / BDPT_NOISE_TW, ty = (c->H + BDPT_NOISE_TH - 1) / BDPT_NOISE_TH;
-    const size_t nt = (size_t)tx * ty;
-    std::vector<float> S(nt), E(nt);
-    std::vector<unsigned> cv(nt), pend(nt);
-    if (c->cpu) {
-        const auto t0 = std::chrono::steady_clock::now();
-        bdpt_cpu_noise_estimate(c->cpu, p, error_out, S.data(), E.data(), cv.data(), pend.data());
-        c->nz_cpu_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    } else {
-        HIPCHK(c, hipSetDevice(c->device));
-        if (p->remark)
-            if (int rc = mark_alloc(c)) return rc;
-        const size_t bytes = sizeof(float) * (np + 4 * nt);
-        if (!c->d_noise && hipMalloc(&c->d_noise, bytes) != hipSuccess) {
-            c->d_noise = nullptr;
-            return fail(c, BDPT_ENOMEM, "bdpt_noise_estimate: result buffers (%zu B)", bytes);
-        }
-        for (hipEvent_t& e : c->nz_ev)
-            if (!e) HIPCHK(c, hipEventCreate(&e));
-        if (int rc = join_fold(c)) return rc;
-        bdpt_noise_args v;
-        memset(&v, 0, sizeof(v));
-        v.W = c->W; v.H = c->H; v.tiles_x = tx;
-        v.live = c->mark_live;
-        v.remark = p->remark != 0;
-        v.dark = p->dark;
-        v.colors = c->d_colors;
-        v.counter = c->d_counter;
-        v.mark = c->d_mark;
-        v.error = error_out ? c->d_noise : nullptr;
-        v.tile_sum = c->d_noise + np;
-        v.tile_error = v.tile_sum + nt;
-        v.tile_valid = (unsigned*)(v.tile_error + nt);
-        v.tile_pending = v.tile_valid + nt;
-        HIPCHK(c, hipEventRecord(c->nz_ev[0], c->stream));
-        hipLaunchKernelGGL(bdpt_noise_kernel, dim3((unsigned)tx, (unsigned)ty, 1), dim3(256), 0, c->stream, v);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(c->nz_ev[1], c->stream));
-        if (v.remark) c->mark_live = true;
-        if (error_out) HIPCHK(c, hipMemcpyAsync(error_out, v.error, sizeof(float) * np, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(S.data(), v.tile_sum, sizeof(float) * nt, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(E.data(), v.tile_error, sizeof(float) * nt, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(cv.data(), v.tile_valid, sizeof(unsigned) * nt, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(pend.data(), v.tile_pending, sizeof(unsigned) * nt, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (int rc = units_verdict(c)) return rc;             // a frame known to be invalid is an error
-    }
-    c->nz_ran = true;
-    if (tile_error) memcpy(tile_error, E.data(), sizeof(float) * nt);
-    if (tile_valid) memcpy(tile_valid, cv.data(), sizeof(unsigned) * nt);
-    if (summary) bdpt_noise_summarize(S.data(), E.data(), cv.data(), pend.data(), tx, ty, p->threshold, summary);
-    return BDPT_OK;
-}
-
-int bdpt_last_noise_ms(bdpt_ctx* c, float* ms) {
-    if (!c || !ms) return BDPT_EINVAL;
-    if (!c->nz_ran) return fail(c, BDPT_ESTATE, "bdpt_last_noise_ms: no estimate made");
-    if (c->cpu) {
-        *ms = c->nz_cpu_ms;
-        return BDPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipEventSynchronize(c->nz_ev[1]));
-    HIPCHK(c, hipEventElapsedTime(ms, c->nz_ev[0], c->nz_ev[1]));
-    return BDPT_OK;
 }
 
 // ---- checkpoint / resume of the accumulation ----------------------------------

@@ -156,3 +156,41 @@ def assert_non_interference(device, name, W, H, streams=None):
     for a, b, what in zip(got[0], got[1], ("colors", "counter", "pixels", "rand", "lightpaths")):
         assert np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8)), what
     assert (got[0][1] == 8).all()
+
+
+CLOCKS = ("aov", "denoise", "reproject", "preview", "noise")     # the bdpt_last_*_ms readers, by service
+
+
+def assert_only_own_clock_answers(device, service):
+    """A fresh context with a camera, a light pass and one path pass: no last_*_ms answers before a
+    service has run (BDPT_ESTATE); after `service` alone only its own reader does, >= 0 on the CPU
+    backend and > 0 on a GPU.  denoise / reproject / preview_denoise run the first-hit kernel
+    themselves but are not render_aov, so last_aov_ms stays unanswered after them."""
+    import pytest
+    cam, sp = scene("cornell", 20, 19)
+    sid, vlp = schedule(2)
+    calls = {"aov": lambda r: r.render_aov(), "denoise": lambda r: r.denoise(levels=2),
+             "reproject": lambda r: r.reproject(), "preview": lambda r: r.preview_denoise(levels=2),
+             "noise": lambda r: r.noise_estimate()}
+    assert set(calls) == set(CLOCKS)
+
+    def answering(r):
+        out = {}
+        for k in CLOCKS:
+            try:
+                out[k] = getattr(r, f"last_{k}_ms")()
+            except g.BdptError as e:
+                assert e.code == g._lib.BDPT_ESTATE, (k, e)
+        return out
+
+    with g.Renderer(sp, 20, 19, cam, device=device) as r:
+        r.light_pass(0)
+        r.path_passes(sid[:1], vlp[:1])
+        if service == "noise":                                          # an estimate measures against a mark
+            r.noise_mark()
+            r.path_passes(sid[1:], vlp[1:])
+        assert answering(r) == {}, "a reader answered before any service ran"
+        calls[service](r)
+        ms = answering(r)
+        assert list(ms) == [service], f"after {service} alone: {sorted(ms)} answer"
+        assert ms[service] >= 0.0 if device < 0 else ms[service] > 0.0, ms

@@ -3,7 +3,9 @@
 // `smallpt` calls, on the product's CPU backend (csrc/bdpt_cpu.cpp) only, so smallpt.c,
 // bdpt_util.c and bdpt_cpu.cpp can be built and run under AddressSanitizer + UBSan on a machine
 // without a GPU (GPU sanitizers are not available on the MI355X pool).  libbdpt.so's real layer
-// (csrc/bdpt_host.cpp) dispatches to the same bdpt_cpu_* functions for BDPT_DEVICE_CPU.
+// (csrc/bdpt_host.cpp, csrc/bdpt_frame.cpp) dispatches to the same bdpt_cpu_* functions for
+// BDPT_DEVICE_CPU.
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -132,3 +134,98 @@ int bdpt_write_radiance(bdpt_ctx* c, const bdpt_vec* col, const unsigned* cnt) {
 int bdpt__fail(bdpt_ctx* c, int code, const char* msg) { return fail(c, code, "%s", msg); }
 
 }  // extern "C"
+
+// ---- the frame services smallpt calls: --denoise, --reproject, --reproject --denoise, --until ----
+// The calls that clear the noise mark (bdpt_reset_accum, bdpt_set_scene, bdpt_set_camera,
+// bdpt_write_radiance) do so inside the CPU backend, so the entry points above need nothing for it.
+
+extern "C" int bdpt_denoise(bdpt_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out,
+                            unsigned char* rgba_out) {
+    if (!c) return BDPT_EINVAL;
+    if (!p || (!colors_out && !rgba_out) || p->levels < 1 || p->levels > 8 || p->normal_power < 0 ||
+        p->normal_power > 6 || !(p->sigma_color > 0.f) ||
+        (p->materials != BDPT_DENOISE_DIFFUSE && p->materials != BDPT_DENOISE_ALL))
+        return fail(c, BDPT_EINVAL, "bdpt_denoise: bad arguments");
+    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_denoise: camera not set");
+    bdpt_cpu_denoise(c->cpu, p, colors_out, rgba_out);
+    return BDPT_OK;
+}
+
+static int rp_check(bdpt_ctx* c, const bdpt_reproject_params* p) {
+    if (!p || (p->materials != BDPT_DENOISE_DIFFUSE && p->materials != BDPT_DENOISE_ALL) || !(p->max_history > 0.f) ||
+        !(p->plane_tol >= 0.f))
+        return fail(c, BDPT_EINVAL, "reprojection: bad parameters");
+    if (!c->cam_set) return fail(c, BDPT_ESTATE, "reprojection: camera not set");
+    return BDPT_OK;
+}
+
+extern "C" int bdpt_history_capture(bdpt_ctx* c, const bdpt_reproject_params* p) {
+    if (!c) return BDPT_EINVAL;
+    if (int rc = rp_check(c, p)) return rc;
+    bdpt_cpu_history_capture(c->cpu, p);
+    return BDPT_OK;
+}
+
+extern "C" int bdpt_history_clear(bdpt_ctx* c) {
+    if (!c) return BDPT_EINVAL;
+    bdpt_cpu_history_clear(c->cpu);
+    return BDPT_OK;
+}
+
+extern "C" int bdpt_reproject(bdpt_ctx* c, const bdpt_reproject_params* p, bdpt_vec* colors_out, float* weight_out,
+                              unsigned char* rgba_out) {
+    if (!c) return BDPT_EINVAL;
+    if (!colors_out && !weight_out && !rgba_out) return fail(c, BDPT_EINVAL, "bdpt_reproject: no output buffer");
+    if (int rc = rp_check(c, p)) return rc;
+    bdpt_cpu_reproject(c->cpu, p, colors_out, weight_out, rgba_out);
+    return BDPT_OK;
+}
+
+extern "C" int bdpt_preview_denoise(bdpt_ctx* c, const bdpt_preview_params* p, bdpt_vec* colors_out, float* weight_out,
+                                    unsigned char* rgba_out) {
+    if (!c) return BDPT_EINVAL;
+    if (!colors_out && !weight_out && !rgba_out) return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: no output buffer");
+    if (!p || p->levels < 0 || p->levels > 8 || p->normal_power < 0 || p->normal_power > 6 || !(p->sigma_color > 0.f) ||
+        !(p->count_ref > 0.f && p->count_ref < INFINITY))
+        return fail(c, BDPT_EINVAL, "bdpt_preview_denoise: bad parameters");
+    if (int rc = rp_check(c, &p->rp)) return rc;
+    bdpt_cpu_preview_denoise(c->cpu, p, colors_out, weight_out, rgba_out);
+    return BDPT_OK;
+}
+
+extern "C" int bdpt_noise_mark(bdpt_ctx* c) {
+    if (!c) return BDPT_EINVAL;
+    bdpt_cpu_noise_mark(c->cpu);
+    return BDPT_OK;
+}
+
+extern "C" int bdpt_noise_clear(bdpt_ctx* c) {
+    if (!c) return BDPT_EINVAL;
+    bdpt_cpu_noise_clear(c->cpu);
+    return BDPT_OK;
+}
+
+extern "C" int bdpt_noise_tiles(const bdpt_ctx* c, int* tiles_x, int* tiles_y) {
+    if (!c) return BDPT_EINVAL;
+    if (tiles_x) *tiles_x = (c->W + BDPT_NOISE_TW - 1) / BDPT_NOISE_TW;
+    if (tiles_y) *tiles_y = (c->H + BDPT_NOISE_TH - 1) / BDPT_NOISE_TH;
+    return BDPT_OK;
+}
+
+extern "C" int bdpt_noise_estimate(bdpt_ctx* c, const bdpt_noise_params* p, float* error_out, float* tile_error,
+                                   unsigned* tile_valid, bdpt_noise_summary* summary) {
+    if (!c) return BDPT_EINVAL;
+    if (!p || !(p->dark > 0.f) || !(p->threshold >= 0.f)) return fail(c, BDPT_EINVAL, "bdpt_noise_estimate: bad parameters");
+    if (!error_out && !tile_error && !tile_valid && !summary)
+        return fail(c, BDPT_EINVAL, "bdpt_noise_estimate: no output buffer");
+    int tx = 0, ty = 0;
+    bdpt_noise_tiles(c, &tx, &ty);
+    const size_t nt = (size_t)tx * ty;
+    std::vector<float> S(nt), E(nt);
+    std::vector<unsigned> cv(nt), pend(nt);
+    bdpt_cpu_noise_estimate(c->cpu, p, error_out, S.data(), E.data(), cv.data(), pend.data());
+    if (tile_error) memcpy(tile_error, E.data(), sizeof(float) * nt);
+    if (tile_valid) memcpy(tile_valid, cv.data(), sizeof(unsigned) * nt);
+    if (summary) bdpt_noise_summarize(S.data(), E.data(), cv.data(), pend.data(), tx, ty, p->threshold, summary);
+    return BDPT_OK;
+}

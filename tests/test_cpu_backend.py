@@ -264,3 +264,12 @@ def test_checkpoint_v1_refused_and_renderer_state_refreshed(rnd0, tmp_path):
     r2.load_checkpoint(str(tmp_path / "e.ckpt"))          # same scene again: upload skipped, same result
     same(r2.read_radiance()[0], before[0], "restored frame, scene unchanged")
     r2.close()
+
+
+@pytest.mark.parametrize("service", ["aov", "denoise", "reproject", "preview", "noise"])
+def test_only_the_service_that_ran_has_a_last_ms(service):
+    """The five bdpt_last_*_ms readers share one clock scaffold (csrc/bdpt_frame.cpp): one service's
+    call must not make another's reader answer."""
+    from aov_common import CLOCKS, assert_only_own_clock_answers
+    assert service in CLOCKS
+    assert_only_own_clock_answers(CPU, service)

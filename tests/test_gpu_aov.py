@@ -1,5 +1,6 @@
-"""First-hit feature buffers on the GPU (bdpt_aov_kernel, csrc/bdpt_kernels.hip): against the
-reference-written fixtures tests/golden/ref_aov_*.npz (the reference's colours of an all-emitter
+"""First-hit feature buffers on the GPU (bdpt_aov_kernel, csrc/bdpt_kernels.hip, launched by
+csrc/bdpt_frame.cpp): against the reference-written fixtures tests/golden/ref_aov_*.npz (the
+reference's colours of an all-emitter
 scene are e[id] * fabs(dp), tests/golden/make_ref_aov_golden.py), against the CPU backend on all six
 planes, against the path kernel of the same context, over windows, and for side effects.  Every
 comparison is on the float bits; no tolerance anywhere.  Sizes are not multiples of the kernel's
@@ -9,8 +10,9 @@ import numpy as np
 import pytest
 
 import gpu_bidirectional_raytracer_amd as g
-from aov_common import (CASES, assert_errors, assert_matches_reference, assert_non_interference,
-                        assert_window_slices, load_case, probe_colors, render_fixture, same, same_aov, scene)
+from aov_common import (CASES, CLOCKS, assert_errors, assert_matches_reference, assert_non_interference,
+                        assert_only_own_clock_answers, assert_window_slices, load_case, probe_colors,
+                        render_fixture, same, same_aov, scene)
 
 pytestmark = pytest.mark.gpu
 
@@ -107,3 +109,10 @@ def test_passes_after_render_aov_equal_passes_without_it(gpu, streams):
 
 def test_errors(gpu):
     assert_errors(gpu)
+
+
+@pytest.mark.parametrize("service", CLOCKS)
+def test_only_the_service_that_ran_has_a_last_ms(gpu, service):
+    """The five bdpt_last_*_ms readers share one clock scaffold (csrc/bdpt_frame.cpp): one service's
+    call must not make another's reader answer, and the one that ran measured a device interval."""
+    assert_only_own_clock_answers(gpu, service)

@@ -1,5 +1,5 @@
 """The edge-avoiding wavelet denoiser on the GPU (bdpt_denoise_pack_kernel and the level kernels,
-csrc/bdpt_kernels.hip) against the CPU backend -- which tests/test_denoise_cpu.py holds to the numpy
+csrc/bdpt_frame_kernels.h) against the CPU backend -- which tests/test_denoise_cpu.py holds to the numpy
 statement of the definition -- and against that statement directly.  Every comparison is on the
 float bits; no tolerance anywhere.  65x49, 40x33, 7x5 and 129x3 are no multiples of the 8x8 / 64x1
 wave tiles or the 32x8 / 64x4 workgroup tiles: every launch has partial tiles, all but 7x5 more than
@@ -19,7 +19,7 @@ CPU = -1
 # (scene, W, H, traversal of the guides)
 GPU_FRAMES = [(n, W, H, None) for n, W, H in FRAMES if n != "complex"] + [
     ("complex", 40, 33, "brute"), ("complex", 40, 33, "bvh"), ("cornell", 129, 3, None)]
-# (BDPT_DENOISE_TILE, BDPT_DENOISE_LDS): the kernel variants of csrc/bdpt_host.cpp bdpt_denoise
+# (BDPT_DENOISE_TILE, BDPT_DENOISE_LDS): the kernel variants of csrc/bdpt_frame.cpp run_levels
 VARIANTS = [("8", "0"), ("64", "0"), ("8", "1"), ("64", "1")]
 
 

@@ -1,5 +1,5 @@
 """The per-tile noise estimate on the GPU (bdpt_noise_kernel and bdpt_noise_mark_kernel,
-csrc/bdpt_kernels.hip) against the CPU backend -- which tests/test_noise_cpu.py holds to the numpy
+csrc/bdpt_frame_kernels.h) against the CPU backend -- which tests/test_noise_cpu.py holds to the numpy
 statement of the definition -- and against that statement directly.  Every comparison is on the
 bits; no tolerance anywhere.  No frame is larger than 65x49; 33x9, 65x49, 40x33, 7x5 and 129x3 are
 no multiples of the 32x8 tile, so their launches have partial tiles, 32x8 is exactly one workgroup,

@@ -1,5 +1,5 @@
 """The denoised preview on the GPU (bdpt_reproject_kernel writing the denoiser's records, then
-bdpt_preview_level_t / bdpt_preview_level_lds_t, csrc/bdpt_kernels.hip) against the CPU backend --
+bdpt_preview_level_t / bdpt_preview_level_lds_t, csrc/bdpt_frame_kernels.h) against the CPU backend --
 which tests/test_preview_denoise_cpu.py holds to the numpy statement of the definition -- and
 against that statement and the existing calls directly.  Every comparison is on the float bits; no
 tolerance anywhere.  No frame is larger than 65x49; 65x49, 40x33, 7x5 and 129x3 are no multiples of

@@ -1,5 +1,5 @@
 """Temporal reprojection on the GPU (bdpt_history_pack_kernel and bdpt_reproject_kernel,
-csrc/bdpt_kernels.hip) against the CPU backend -- which tests/test_reproject_cpu.py holds to the numpy
+csrc/bdpt_frame_kernels.h) against the CPU backend -- which tests/test_reproject_cpu.py holds to the numpy
 statement of the definition -- and against that statement directly.  Every comparison is on the
 float bits; no tolerance anywhere.  65x49, 40x33, 7x5 and 129x3 are no multiples of the 8x8 / 64x1
 wave tiles or the 32x8 / 64x4 workgroup tiles: every launch has partial tiles, all but 7x5 more than

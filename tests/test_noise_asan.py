@@ -31,7 +31,7 @@ def test_cpu_noise_estimate_under_asan():
 
 
 def test_smallpt_until_under_asan(tmp_path):
-    """The sanitized C host through its HIP-free context layer (tests/native/asan_cpu_abi_noise.cpp):
+    """The sanitized C host through its HIP-free context layer (tests/native/asan_cpu_abi.cpp):
     --until at the start and after a camera and a sphere key, whose re-initialisation clears the mark."""
     subprocess.check_call(["make", "-s", "-j4", "asan"], cwd=REPO, timeout=600)
     env = dict(os.environ, BDPT_CPU_THREADS="4", ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
