@@ -20,7 +20,8 @@ LIB      ?= $(PKG)/libbdpt.so
 HOST     := $(PKG)/smallpt
 ORACLE   := oracle/liboracle.so
 
-CHECKS   := tests/native/hw_exact_check tests/native/leaf_check tests/native/leaf_check_coarse
+CHECKS   := tests/native/hw_exact_check tests/native/leaf_check tests/native/leaf_check_coarse \
+            tests/native/plan_tiles_check
 
 all: $(LIB) $(HOST) $(ORACLE) $(CHECKS)
 
@@ -37,11 +38,20 @@ tests/native/leaf_check: $(LEAF_DEPS)
 tests/native/leaf_check_coarse: $(LEAF_DEPS)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -ffp-contract=off -pthread -DBDPT_SC_COARSE=1 -o $@ $<
 
+# the planner of masked path passes (host code only), run by tests/test_plan_tiles.py
+tests/native/plan_tiles_check: tests/native/plan_tiles_check.cpp $(CSRC)/bdpt_plan.h $(CSRC)/bdpt_device.h include/bdpt.h
+	$(HIPCC) -O1 -std=c++17 -o $@ $<
+
 $(BUILD):
 	mkdir -p $(BUILD)
 
 $(BUILD)/bdpt_kernels.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h $(CSRC)/bdpt_frame_kernels.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the same file once more for launches over a tile list (BDPT_TILES: only the generic and the BVH
+# instance of the path kernel with the tile-list code, bdpt_path_tiles_kernel_table)
+$(BUILD)/bdpt_kernels_tiles.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -DBDPT_TILES=1 -c $< -o $@
 
 # the path kernel's sources as strings, for scene-specialised kernels compiled at run time
 $(CSRC)/bdpt_jit_src.h: tools/embed_jit_sources.py $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h
@@ -66,7 +76,7 @@ $(BUILD)/bdpt_util.o: $(CSRC)/bdpt_util.c include/bdpt.h | $(BUILD)
 $(BUILD)/bdpt_ckpt.o: $(CSRC)/bdpt_ckpt.c include/bdpt.h | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(LIB): $(BUILD)/bdpt_kernels.o $(BUILD)/bdpt_host.o $(BUILD)/bdpt_frame.o $(BUILD)/bdpt_bvh.o $(BUILD)/bdpt_cpu.o $(BUILD)/bdpt_util.o $(BUILD)/bdpt_ckpt.o
+$(LIB): $(BUILD)/bdpt_kernels.o $(BUILD)/bdpt_host.o $(BUILD)/bdpt_frame.o $(BUILD)/bdpt_bvh.o $(BUILD)/bdpt_cpu.o $(BUILD)/bdpt_util.o $(BUILD)/bdpt_ckpt.o $(BUILD)/bdpt_kernels_tiles.o
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl
 
@@ -129,7 +139,7 @@ endif
 ASAN_FLAGS := -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -g -O1 -ffp-contract=off
 ASAN_DIR   := tests/native/_asan
 asan: $(ASAN_DIR)/smallpt_asan $(ASAN_DIR)/oracle_asan $(ASAN_DIR)/aov_asan $(ASAN_DIR)/denoise_asan $(ASAN_DIR)/reproject_asan \
-      $(ASAN_DIR)/preview_asan $(ASAN_DIR)/noise_asan
+      $(ASAN_DIR)/preview_asan $(ASAN_DIR)/noise_asan $(ASAN_DIR)/tiles_asan
 
 $(ASAN_DIR):
 	mkdir -p $(ASAN_DIR)
@@ -176,6 +186,10 @@ $(ASAN_DIR)/preview_asan: tests/native/preview_asan.cpp $(CSRC)/bdpt_cpu.h inclu
 
 # the CPU backend's noise estimate (bdpt_cpu_noise_*) driven directly; tests/test_noise_asan.py
 $(ASAN_DIR)/noise_asan: tests/native/noise_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
+	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
+
+# the CPU backend's masked path passes (bdpt_cpu_path_passes with a tile mask) driven directly; tests/test_tiles_asan.py
+$(ASAN_DIR)/tiles_asan: tests/native/tiles_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
 	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
 
 clean:

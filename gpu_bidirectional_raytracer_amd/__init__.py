@@ -309,13 +309,28 @@ class Renderer:
     def light_pass(self, current_sample: int = 0) -> None:
         self._chk(lib.bdpt_light_pass(self._h, current_sample))
 
-    def path_passes(self, sid: Sequence[int], vlp: Sequence[int], sync: bool = True) -> None:
+    def path_passes(self, sid: Sequence[int], vlp: Sequence[int], sync: bool = True, tiles=None) -> None:
+        """tiles: a [tiles_y, tiles_x] bool or uint8 array over the 32 x 8 tiles of noise_tiles();
+        only the pixels of tiles with a non-zero entry are rendered, every other pixel keeps its
+        state bit for bit (bdpt_path_passes_tiles).  None: every pixel."""
         sid = np.ascontiguousarray(sid, dtype=np.uint32)
         vlp = np.ascontiguousarray(vlp, dtype=np.int32)
         assert sid.shape == vlp.shape and sid.ndim == 1
-        self._chk(lib.bdpt_path_passes(self._h, _ptr(sid), _ptr(vlp), len(sid)))
+        if tiles is None:
+            self._chk(lib.bdpt_path_passes(self._h, _ptr(sid), _ptr(vlp), len(sid)))
+        else:
+            mask = self._tile_mask(tiles)
+            self._chk(lib.bdpt_path_passes_tiles(self._h, _ptr(sid), _ptr(vlp), len(sid), _ptr(mask)))
         if sync:
             self.synchronize()
+
+    def _tile_mask(self, tiles) -> np.ndarray:
+        """`tiles` as the contiguous uint8 [tiles_y, tiles_x] mask the C-ABI takes (non-zero -> 1)."""
+        mask = np.ascontiguousarray(np.asarray(tiles) != 0, dtype=np.uint8)
+        ty, tx = -(-self.height // 8), -(-self.width // 32)
+        if mask.shape != (ty, tx):
+            raise ValueError(f"tiles must have shape {(ty, tx)} (tiles_y, tiles_x), not {mask.shape}")
+        return mask
 
     def synchronize(self) -> None:
         self._chk(lib.bdpt_synchronize(self._h))
@@ -630,6 +645,14 @@ class Renderer:
             out["error"] = err
         return out
 
+    def noise_tile_pending(self) -> np.ndarray:
+        """The last noise_estimate's pending pixels per tile, [tiles_y, tiles_x] uint32: pixels with
+        0 < count < 30000 that are not valid yet (their sum is the summary's pending_pixels)."""
+        tx, ty = self.noise_tiles()
+        tp = np.empty((ty, tx), np.uint32)
+        self._chk(lib.bdpt_noise_tile_pending(self._h, _ptr(tp)))
+        return tp
+
     def last_noise_ms(self) -> float:
         """Device time (ms) of the last noise_estimate call's kernel alone."""
         ms = ctypes.c_float()
@@ -709,25 +732,36 @@ class SmallPT:
         self.renderer.light_pass(self.current_sample)
         self.sched.light()
 
-    def UpdateRendering(self, npass: int = 1) -> float:      # smallpt_cpu.c:265-297 (x npass)
+    def UpdateRendering(self, npass: int = 1, tiles=None) -> float:   # smallpt_cpu.c:265-297 (x npass)
+        """tiles (no reference counterpart): render only these 32 x 8 tiles (Renderer.path_passes);
+        the pass schedule and current_sample advance by npass either way, and the returned samples
+        per second count the masked tiles' pixels inside the frame."""
         import time
         sid, vlp = self.sched.next(npass)
         t0 = time.perf_counter()
-        self.renderer.path_passes(sid, vlp)
+        self.renderer.path_passes(sid, vlp, tiles=tiles)
         dt = time.perf_counter() - t0
         self.current_sample += npass
         # static float total_time; total_time += (float)elapsed (smallpt_cpu.c:35,283)
         self.total_time = float(np.float32(np.float32(self.total_time) + np.float32(dt)))
-        return self.width * self.height * npass / dt if dt > 0 else float("inf")
+        npix = self.width * self.height if tiles is None else self.tile_pixels(tiles)
+        return npix * npass / dt if dt > 0 else float("inf")
 
-    def IdleFunc(self, npass: int = 1) -> None:              # display_func.c:192-217
+    def tile_pixels(self, tiles) -> int:
+        """The pixels inside the frame of the 32 x 8 tiles with a non-zero entry in `tiles`."""
+        mask = self.renderer._tile_mask(tiles).astype(bool)
+        w = np.minimum(32, self.width - 32 * np.arange(mask.shape[1]))
+        h = np.minimum(8, self.height - 8 * np.arange(mask.shape[0]))
+        return int((np.outer(h, w) * mask).sum())
+
+    def IdleFunc(self, npass: int = 1, tiles=None) -> None:  # display_func.c:192-217
         if self.flag == 1:
             self.UpdateRendering2()
         if self.flag > 1:
-            self.UpdateRendering(npass)
+            self.UpdateRendering(npass, tiles)
 
     def RenderUntil(self, threshold: float = 0.05, max_passes: int = 4096, batch: int = 8,
-                    dark: float = 0.01, pixels: bool = False) -> dict:
+                    dark: float = 0.01, pixels: bool = False, adaptive: bool = False, min_passes: int = 0) -> dict:
         """Render until the frame is good enough instead of a fixed number of passes (no reference
         counterpart): IdleFunc(batch), then Renderer.noise_estimate(remark=True), repeated.  Stops
         as converged when some pixel is valid, none is pending and no tile's error is over
@@ -735,9 +769,23 @@ class SmallPT:
         estimate's dict (pixels=True: with its per-pixel `error`) with `passes` (current_sample)
         and `converged`.  The frame is exactly what
         the same IdleFunc(batch) calls render.  ReInit and ReInitScene clear the mark through the
-        calls they make."""
+        calls they make.
+
+        adaptive=True stops each 32 x 8 tile on its own instead of rendering every pixel until the
+        worst tile is good enough: IdleFunc(batch, tiles=the tiles not retired), the estimate, and
+        then every tile not yet retired retires if none of its pixels is pending, its error is at
+        most `threshold` (or it has no valid pixel: nothing in it is being sampled) and
+        current_sample >= min_passes.  A retired tile stays retired: it is not rendered again, so
+        its pixels hold what the unmasked frame held after retired_at passes.  Stops as converged
+        when every tile is retired.  The dict then also carries retired_at (int32, the
+        current_sample a tile retired at, 0: not retired), retired_error (float32, its error then)
+        and pixel_passes (the sum over batches of batch x pixels rendered).  The frame is noisier
+        than the unmasked one at the same stop: that one oversamples the easy tiles (DESIGN.md 4h;
+        min_passes guards tiles that look settled after very few passes)."""
         if batch < 1:
             raise ValueError("batch must be >= 1")
+        if adaptive:
+            return self._render_until_adaptive(threshold, max_passes, batch, dark, pixels, min_passes)
         while True:
             self.IdleFunc(batch)
             est = self.renderer.noise_estimate(dark=dark, threshold=threshold, remark=True, pixels=pixels)
@@ -746,6 +794,30 @@ class SmallPT:
                 break
         est["passes"] = self.current_sample
         est["converged"] = bool(converged)
+        return est
+
+    def _render_until_adaptive(self, threshold, max_passes, batch, dark, pixels, min_passes) -> dict:
+        tx, ty = self.renderer.noise_tiles()
+        retired_at = np.zeros((ty, tx), np.int32)
+        retired_error = np.zeros((ty, tx), np.float32)
+        pixel_passes = 0
+        while True:
+            live = retired_at == 0
+            first = self.current_sample
+            self.IdleFunc(batch, tiles=live)
+            pixel_passes += (self.current_sample - first) * self.tile_pixels(live)
+            est = self.renderer.noise_estimate(dark=dark, threshold=threshold, remark=True, pixels=pixels)
+            pending = self.renderer.noise_tile_pending()
+            settled = (est["tile_valid"] == 0) | (est["tile_error"] <= np.float32(threshold))
+            retire = live & (pending == 0) & settled & (self.current_sample >= min_passes)
+            retired_at[retire] = self.current_sample
+            retired_error[retire] = est["tile_error"][retire]
+            converged = bool((retired_at != 0).all())
+            if converged or self.current_sample >= max_passes:
+                break
+        est["passes"] = self.current_sample
+        est["converged"] = converged
+        est["retired_at"], est["retired_error"], est["pixel_passes"] = retired_at, retired_error, int(pixel_passes)
         return est
 
     def ReInit(self, realloc: bool = True) -> None:          # smallpt_cpu.c:373-387

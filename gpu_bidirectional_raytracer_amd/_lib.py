@@ -22,7 +22,7 @@ DIFF, SPEC, REFR, LITE = 0, 1, 2, 3
 KEY_UP, KEY_DOWN, KEY_LEFT, KEY_RIGHT, KEY_PAGE_UP, KEY_PAGE_DOWN = range(0x101, 0x107)
 CHOICES = {1: "decided", 2: "fused", 4: "paired", 8: "quarter", 16: "pools", 32: "units"}   # BDPT_CHOICE_*
 FEATURES = {1: "specialized", 2: "det_skip", 4: "zero_exit", 8: "last_skip", 16: "bvh", 32: "pass_streams",
-            64: "pixel_pools", 128: "unit_fold", 256: "sincos_planes", 512: "sample_records"}
+            64: "pixel_pools", 128: "unit_fold", 256: "sincos_planes", 512: "sample_records", 1024: "tile_list"}
 
 
 class Vec(ctypes.Structure):
@@ -140,6 +140,7 @@ _SIGS = [
     ("bdpt_light_pass", ctypes.c_int, [_P, ctypes.c_int]),
     ("bdpt_generate_rand", ctypes.c_int, [_P, ctypes.c_uint]),
     ("bdpt_path_passes", ctypes.c_int, [_P, _P, _P, ctypes.c_int]),
+    ("bdpt_path_passes_tiles", ctypes.c_int, [_P, _P, _P, ctypes.c_int, _P]),
     ("bdpt_synchronize", ctypes.c_int, [_P]),
     ("bdpt_last_path_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_path_timing", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double),
@@ -179,6 +180,7 @@ _SIGS = [
     ("bdpt_noise_read_mark", ctypes.c_int, [_P, _P, _P]),
     ("bdpt_noise_write_mark", ctypes.c_int, [_P, _P, _P]),
     ("bdpt_noise_estimate", ctypes.c_int, [_P, ctypes.POINTER(NoiseParams), _P, _P, _P, ctypes.POINTER(NoiseSummary)]),
+    ("bdpt_noise_tile_pending", ctypes.c_int, [_P, _P]),
     ("bdpt_last_noise_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_gl_register_pbo", ctypes.c_int, [_P, ctypes.c_uint]),
     ("bdpt_gl_publish", ctypes.c_int, [_P]),

@@ -167,6 +167,7 @@ struct bdpt_cpu_ctx {
     // first use; empty while no mark was ever stored
     struct NoiseMark { bdpt_vec c; unsigned n; };
     std::vector<NoiseMark> mark;
+    std::vector<unsigned> last_pending;   // per tile, of the last estimate (empty: none made yet)
 };
 
 extern "C" void bdpt_gamma_thresholds(float thr[256]);
@@ -418,13 +419,21 @@ struct PathTracer {
 }  // namespace
 
 // npass x UpdateRendering (smallpt_cpu.c:265-297): each pixel of this context's shard renders its
-// passes in order with the running mean of device.cu:774-787.
-void bdpt_cpu_path_passes(bdpt_cpu_ctx* c, const unsigned* sid, const int* vlp, int npass) {
+// passes in order with the running mean of device.cu:774-787.  With a tile mask, only the pixels of
+// the 32 x 8 tiles (anchored at (0, 0), row-major) whose byte is non-zero; the others are not touched.
+void bdpt_cpu_path_passes(bdpt_cpu_ctx* c, const unsigned* sid, const int* vlp, int npass,
+                          const unsigned char* tile_mask) {
     const PathTracer pt(c);
     const int W = c->W;
+    const int tiles_x = (W + BDPT_NOISE_TW - 1) / BDPT_NOISE_TW;
     parallel_rows(0, c->H, c->threads, [&](int y) {
         if (c->nshards > 1 && (y / c->band_rows) % c->nshards != c->shard) return;
+        const unsigned char* row = tile_mask ? tile_mask + (size_t)(y / BDPT_NOISE_TH) * tiles_x : nullptr;
         for (int x = 0; x < W; x++) {
+            if (row && !row[x / BDPT_NOISE_TW]) {
+                x = (x / BDPT_NOISE_TW + 1) * BDPT_NOISE_TW - 1;      // on to the next tile
+                continue;
+            }
             const size_t i = (size_t)y * W + x;
             bdpt_vec col = c->colors[i];
             unsigned cnt = c->counter[i];
@@ -886,6 +895,7 @@ void bdpt_cpu_noise_estimate(bdpt_cpu_ctx* c, const bdpt_noise_params* p, float*
     const int tx = (W + BDPT_NOISE_TW - 1) / BDPT_NOISE_TW, ty = (H + BDPT_NOISE_TH - 1) / BDPT_NOISE_TH;
     if (p->remark && c->mark.empty()) c->mark.assign((size_t)W * H, {bdpt_vec{0.f, 0.f, 0.f}, 0u});
     const bool stored = !c->mark.empty();
+    c->last_pending.assign((size_t)tx * ty, 0u);
     for (int by = 0; by < ty; by++)
         for (int bx = 0; bx < tx; bx++) {
             float v[BDPT_NOISE_TW * BDPT_NOISE_TH];
@@ -925,7 +935,13 @@ void bdpt_cpu_noise_estimate(bdpt_cpu_ctx* c, const bdpt_noise_params* p, float*
             if (tile_error) tile_error[t] = valid ? v[0] / (float)valid : 0.f;
             if (tile_valid) tile_valid[t] = valid;
             if (tile_pending) tile_pending[t] = pending;
+            c->last_pending[t] = pending;
         }
+}
+bool bdpt_cpu_noise_tile_pending(const bdpt_cpu_ctx* c, unsigned* tile_pending) {
+    if (c->last_pending.empty()) return false;
+    memcpy(tile_pending, c->last_pending.data(), sizeof(unsigned) * c->last_pending.size());
+    return true;
 }
 
 // The frame's summary from the tile arrays in row-major order: the one statement of it, shared by

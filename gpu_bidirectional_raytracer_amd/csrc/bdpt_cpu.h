@@ -18,7 +18,10 @@ void bdpt_cpu_set_shard(bdpt_cpu_ctx* c, int shard, int nshards, int band_rows);
 int bdpt_cpu_threads(const bdpt_cpu_ctx* c);
 void bdpt_cpu_generate_rand(bdpt_cpu_ctx* c, unsigned seed);
 void bdpt_cpu_light_pass(bdpt_cpu_ctx* c, int current_sample);
-void bdpt_cpu_path_passes(bdpt_cpu_ctx* c, const unsigned* sid, const int* vlp, int npass);
+// tile_mask (include/bdpt.h bdpt_path_passes_tiles): one byte per BDPT_NOISE_TW x BDPT_NOISE_TH tile,
+// row-major; only pixels of tiles with a non-zero byte are rendered.  nullptr: every pixel.
+void bdpt_cpu_path_passes(bdpt_cpu_ctx* c, const unsigned* sid, const int* vlp, int npass,
+                          const unsigned char* tile_mask = nullptr);
 void bdpt_cpu_render_aov(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid,
                          const bdpt_aov_buffers* out);
 void bdpt_cpu_denoise(const bdpt_cpu_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out,
@@ -45,6 +48,8 @@ void bdpt_cpu_noise_read_mark(const bdpt_cpu_ctx* c, bdpt_vec* colors, unsigned*
 void bdpt_cpu_noise_write_mark(bdpt_cpu_ctx* c, const bdpt_vec* colors, const unsigned* counter);
 void bdpt_cpu_noise_estimate(bdpt_cpu_ctx* c, const bdpt_noise_params* p, float* error_out, float* tile_sum,
                              float* tile_error, unsigned* tile_valid, unsigned* tile_pending);
+// the last estimate's pending count per tile (bdpt_noise_tile_pending); false before the first estimate
+bool bdpt_cpu_noise_tile_pending(const bdpt_cpu_ctx* c, unsigned* tile_pending);
 // the frame's summary from the tile arrays: host code shared by both backends
 void bdpt_noise_summarize(const float* tile_sum, const float* tile_error, const unsigned* tile_valid,
                           const unsigned* tile_pending, int tiles_x, int tiles_y, float threshold,

@@ -58,6 +58,7 @@ struct bdpt_ctx {
         int launches = 0;
         bool pending = false;                      // issued, not folded yet
         bool serial_fold = false;                  // its folds ran after its path kernels, in-stream
+        std::vector<unsigned> tiles;               // a masked call's tile list while its upload may be pending
     } ring[kRing];
     long long issued = 0, folded = 0;   // calls issued / folded into the accumulators
     double acc_ms = 0.0;         // accumulated device time of finished path-pass calls
@@ -95,6 +96,10 @@ struct bdpt_ctx {
     unsigned* d_uflags = nullptr;       // ordered in-kernel fold (units): per 8x8 wave tile, epoch << 8 | range
     size_t uflags_cap = 0;
     unsigned uepoch = 0;                // launches of the units kernel (flag tags)
+    // bdpt_path_passes_tiles: the tile list of the last masked call (one buffer: a masked call joins
+    // the outstanding fold, the list's other reader, before it uploads its own list on `stream`)
+    unsigned* d_tiles = nullptr;
+    size_t tiles_cap = 0;
     unsigned* d_uerr = nullptr;         // set by a unit whose handover wait timed out
     bool units_check = false;           // a units launch ran since the last error check
     int traversal = BDPT_TRAVERSE_AUTO; // bdpt_set_traversal
@@ -144,7 +149,7 @@ struct bdpt_ctx {
         hipFunction_t fn = nullptr;
         int waves = 0;
         std::string flags, err;
-    } jit_memo[4][2];
+    } jit_memo[6][2];                   // ([4], [5]: the fused and pass-stream builds for tile lists)
     int last_features = 0;              // BDPT_FEAT_* of the last path-pass launch
     unsigned rand_seed = 0;             // seed of the current MT607 table (rand_ready)
     char err[512] = {0};
@@ -189,6 +194,7 @@ struct bdpt_ctx {
     uint4* d_mark = nullptr;
     bool mark_live = false;
     float* d_noise = nullptr;
+    std::vector<unsigned> noise_pending;   // per tile, of the last estimate (bdpt_noise_tile_pending); empty: none yet
     unsigned gl_pbo = 0;
 };
 enum { kReduceNone = 0, kReduceRccl = 1, kReducePeer = 2 };

@@ -135,6 +135,12 @@ struct bdpt_path_args {
     unsigned* unit_err;             // non-zero: a handover wait timed out (ordering violated)
     unsigned* unit_ctr;             // per XCD queue: units claimed (8 counters, 128 B apart, zeroed per launch)
     int unit_taper;                 // 1: the launch's last unit_passes passes in halving ranges
+    // Tile list (bdpt_path_passes_tiles; not pools, not units): workgroup b of the launch's x
+    // dimension renders tile tile_list[b] of the gx x gy tile grid (row-major), and the launch's
+    // pixel b * 256 + slot is that tile's slot (bdpt_dev_list_* below), inside the frame or
+    // not: nloc = 256 * ntiles.  nullptr: the grid enumerates every tile itself.
+    const unsigned* tile_list;
+    int ntiles;
 };
 
 // First-hit feature buffers (bdpt_aov_kernel; include/bdpt.h bdpt_render_aov): the window, the
@@ -306,6 +312,21 @@ __device__ __forceinline__ int bdpt_dev_tile_row(const bdpt_path_args& a, int by
     if (a.tiles_per_band == 1) return a.shard + by * a.nshards;   // 8-row bands (the default)
     const int k = by / a.tiles_per_band, sub = by - k * a.tiles_per_band;
     return (a.shard + k * a.nshards) * a.tiles_per_band + sub;
+}
+
+// Launch-local pixel index under a tile list (bdpt_path_args::tile_list), the one statement of it:
+// list entry b is tile (bx, by), and its pixel (x, y) is the launch's pixel
+//   b * 256 + (y - by * BDPT_BTH) * BDPT_BTW + (x - bx * BDPT_BTW)
+// -- the tile's 256 slots row-major, whether inside the frame or not.  The path kernel forms it as
+// (y - row0) * BDPT_BTW + x with the wave-uniform row0 = bdpt_dev_list_row0(b, bx, by), the shape
+// of its index without a list, (y - yoff) * W + x; the fold inverts it with bdpt_dev_list_pixel.
+static_assert(BDPT_BTW * BDPT_BTH == 256, "a workgroup tile is 256 pixels");
+__host__ __device__ __forceinline__ int bdpt_dev_list_row0(int b, int bx, int by) {
+    return (by - b) * BDPT_BTH + bx;          // BTW * ((b - by) * BTH - bx) = b * 256 - by * BTH * BTW - bx * BTW
+}
+__host__ __device__ __forceinline__ void bdpt_dev_list_pixel(int bx, int by, int slot, int* x, int* y) {
+    *x = bx * BDPT_BTW + slot % BDPT_BTW;
+    *y = by * BDPT_BTH + slot / BDPT_BTW;
 }
 
 // toInt (vec.h:34) by threshold search: thr[k] is the smallest float whose toInt is >= k,

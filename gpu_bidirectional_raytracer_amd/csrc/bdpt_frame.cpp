@@ -723,7 +723,16 @@ int bdpt_noise_estimate(bdpt_ctx* c, const bdpt_noise_params* p, float* error_ou
     }
     if (tile_error) memcpy(tile_error, E, sizeof(float) * nt);
     if (tile_valid) memcpy(tile_valid, cv, sizeof(unsigned) * nt);
+    c->noise_pending.assign(pend, pend + nt);
     if (summary) bdpt_noise_summarize(S, E, cv, pend, tx, ty, p->threshold, summary);
+    return BDPT_OK;
+}
+
+int bdpt_noise_tile_pending(bdpt_ctx* c, unsigned* tile_pending) {
+    if (int rc = nz_check(c, "bdpt_noise_tile_pending")) return rc;
+    if (!tile_pending) return fail(c, BDPT_EINVAL, "bdpt_noise_tile_pending: no output buffer");
+    if (c->noise_pending.empty()) return fail(c, BDPT_ESTATE, "bdpt_noise_tile_pending: no estimate made");
+    memcpy(tile_pending, c->noise_pending.data(), sizeof(unsigned) * c->noise_pending.size());
     return BDPT_OK;
 }
 

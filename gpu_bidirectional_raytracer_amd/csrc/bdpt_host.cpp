@@ -49,6 +49,7 @@ extern "C" __global__ void bdpt_sincos_planar_kernel(const float*, float2*);
 extern "C" __global__ void bdpt_sample_records_kernel(const float*, float4*);
 extern "C" __global__ void bdpt_light_kernel(const bdpt_dev_sphere*, unsigned, const float*, int,
                                              bdpt_dev_lightpath*);
+extern "C" const void* bdpt_path_tiles_kernel_table[4];   // launches over a tile list: [(S > 1) * 2 + BVH]
 extern "C" const void* bdpt_path_kernel_table[36];   // [(S > 1) * 18 + (BVH ? 17 : n <= 16 ? n : 0)]
 extern "C" __global__ void bdpt_pixels_kernel(const bdpt_dev_vec*, uchar4*, const float*, int);
 extern "C" __global__ void bdpt_accum_kernel(bdpt_path_args);
@@ -167,7 +168,7 @@ static void release(bdpt_ctx* c) {
                     c->d_counter, c->d_pixels, c->d_thr, c->d_rbuf, c->d_rmask, c->d_poolctr, c->d_uflags, c->d_uerr, c->d_bvh_nodes,
                     c->d_bvh_geom, c->d_big_geom, c->d_mat, c->d_bvh_ids, c->d_big_ids,
                     c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc, c->d_aov, c->d_dn, c->d_hist,
-                    c->d_mark, c->d_noise};
+                    c->d_mark, c->d_noise, c->d_tiles};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (const bdpt_svc_clock& k : c->svc)
@@ -442,7 +443,7 @@ static bdpt_path_env path_env() {
     return e;
 }
 
-static hipFunction_t jit_path_kernel_build(bdpt_ctx* c, bool streams, bool pair, bool pool, bool units) {
+static hipFunction_t jit_path_kernel_build(bdpt_ctx* c, bool streams, bool pair, bool pool, bool units, bool tiles) {
     const unsigned n = (unsigned)c->spheres.size();
     if (!c->specialize || n < 1 || n > 64) return nullptr;          // kJitEmis is 64 bits
     unsigned long long emis = 0;
@@ -469,7 +470,9 @@ static hipFunction_t jit_path_kernel_build(bdpt_ctx* c, bool streams, bool pair,
     // caustic8 measured 0.6 % slower than 5 waves with the 4-KB table; fused_max_passes()).
     const char* wenv = getenv(streams ? "BDPT_JIT_WAVES" : "BDPT_JIT_FUSED_WAVES");
     int waves = wenv ? atoi(wenv) : (streams ? 6 : 5);
-    const std::string name = "&bdpt_path_kernel_t<" + std::to_string(n) + (streams ? ", true>" : ", false>");
+    // (a launch over a tile list runs the instance with the tile-list code, bdpt_kernels.hip)
+    const std::string name = std::string(tiles ? "&bdpt_path_tiles_kernel_t<" : "&bdpt_path_kernel_t<") + std::to_string(n) +
+                             (streams ? ", true>" : ", false>");   // (BDPT_TILES=1 below gives the kernel that name)
     const char* jflags = getenv("BDPT_JIT_FLAGS");
     const bool user_coarse = jflags && strstr(jflags, "BDPT_SC_COARSE");   // experiments decide
     bool coarse = false, pf_off = false;
@@ -485,6 +488,7 @@ static hipFunction_t jit_path_kernel_build(bdpt_ctx* c, bool streams, bool pair,
         if (!streams && !pair) all.push_back("-DBDPT_RNG_PAIR=0");
         if (streams && pool) all.push_back("-DBDPT_POOL=1");
         if (streams && units) all.push_back("-DBDPT_UNITS=1");
+        if (tiles) all.push_back("-DBDPT_TILES=1");
         // VLP-only part-full shadow rounds over the non-emitters' list (BDPT_VAC_LIST): only where
         // dropping the emitters saves a lane-group iteration (cornell: 8 of 9 spheres fit 4, 2, 1
         // iterations instead of 5, 3, 2); elsewhere the staging costs (synthetic64 -0.4 %,
@@ -572,15 +576,15 @@ static std::string jit_env_key() {
 }
 
 static hipFunction_t jit_path_kernel(bdpt_ctx* c, bool streams, bool pair = true, bool pool = false,
-                                     bool units = false) {
+                                     bool units = false, bool tiles = false) {
     const std::string key = jit_env_key();
-    bdpt_ctx::jit_memo_t& m = c->jit_memo[streams ? (units ? 3 : pool ? 2 : 1) : 0][pair];
+    bdpt_ctx::jit_memo_t& m = c->jit_memo[tiles ? (streams ? 5 : 4) : streams ? (units ? 3 : pool ? 2 : 1) : 0][pair];
     if (m.valid && m.flags == key) {
         snprintf(c->jit_err, sizeof c->jit_err, "%s", m.err.c_str());
         if (m.fn) { c->jit_waves = m.waves; c->jit_zero_exit = m.zero_exit; }
         return m.fn;
     }
-    hipFunction_t fn = jit_path_kernel_build(c, streams, pair, streams && pool, streams && units);
+    hipFunction_t fn = jit_path_kernel_build(c, streams, pair, streams && pool, streams && units, tiles);
     m.valid = true;
     m.fn = fn;
     m.waves = c->jit_waves;
@@ -999,9 +1003,9 @@ static void camera_args(const bdpt_ctx* c, bdpt_path_args& a) { camera_args(c, c
 // ---- bdpt_path_passes: the steps of one call, in the order one_path_passes runs them.  What a
 // call launches is decided in bdpt_plan.h; the functions below issue it. ----
 
-static int cpu_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int npass) {
+static int cpu_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int npass, const unsigned char* mask) {
     const auto t0 = std::chrono::steady_clock::now();       // synchronous; wall-clock timing
-    bdpt_cpu_path_passes(c->cpu, sid, vlp, npass);
+    bdpt_cpu_path_passes(c->cpu, sid, vlp, npass, mask);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c->last_ms = (float)ms;
     c->acc_ms += ms;
@@ -1010,7 +1014,7 @@ static int cpu_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int
     c->last_streams = 1;
     c->last_specialized = false;
     c->last_bvh = false;
-    c->last_features = 0;
+    c->last_features = mask ? BDPT_FEAT_TILES : 0;
     return BDPT_OK;
 }
 
@@ -1058,6 +1062,8 @@ extern "C++" void bdpt_host::bvh_args(const bdpt_ctx* c, bdpt_path_args& a) {
 static void path_args_plan(const bdpt_ctx* c, const bdpt_plan& plan, bdpt_path_args& a) {
     a.tiles_per_band = plan.tiles_per_band;
     a.nloc = (int)plan.lanes;
+    a.gx = plan.gx;
+    a.gy = plan.grid_rows;
     if (!plan.bvh) return;
     bvh_args(c, a);
     a.mat = c->d_mat;
@@ -1121,7 +1127,7 @@ struct path_kernels {
 // Resolve the specialised kernels (a compile on first use) and build the derived table the call's
 // pass-stream kernels read, both before the timed region starts.
 static int resolve_path_kernels(bdpt_ctx* c, const bdpt_plan& plan, int npass, bdpt_path_args& a, path_kernels& k) {
-    for (int p0 = 0; plan.grid_rows > 0 && p0 < npass; p0 += plan.chunk) {
+    for (int p0 = 0; plan.launches > 0 && p0 < npass; p0 += plan.chunk) {
         const int np = npass - p0 < plan.chunk ? npass - p0 : plan.chunk;
         const bool st = (plan.S < np ? plan.S : np) > 1;
         k.any_fused |= !st;
@@ -1130,8 +1136,10 @@ static int resolve_path_kernels(bdpt_ctx* c, const bdpt_plan& plan, int npass, b
         hipFunction_t& pool = k.jf[BDPT_KERNEL_POOL], &units = k.jf[BDPT_KERNEL_UNITS];
         if (st && plan.want_pool && !pool) pool = jit_path_kernel(c, true, true, true);
         if (st && plan.want_units && !units) units = jit_path_kernel(c, true, true, false, true);
-        if (st && !pool && !units && !k.jf[BDPT_KERNEL_STREAMS]) k.jf[BDPT_KERNEL_STREAMS] = jit_path_kernel(c, true);
-        if (!st && !k.jf[BDPT_KERNEL_FUSED]) k.jf[BDPT_KERNEL_FUSED] = jit_path_kernel(c, false, plan.pair);
+        const bool tiles = plan.ntiles >= 0;
+        if (st && !pool && !units && !k.jf[BDPT_KERNEL_STREAMS])
+            k.jf[BDPT_KERNEL_STREAMS] = jit_path_kernel(c, true, true, false, false, tiles);
+        if (!st && !k.jf[BDPT_KERNEL_FUSED]) k.jf[BDPT_KERNEL_FUSED] = jit_path_kernel(c, false, plan.pair, false, false, tiles);
     }
     // the derived table (the pooled build reads neither): sample records for a specialised build
     // that has them, else the sin/cos planes -- built if the table changed since they last were
@@ -1153,12 +1161,18 @@ static void path_lds_table(const bdpt_path_args& a, bool bvh, size_t* tab, size_
     *ids = bvh ? a.big_n : 0;
 }
 
+// The precompiled instance of a launch: by sphere count (or the BVH's), or for a launch over a tile
+// list the generic instance (any sphere count) or the BVH's with the tile-list code.
+static const void* precompiled_path_kernel(const bdpt_plan& plan, const bdpt_launch& L) {
+    return plan.ntiles >= 0 ? bdpt_path_tiles_kernel_table[L.st * 2 + plan.bvh] : bdpt_path_kernel_table[L.st * 18 + plan.kidx];
+}
+
 // Static LDS of the function a launch runs (HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES: the camera basis,
 // the sincos table, the claim words), asked once per function.
 static int path_kernel_static_lds(bdpt_ctx* c, const bdpt_plan& plan, const bdpt_launch& L, const path_kernels& k,
                                   size_t* stat) {
     const hipFunction_t jf = k.jf[L.kernel];
-    const void* key = jf ? (const void*)jf : (const void*)bdpt_path_kernel_table[L.st * 18 + plan.kidx];
+    const void* key = jf ? (const void*)jf : precompiled_path_kernel(plan, L);
     for (const auto& e : c->lds_static)
         if (e.first == key) {
             *stat = e.second;
@@ -1392,7 +1406,7 @@ static int launch_path_kernel(bdpt_ctx* c, const bdpt_plan& plan, const bdpt_lau
     if (jf)
         HIPCHK(c, hipModuleLaunchKernel(jf, grid.x, grid.y, grid.z, block.x, 1, 1, (unsigned)L.smem, ls, kargs, nullptr));
     else
-        HIPCHK(c, hipLaunchKernel(bdpt_path_kernel_table[L.st * 18 + plan.kidx], grid, block, kargs, L.smem, ls));
+        HIPCHK(c, hipLaunchKernel(precompiled_path_kernel(plan, L), grid, block, kargs, L.smem, ls));
     HIPCHK(c, hipEventRecord(call.cs->kev[2 * call.launches + 1], ls));
     call.launches++;
     return L.st && !L.unitsl ? issue_fold(c, call, plan.lanes, ls, half, kargs) : BDPT_OK;
@@ -1415,13 +1429,41 @@ static int end_call(bdpt_ctx* c, const bdpt_plan& plan, const path_kernels& k, c
     return BDPT_OK;
 }
 
-static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int npass) {
+// The tile list of a masked call: the mask's non-zero bytes as tile indices, ascending, kept in the
+// call's ring slot until the call has finished and uploaded on the context's stream behind the
+// outstanding fold (the previous list's last reader).
+static_assert(BDPT_NOISE_TW == BDPT_BTW && BDPT_NOISE_TH == BDPT_BTH, "the mask's tiles are the path kernel's workgroup tiles");
+static int upload_tile_list(bdpt_ctx* c, const std::vector<unsigned>& tiles) {
+    if (int rc = join_fold(c)) return rc;
+    if (tiles.size() > c->tiles_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));         // queued launches may read the old buffer
+        if (c->d_tiles) HIPCHK(c, hipFree(c->d_tiles));
+        c->d_tiles = nullptr;
+        c->tiles_cap = 0;
+        const size_t cap = (size_t)((c->W + BDPT_BTW - 1) / BDPT_BTW) * ((c->H + BDPT_BTH - 1) / BDPT_BTH);
+        if (hipMalloc(&c->d_tiles, sizeof(unsigned) * cap) != hipSuccess)
+            return fail(c, BDPT_ENOMEM, "bdpt_path_passes_tiles: tile list (%zu B)", sizeof(unsigned) * cap);
+        c->tiles_cap = cap;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_tiles, tiles.data(), sizeof(unsigned) * tiles.size(), hipMemcpyHostToDevice, c->stream));
+    return BDPT_OK;
+}
+
+static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int npass, const unsigned char* mask = nullptr) {
     if (!c) return BDPT_EINVAL;
     if (npass < 0 || (npass > 0 && (!sid || !vlp))) return fail(c, BDPT_EINVAL, "bdpt_path_passes: bad pass list");
+    if (mask && c->nshards > 1) return fail(c, BDPT_EINVAL, "bdpt_path_passes_tiles: sharded contexts take no tile mask");
     if (npass == 0) return BDPT_OK;
     if (!c->rand_ready) return fail(c, BDPT_ESTATE, "bdpt_path_passes: no random table (run the light pass first)");
     if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_path_passes: camera not set");
-    if (c->cpu) return cpu_path_passes(c, sid, vlp, npass);
+    int ntiles = -1;
+    if (mask) {
+        const size_t nt = (size_t)((c->W + BDPT_BTW - 1) / BDPT_BTW) * ((c->H + BDPT_BTH - 1) / BDPT_BTH);
+        ntiles = 0;
+        for (size_t t = 0; t < nt; t++) ntiles += mask[t] != 0;
+        if (ntiles == 0) return BDPT_OK;                     // nothing to render: no launch, no change
+    }
+    if (c->cpu) return cpu_path_passes(c, sid, vlp, npass, mask);
     HIPCHK(c, hipSetDevice(c->device));
     // this call's ring slot was last used kRing calls ago: wait for (only) that call
     path_call call;
@@ -1429,15 +1471,26 @@ static int one_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int
     if (int rc = fold_timing(c, c->issued - bdpt_ctx::kRing + 1)) return rc;
     bdpt_path_args a;
     if (int rc = path_args_base(c, a)) return rc;
-    if (int rc = settle_stream_mode(c)) return rc;
+    if (!mask)                                               // a masked call leaves the tuner as it is
+        if (int rc = settle_stream_mode(c)) return rc;
 
     const bdpt_path_env env = path_env();
     const bdpt_plan_in in = {c->W, c->H, c->shard, c->nshards, c->band_rows, c->streams_req, npass, a.n,
-                             c->has_bvh, c->traversal, c->bvh_ns, kBvhAutoSpheres, c->cus};
+                             c->has_bvh, c->traversal, c->bvh_ns, kBvhAutoSpheres, c->cus, ntiles};
     const bdpt_plan plan = bdpt_plan_call(in, c->tuner, env);
     c->last_streams = plan.S;
     c->last_bvh = plan.bvh;
     path_args_plan(c, plan, a);
+    if (mask) {
+        std::vector<unsigned>& tiles = call.cs->tiles;
+        tiles.clear();
+        for (unsigned t = 0; t < (unsigned)(plan.gx * plan.grid_rows); t++)
+            if (mask[t]) tiles.push_back(t);
+        if (int rc = upload_tile_list(c, tiles)) return rc;
+        a.tile_list = c->d_tiles;
+        a.ntiles = ntiles;
+        a.tiles_per_band = 1;               // no packed edges; one shard: tile row r is grid row r
+    }
 
     while (call.cs->kev.size() < 2 * (size_t)plan.launches) {   // per launch {before, after}
         hipEvent_t e;
@@ -1994,6 +2047,12 @@ int bdpt_light_pass(bdpt_ctx* c, int current_sample) {
 int bdpt_path_passes(bdpt_ctx* c, const unsigned* sid, const int* vlp, int npass) {
     if (int rc = one_path_passes(c, sid, vlp, npass)) return rc;
     return forward(c, [&](bdpt_ctx* p) { return one_path_passes(p, sid, vlp, npass); });
+}
+int bdpt_path_passes_tiles(bdpt_ctx* c, const unsigned* sid, const int* vlp, int npass, const unsigned char* tile_mask) {
+    if (!tile_mask) return bdpt_path_passes(c, sid, vlp, npass);
+    if (!c) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_path_passes_tiles: multi-device contexts take no tile mask");
+    return one_path_passes(c, sid, vlp, npass, tile_mask);
 }
 int bdpt_synchronize(bdpt_ctx* c) {
     if (int rc = one_synchronize(c)) return rc;

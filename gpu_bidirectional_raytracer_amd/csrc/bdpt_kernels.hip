@@ -135,13 +135,27 @@ namespace {
 #ifndef BDPT_UNITS
 #define BDPT_UNITS 0
 #endif
+// BDPT_TILES        0.  =1 builds the path kernel for launches over a tile list
+//                   (bdpt_path_passes_tiles) under the name bdpt_path_tiles_kernel_t: the Makefile
+//                   compiles this file a second time with it for the generic and the BVH instance
+//                   (bdpt_path_tiles_kernel_table, nothing else of the file), and the host builds the
+//                   specialised instance with it on the first masked call.  The code it adds is
+//                   compiled out of every other build, which so compiles from what it always did: a
+//                   run-time branch on the list, wave-uniform as it is, moved SGPR spills in four
+//                   of the 36 precompiled instances.
+#ifndef BDPT_TILES
+#define BDPT_TILES 0
+#endif
+#if BDPT_TILES
+#define bdpt_path_kernel_t bdpt_path_tiles_kernel_t
+#endif
 #ifdef BDPT_JIT
 constexpr int kJitNLights = __builtin_popcountll(kJitEmis);      // bdpt_host.cpp upload_scene lights
 #endif
 
 }  // namespace
 
-#ifndef BDPT_JIT
+#if !defined(BDPT_JIT) && !BDPT_TILES
 // =============================================================================================
 // Kernel 1: MT607 table (RandomGPU MersenneTwister_kernel.cu:63-110).  4096 independent twisters,
 // lane-major output d_Rand[tid + k*4096].  The 19-word state lives in VGPRs: the recurrence is
@@ -297,7 +311,7 @@ extern "C" __global__ __launch_bounds__(64) void bdpt_light_kernel(const bdpt_de
     lp[ind] = out;
 }
 
-#endif  // BDPT_JIT
+#endif  // BDPT_JIT, BDPT_TILES
 
 // =============================================================================================
 // Kernel 3: the eye-path integrator (RadiancePathTracingKernel device.cu:544-791), `npass`
@@ -647,8 +661,18 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
         vtile = (int)uclaim[1];
         if (urange == 0xffffffffu) return;                                     // (cannot happen)
     }
+    // a tile list (bdpt_path_passes_tiles; never pools or units): workgroup b renders tile
+    // tile_list[b] of the a.gx x a.gy grid and nothing else -- no packed edges, launch-local
+    // radiance index b * 256 + the pixel's row-major slot in the tile (bdpt_device.h)
     // the workgroup's tile (vbx, vby) in the tile grid (vgx, vgy)
+#if BDPT_TILES
+    constexpr bool listed = !kPool && !kUnits;
+    if constexpr (listed) vtile = (int)a.tile_list[blockIdx.x];
+    const bool vt = kUnits || listed;
+    const int vbx = vt ? vtile % a.gx : (int)blockIdx.x, vby = vt ? vtile / a.gx : (int)blockIdx.y;
+#else
     const int vbx = kUnits ? vtile % a.gx : (int)blockIdx.x, vby = kUnits ? vtile / a.gx : (int)blockIdx.y;
+#endif
     const int vgx = kUnits ? a.gx : (int)gridDim.x, vgy = kUnits ? a.gy : (int)gridDim.y;
     const int S = kUnits ? 1 : (STREAMS ? a.streams : 1);
     int ulen = 0;
@@ -817,7 +841,9 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
     // tile row one wave with tw x 8 live lanes that still runs whole paths; instead those tw x H
     // pixels are dealt out y-major, 256 per workgroup of that column, and likewise the th < 8
     // rows of the last workgroup row (x below the last column, row-major) to the workgroups of
-    // that row.  Every pixel is still rendered by exactly one lane.
+    // that row.  Every pixel is still rendered by exactly one lane.  (Not under a
+    // tile list, where a listed edge tile renders its own pixels inside the frame: the host sets
+    // tiles_per_band = 1 for it, with one shard the identity of bdpt_dev_tile_row.)
     if (a.tiles_per_band <= 0) {
         const int gx = vgx, gy = vgy;
         const int xt = (gx - 1) * BDPT_BTW, yt = (gy - 1) * BDPT_BTH;
@@ -834,6 +860,12 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
     }
     const int yoff = (bdpt_dev_tile_row(a, vby) - vby) * BDPT_BTH;   // uniform
     int y = ly + yoff;
+#if BDPT_TILES
+    // the launch-local radiance index of pixel (x, y) is (y - lrow0) * lw + x: under a tile list the
+    // listed tiles' slots (bdpt_device.h), else the launch's rows; both uniform
+    const int lrow0 = listed ? bdpt_dev_list_row0((int)blockIdx.x, vbx, vby) : yoff;
+    const int lw = listed ? BDPT_BTW : a.W;
+#endif
     bool active = x < a.W && y < a.H;
     if (active && a.nshards > 1) active = ((y / a.band_rows) % a.nshards) == a.shard;
     // pixel pools: this wave's chunk is [.., pend) of the launch's row-major pixels (local rows:
@@ -1521,7 +1553,11 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
                     r.x = rad.x; r.y = rad.y; r.z = rad.z;
                     unsigned xyv = xy;
                     asm volatile("" : "+v"(xyv));
+#if BDPT_TILES
+                    const int li = kPool ? (int)lix : ((int)(xyv >> 16) - lrow0) * lw + (int)(xyv & 0xffffu);
+#else
                     const int li = kPool ? (int)lix : ((int)(xyv >> 16) - yoff) * a.W + (int)(xyv & 0xffffu);
+#endif
                     const size_t ri = (size_t)(s0 + k * S) * a.nloc + (size_t)li;
                     if constexpr (kPool) {
                         // sparse radiance: pixel pools serve open scenes, where most samples are
@@ -1680,7 +1716,14 @@ void bdpt_path_kernel_t(bdpt_path_args a) {
     a.pixels[i] = bdpt_dev_to_rgba(col.x, col.y, col.z, a.gamma_thr);
 }
 
-#ifndef BDPT_JIT
+#if !defined(BDPT_JIT) && BDPT_TILES
+// launches over a tile list: [streams * 2 + bvh], the generic LDS traversal (any sphere count) or the
+// BVH (bdpt_path_kernel_t is bdpt_path_tiles_kernel_t in this build)
+extern "C" const void* bdpt_path_tiles_kernel_table[4] = {
+    (const void*)&bdpt_path_kernel_t<0, false>, (const void*)&bdpt_path_kernel_t<-1, false>,
+    (const void*)&bdpt_path_kernel_t<0, true>, (const void*)&bdpt_path_kernel_t<-1, true>};
+#endif
+#if !defined(BDPT_JIT) && !BDPT_TILES
 // host-side launch table: [streams * 18 + k], k = sphere count (0 = generic LDS traversal) or 17 = BVH
 #define BDPT_K(NN, ST) (const void*)&bdpt_path_kernel_t<NN, ST>
 #define BDPT_ROW(ST) BDPT_K(0, ST), BDPT_K(1, ST), BDPT_K(2, ST), BDPT_K(3, ST), BDPT_K(4, ST), \
@@ -1701,13 +1744,23 @@ template <int U, bool SPARSE>
 __device__ __forceinline__ void accum_body(const bdpt_path_args& a) {
     const long l = (long)blockIdx.x * 256 + threadIdx.x;
     if (l >= a.nloc) return;
-    const int ly = (int)(l / a.W);
-    const int x = (int)(l - (long)ly * a.W);
-    const int y = bdpt_dev_tile_row(a, ly / BDPT_BTH) * BDPT_BTH + ly % BDPT_BTH;
+    int x, y;
+    size_t li;
+    if (a.tile_list) {
+        // a tile list: launched pixel l is slot l & 255 of list entry l >> 8 (bdpt_device.h)
+        const int t = (int)a.tile_list[blockIdx.x];
+        bdpt_dev_list_pixel(t % a.gx, t / a.gx, (int)threadIdx.x, &x, &y);
+        if (x >= a.W) return;
+        li = (size_t)l;
+    } else {
+        const int ly = (int)(l / a.W);
+        x = (int)(l - (long)ly * a.W);
+        y = bdpt_dev_tile_row(a, ly / BDPT_BTH) * BDPT_BTH + ly % BDPT_BTH;
+        li = (size_t)ly * a.W + x;
+    }
     if (y >= a.H) return;
     if (a.nshards > 1 && ((y / a.band_rows) % a.nshards) != a.shard) return;
     const int i = y * a.W + x;
-    const size_t li = (size_t)ly * a.W + x;
     const unsigned cnt0 = a.counter[i];
     unsigned cnt = cnt0;
     bdpt_dev_vec col = a.colors[i];
@@ -1909,4 +1962,4 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_aov_kernel(bdpt_path_args
 }
 
 #include "bdpt_frame_kernels.h"    // the frame services' kernels (denoiser, reprojection, preview, noise)
-#endif  // BDPT_JIT
+#endif  // BDPT_JIT, BDPT_TILES

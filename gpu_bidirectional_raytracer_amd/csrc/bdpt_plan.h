@@ -160,11 +160,16 @@ struct bdpt_plan_in {
     bool has_bvh;
     int traversal, bvh_ns, bvh_auto_spheres;   // BDPT_TRAVERSE_*, BVH spheres, the auto mode's threshold
     int cus;
+    // bdpt_path_passes_tiles: the mask's non-zero bytes, or -1 for a call without a mask.  A masked
+    // call launches one workgroup per listed tile and stream, never pools or units, and takes no
+    // part in the auto mode's measurement (it follows the decision kept, and leaves it alone).
+    int ntiles = -1;
 };
 
 struct bdpt_plan {
     int gx, grid_rows, tiles_per_band;   // tile columns and rows of a launch
-    long lanes;                     // launched pixels per pass
+    int ntiles;                     // >= 0: the launch enumerates a list of this many tiles of the gx x grid_rows grid
+    long lanes;                     // launched pixels per pass (a listed tile counts in full: 256)
     int chunk;                      // passes per launch (the last may have fewer)
     int launches;
     int S;                          // pass streams of a full launch (bdpt_last_streams)
@@ -187,11 +192,14 @@ inline bdpt_plan bdpt_plan_call(const bdpt_plan_in& in, const bdpt_tuner& t, con
     // balanced, while a lane that regenerates through many passes waits for the wave's slowest
     // sum (+11.7 % at 1080p, and it fills the GPU when a shard has few pixels).
     p.lanes = (long)p.grid_rows * BDPT_BTH * in.W;
+    const bool listed = in.ntiles >= 0;
+    p.ntiles = listed ? in.ntiles : -1;
+    if (listed) p.lanes = 256L * in.ntiles;
     int S = in.streams_req <= 0 ? BDPT_MAX_STREAMS : in.streams_req;
     // auto: a measuring call runs its role's variant, later calls the variant kept
     const bool autom = in.streams_req == 0;
     const bool kept = autom && t.enabled && t.decided();
-    p.tune_role = autom ? t.role(in.npass) : -1;
+    p.tune_role = autom && !listed ? t.role(in.npass) : -1;
     const int kind = p.tune_role >= 0 ? (int)kTuneRole[p.tune_role] : -1;
     p.pair = true;
     if (kind == BDPT_ROLE_FUSED_PAIRED || kind == BDPT_ROLE_FUSED_UNPAIRED) {
@@ -218,7 +226,7 @@ inline bdpt_plan bdpt_plan_call(const bdpt_plan_in& in, const bdpt_tuner& t, con
         if (S > chunk) S = chunk;
     }
     p.chunk = chunk;
-    p.launches = p.grid_rows > 0 ? (in.npass + chunk - 1) / chunk : 0;
+    p.launches = p.grid_rows > 0 && in.ntiles != 0 ? (in.npass + chunk - 1) / chunk : 0;
     p.bvh = in.has_bvh && (in.traversal == BDPT_TRAVERSE_BVH ||
                            (in.traversal == BDPT_TRAVERSE_AUTO && in.bvh_ns >= in.bvh_auto_spheres));
     p.kidx = p.bvh ? 17 : (in.n_spheres <= 16 ? (int)in.n_spheres : 0);
@@ -233,14 +241,16 @@ inline bdpt_plan bdpt_plan_call(const bdpt_plan_in& in, const bdpt_tuner& t, con
         S = p.quarter_ran ? (S + 3) / 4 : (S + 1) / 2;
     }
     // pixel pools: forced by BDPT_POOL=R, or measured and kept
-    p.want_pool = !p.bvh && S > 1 && env.pool != 0 &&
+    // (a tile list takes neither pools, which enumerate row-major pixels, nor units, whose handover
+    // waits are not worth carrying onto a partial tile set -- not even when forced)
+    p.want_pool = !listed && !p.bvh && S > 1 && env.pool != 0 &&
                   (env.pool > 0 || (autom && (kind >= 0 ? kind == BDPT_ROLE_POOLS : (kept && t.pool))));
     if (p.want_pool) S = chunk < in.npass ? chunk : in.npass;    // one pass per lane slice
     // ordered in-kernel fold (units of a tile and a range of passes; no radiance buffer): forced by
     // BDPT_UNITS=P (ranges of P passes), or measured and kept; not for shards whose tile workgroups
     // cannot keep the chip busy with one range per tile (a tile's units run one after another)
     const bool units_fit = (long)p.gx * p.grid_rows >= 2L * in.cus * 6;
-    p.want_units = !p.bvh && S > 1 && !p.want_pool && env.units != 0 &&
+    p.want_units = !listed && !p.bvh && S > 1 && !p.want_pool && env.units != 0 &&
                    (env.units > 0 ||
                     (autom && units_fit && (kind >= 0 ? kind == BDPT_ROLE_UNITS : (kept && t.units))));
     p.unit_passes = env.units > 0 ? env.units : kUnitPasses;
@@ -340,8 +350,10 @@ inline bdpt_launch bdpt_plan_launch(const bdpt_plan& p, int p0, int npass, bool 
                  (l.pooled ? BDPT_FEAT_POOLS : 0) | (l.unitsl ? BDPT_FEAT_UNITS : 0) |
                  (l.st && !l.pooled ? BDPT_FEAT_SCP : 0) | (l.st && use_srec ? BDPT_FEAT_SREC : 0) |
                  (l.kernel != BDPT_KERNEL_PRECOMPILED
-                      ? BDPT_FEAT_SPECIALIZED | BDPT_FEAT_DET_SKIP | (zero_exit ? BDPT_FEAT_ZERO_EXIT : 0) : 0);
+                      ? BDPT_FEAT_SPECIALIZED | BDPT_FEAT_DET_SKIP | (zero_exit ? BDPT_FEAT_ZERO_EXIT : 0) : 0) |
+                 (p.ntiles >= 0 ? BDPT_FEAT_TILES : 0);
     l.grid[0] = (unsigned)p.gx; l.grid[1] = (unsigned)p.grid_rows; l.grid[2] = (unsigned)l.streams;
+    if (p.ntiles >= 0) { l.grid[0] = (unsigned)p.ntiles; l.grid[1] = 1; }   // one workgroup per listed tile
     if (l.pooled) {
         // waves of pool x 64 pixels; 1-D, passes interleaved in groups of 8 workgroups (bdpt_kernels.hip s0)
         bdpt_pool_shape(p.lanes, l.overlap, env, &l.pool, &l.pool_grid);

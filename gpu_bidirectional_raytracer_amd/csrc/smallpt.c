@@ -7,7 +7,7 @@
  *           [--device D | --gpus N | --devices D0,D1,...] [--tile ROWS] [--seed S] [--dat PATH]
  *           [--denoise [--denoise-levels N] [--denoise-sigma S] [--denoise-all] [--denoise-count N]]
  *           [--reproject [--reproject-history N] [--reproject-tol T]]
- *           [--until E [--max-spp N]]
+ *           [--until E [--max-spp N] [--adaptive [--min-spp N]]]
  *
  * Without positional arguments the built-in CornellSpheres scene is used (smallpt_cpu.c:400).
  * Like the reference, width/height get +1 (smallpt_cpu.c:409-410).  The first frame runs the
@@ -37,7 +37,11 @@
  * each key of --keys: batches of --batch passes, after each a noise estimate (bdpt_noise_estimate
  * with remark, threshold E), until some pixel is valid, none is pending and no tile is over E, or
  * until --max-spp passes (default 4096) are rendered; one report line per render on stderr.  One
- * device (or the CPU) only.
+ * device (or the CPU) only.  With --adaptive every 32 x 8 tile stops on its own: a batch renders only
+ * the tiles that are not settled yet (bdpt_path_passes_tiles), and a tile is settled for good once
+ * none of its pixels is pending, its error is at most E and --min-spp passes (default 0) are done;
+ * the report line then also says how many pixel-passes that took.  The frame is noisier than the
+ * one plain --until leaves, which oversamples the easy tiles.
  */
 #include "smallpt_app.h"
 
@@ -53,7 +57,7 @@ int main(int argc, char **argv)
     int denoise = 0;
     bdpt_denoise_params dn = {4, 5, 0.5f, BDPT_DENOISE_DIFFUSE};
     float count_ref = 8.f;
-    int until = 0, max_spp = 4096;
+    int until = 0, max_spp = 4096, adaptive = 0, min_spp = 0;
     bdpt_noise_params nz = {0.01f, 0.05f, 1};
     h.rp.materials = BDPT_DENOISE_DIFFUSE;
     h.rp.max_history = 64.f;
@@ -86,6 +90,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[a], "--reproject-tol") && a + 1 < argc) h.rp.plane_tol = strtof(argv[++a], NULL);
         else if (!strcmp(argv[a], "--until") && a + 1 < argc) { until = 1; nz.threshold = strtof(argv[++a], NULL); }
         else if (!strcmp(argv[a], "--max-spp") && a + 1 < argc) max_spp = atoi(argv[++a]);
+        else if (!strcmp(argv[a], "--adaptive")) adaptive = 1;
+        else if (!strcmp(argv[a], "--min-spp") && a + 1 < argc) min_spp = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--checkpoint") && a + 1 < argc) ckpt = argv[++a];
         else if (!strcmp(argv[a], "--resume") && a + 1 < argc) resume = argv[++a];
         else if (npos < 3) pos[npos++] = argv[a];
@@ -107,6 +113,10 @@ int main(int argc, char **argv)
     }
     if (until && (batch < 1 || !(nz.threshold >= 0.f))) {
         fprintf(stderr, "--until: a threshold >= 0 and --batch >= 1\n");
+        return 1;
+    }
+    if (adaptive && !until) {
+        fprintf(stderr, "--adaptive goes with --until E\n");
         return 1;
     }
     if (npos == 3) {
@@ -173,7 +183,8 @@ int main(int argc, char **argv)
     }
     int until_failed = 0;
     if (until) {
-        if (render_until(&h, &nz, max_spp, batch) < 0) until_failed = 1;
+        if ((adaptive ? render_until_adaptive(&h, &nz, max_spp, batch, min_spp)
+                      : render_until(&h, &nz, max_spp, batch)) < 0) until_failed = 1;
     } else {
         for (int done = 0; done < spp; done += batch)
             update_rendering(&h, spp - done < batch ? spp - done : batch);
@@ -181,7 +192,8 @@ int main(int argc, char **argv)
     for (const char *k = keys; *k; k++) {
         key(&h, (unsigned char)*k);
         if (until) {
-            if (render_until(&h, &nz, max_spp, batch) < 0) until_failed = 1;
+            if ((adaptive ? render_until_adaptive(&h, &nz, max_spp, batch, min_spp)
+                          : render_until(&h, &nz, max_spp, batch)) < 0) until_failed = 1;
         } else {
             for (int done = 0; done < spp; done += batch)
                 update_rendering(&h, spp - done < batch ? spp - done : batch);

@@ -47,24 +47,31 @@ static void update_rendering2(host *h)
     bdpt_pass_state_light(&h->ps);
 }
 
-/* npass x UpdateRendering smallpt_cpu.c:265-297, fused into one launch */
-static void update_rendering(host *h, int npass)
+/* npass x UpdateRendering smallpt_cpu.c:265-297, fused into one launch; with a tile mask
+ * (bdpt_path_passes_tiles, no reference counterpart) only the `pixels` pixels of the masked-in
+ * tiles are rendered and counted, while the pass schedule and current_sample advance all the same */
+static void update_rendering_tiles(host *h, int npass, const unsigned char *tile_mask, long long pixels)
 {
     unsigned *sid = malloc(sizeof(unsigned) * npass);
     int *vlp = malloc(sizeof(int) * npass);
     bdpt_pass_schedule(&h->ps, npass, sid, vlp);
     double start = wall_clock();
-    int rc = bdpt_path_passes(h->ctx, sid, vlp, npass);
+    int rc = bdpt_path_passes_tiles(h->ctx, sid, vlp, npass, tile_mask);
     if (rc == BDPT_OK) rc = bdpt_synchronize(h->ctx);
     report(h, rc, "Kernel RadiancePathTracing");
     h->current_sample += npass;
     const float elapsed = (float)(wall_clock() - start);
     h->total_time += elapsed;
-    const float sample_sec = (float)h->height * h->width * npass / elapsed;
+    const float sample_sec = (tile_mask ? (float)pixels : (float)h->height * h->width) * npass / elapsed;
     printf("Rendering time %.3f sec (pass %d) Total:%.2f  Sample/sec  %.1fK\n", elapsed,
            h->current_sample, h->total_time, sample_sec / 1000.f);
     free(sid);
     free(vlp);
+}
+
+static void update_rendering(host *h, int npass)
+{
+    update_rendering_tiles(h, npass, NULL, 0);
 }
 
 /* ReInit smallpt_cpu.c:373-387 (buffers persist; only the accumulation restarts) */
@@ -169,6 +176,62 @@ __attribute__((unused)) static int render_until(host *h, const bdpt_noise_params
             h->current_sample, h->current_sample - first, converged ? "converged" : "not converged",
             (double)s.max_tile, s.mean);
     return converged;
+}
+
+/* --until E --adaptive: the same loop, but every 32 x 8 tile stops on its own: a batch renders only
+ * the tiles not yet retired (bdpt_path_passes_tiles), and after its estimate a tile retires -- for
+ * good -- when none of its pixels is pending, its error is at most the threshold (or it has no
+ * valid pixel) and min_spp passes are done.  Converged when every tile is retired.  One report
+ * line on stderr with the pixel-passes rendered against width x height x passes. */
+__attribute__((unused)) static int render_until_adaptive(host *h, const bdpt_noise_params *np, int max_spp, int batch,
+                                                         int min_spp)
+{
+    int tx = 0, ty = 0, converged = 0, left = 0;
+    if (bdpt_noise_tiles(h->ctx, &tx, &ty) != BDPT_OK) {
+        report(h, BDPT_EINVAL, "Noise tiles");
+        return -1;
+    }
+    const int nt = tx * ty, first = h->current_sample;
+    unsigned char *live = malloc((size_t)nt);
+    float *err = malloc(sizeof(float) * (size_t)nt);
+    unsigned *valid = malloc(sizeof(unsigned) * (size_t)nt), *pending = malloc(sizeof(unsigned) * (size_t)nt);
+    bdpt_noise_summary s;
+    long long pixel_passes = 0;
+    int rc = live && err && valid && pending ? BDPT_OK : BDPT_ENOMEM;
+    memset(&s, 0, sizeof s);
+    if (rc == BDPT_OK) memset(live, 1, (size_t)nt);
+    while (rc == BDPT_OK) {
+        long long pixels = 0;
+        for (int t = 0; t < nt; t++) {
+            const int w = h->width - (t % tx) * BDPT_NOISE_TW, r = h->height - (t / tx) * BDPT_NOISE_TH;
+            if (live[t]) pixels += (long long)(w < BDPT_NOISE_TW ? w : BDPT_NOISE_TW) * (r < BDPT_NOISE_TH ? r : BDPT_NOISE_TH);
+        }
+        const int before = h->current_sample;
+        update_rendering_tiles(h, batch, live, pixels);
+        pixel_passes += pixels * (h->current_sample - before);
+        rc = bdpt_noise_estimate(h->ctx, np, NULL, err, valid, &s);
+        if (rc == BDPT_OK) rc = bdpt_noise_tile_pending(h->ctx, pending);
+        if (rc != BDPT_OK) break;
+        left = 0;
+        for (int t = 0; t < nt; t++) {
+            if (live[t] && pending[t] == 0 && (valid[t] == 0 || err[t] <= np->threshold) && h->current_sample >= min_spp)
+                live[t] = 0;
+            left += live[t];
+        }
+        converged = left == 0;
+        if (converged || h->current_sample >= max_spp) break;
+    }
+    report(h, rc, "Adaptive noise estimate");
+    if (rc == BDPT_OK)
+        fprintf(stderr, "Until %g adaptive: %d passes (%d in this render), %s, %d of %d tiles left, "
+                "%lld pixel-passes of %lld (width x height x passes)\n", (double)np->threshold, h->current_sample,
+                h->current_sample - first, converged ? "converged" : "not converged", left, nt, pixel_passes,
+                (long long)h->width * h->height * (h->current_sample - first));
+    free(live);
+    free(err);
+    free(valid);
+    free(pending);
+    return rc == BDPT_OK ? converged : -1;
 }
 
 /* what a checkpoint carries besides the frame: the pass schedule and the host counters */

@@ -2,6 +2,7 @@
 
     python -m gpu_bidirectional_raytracer_amd.noise <width> <height> <scene> --out PREFIX
                                   [--until E] [--max-spp N] [--batch B] [--device D] [--ppm]
+                                  [--adaptive [--min-spp N]]
 
 Sizes get +1 like `smallpt` (smallpt_cpu.c:409-410).  SmallPT.RenderUntil: batches of B passes
 (default 8), after each a noise estimate with re-marking (Renderer.noise_estimate), until some pixel
@@ -11,6 +12,10 @@ where not valid; row 0 is the frame's bottom row, as in read_radiance), tile_err
 [tiles_y, tiles_x], and summary, one record with the fields of bdpt_noise_summary plus threshold,
 passes and converged.  --ppm also writes PREFIX_error.ppm, a grey heat map through save_ppm
 (bottom-up rows, as SavePPM): black is no error or not valid, white is 2 E or more.
+--adaptive stops every 32 x 8 tile on its own (RenderUntil(adaptive=True, min_passes=N): a tile is
+not rendered again once none of its pixels is pending and its error is at most E); the archive then
+also holds retired_at and retired_error [tiles_y, tiles_x], pixel_passes, and counter [H, W], the
+passes every pixel got.
 """
 from __future__ import annotations
 
@@ -56,19 +61,30 @@ def main(argv=None) -> int:
     ap.add_argument("--batch", type=int, default=8, metavar="B", help="passes between two checks (default 8)")
     ap.add_argument("--device", type=int, default=0, help="HIP ordinal, -1 = the CPU backend")
     ap.add_argument("--ppm", action="store_true", help="also write PREFIX_error.ppm, a grey heat map")
+    ap.add_argument("--adaptive", action="store_true", help="stop every 32 x 8 tile on its own")
+    ap.add_argument("--min-spp", type=int, default=0, metavar="N", help="--adaptive: no tile stops before N passes")
     args = ap.parse_args(argv)
 
     app = SmallPT(args.width, args.height, args.scene, device=args.device)
     try:
-        est = app.RenderUntil(args.until, max_passes=args.max_spp, batch=args.batch, pixels=True)
+        est = app.RenderUntil(args.until, max_passes=args.max_spp, batch=args.batch, pixels=True,
+                              adaptive=args.adaptive, min_passes=args.min_spp)
+        counter = app.colors()[1] if args.adaptive else None
     finally:
         app.FreeBuffers()
+    extra = {}
+    if args.adaptive:
+        extra = dict(retired_at=est["retired_at"], retired_error=est["retired_error"],
+                     pixel_passes=np.int64(est["pixel_passes"]), counter=counter)
     np.savez_compressed(args.out + ".npz", error=est["error"], tile_error=est["tile_error"],
-                        tile_valid=est["tile_valid"], summary=summary_record(est, args.until))
+                        tile_valid=est["tile_valid"], summary=summary_record(est, args.until), **extra)
     if args.ppm:
         save_ppm(args.out + "_error.ppm", error_rgba(est["error"], args.until))
     print(f"{app.width}x{app.height}: {est['passes']} passes, {'converged' if est['converged'] else 'not converged'}, "
           f"worst tile {est['max_tile']:.9g}, mean {est['mean']:.17g} -> {args.out}.npz", file=sys.stderr)
+    if args.adaptive:
+        print(f"adaptive: {est['pixel_passes']} pixel-passes of {app.width * app.height * est['passes']} "
+              f"(width x height x passes)", file=sys.stderr)
     return 0
 
 

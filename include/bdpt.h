@@ -183,6 +183,8 @@ int  bdpt_last_traversal(const bdpt_ctx *ctx);
 #define BDPT_FEAT_UNITS     128             /* pass streams with the ordered fold in the kernel:
                                                units of (tile, range of passes) in range order,
                                                running mean in registers, no radiance buffer   */
+#define BDPT_FEAT_TILES    1024             /* the launch enumerated a tile list: one workgroup per
+                                               masked-in tile (bdpt_path_passes_tiles)         */
 int  bdpt_last_kernel_features(const bdpt_ctx *ctx);
 /* LDS of the last bdpt_path_passes call's largest launch, in bytes, whether it ran or was refused:
  * what the launched kernel declares itself (static), what the launch adds for the scene tables and
@@ -209,6 +211,28 @@ int  bdpt_generate_rand(bdpt_ctx *ctx, unsigned seed);
  * Asynchronous on the context's stream (a call only waits for the call issued 4 calls earlier,
  * whose pass-table slot it reuses); bdpt_synchronize() waits for all. */
 int  bdpt_path_passes(bdpt_ctx *ctx, const unsigned *sid, const int *vlp_index, int npass);
+/* Path passes over some tiles only (no reference counterpart): the passes of
+ * bdpt_path_passes for the pixels of the tiles whose byte in tile_mask is non-zero.  Tiles are the
+ * noise estimate's: BDPT_NOISE_TW x BDPT_NOISE_TH pixels anchored at (0, 0), row-major, tiles_x *
+ * tiles_y of them (bdpt_noise_tiles); tiles of the last column and row hold only their pixels inside
+ * the frame.  A pixel of a masked-in tile gets exactly what bdpt_path_passes gives it -- the same
+ * samples (sid and vlp_index are per pass, whatever the mask), the `counter < 30000` rule, the
+ * pixel bytes; every other pixel keeps colours, counter and pixel bytes bit for bit.  Pixels are
+ * independent, so a frame rendered under changing masks holds, per pixel, what the unmasked frame
+ * held after as many passes as that pixel's tile was rendered for.
+ *   tile_mask == NULL   is bdpt_path_passes: the same code path, auto stream mode included.
+ *   all bytes zero      BDPT_OK after the usual argument and state checks; nothing is launched and
+ *                       nothing changes (bdpt_kernel_timing's launch count included).
+ * A masked call launches one workgroup per masked-in tile and pass stream (BDPT_FEAT_TILES) from a
+ * tile list the context uploads before the launch.  It never runs pixel pools or the in-kernel fold
+ * (BDPT_POOL / BDPT_UNITS are ignored) and it neither takes a turn of the auto stream mode's
+ * measurement nor resets its decision: in auto mode it runs the variant kept (fused or pass
+ * streams, two or four passes per lane), two passes per lane while there is no decision; explicit
+ * bdpt_set_streams values are honoured.  Like any path pass it keeps the noise estimate's mark and
+ * the reprojection history.  BDPT_EINVAL: a multi-device context or a sharded one (nshards > 1)
+ * with a non-NULL mask, and what bdpt_path_passes refuses. */
+int  bdpt_path_passes_tiles(bdpt_ctx *ctx, const unsigned *sid, const int *vlp_index, int npass,
+                            const unsigned char *tile_mask);
 int  bdpt_synchronize(bdpt_ctx *ctx);
 /* Device time (ms, HIP events on the context's stream) of the last bdpt_path_passes call. */
 int  bdpt_last_path_ms(bdpt_ctx *ctx, float *ms);
@@ -495,7 +519,11 @@ int  bdpt_last_preview_ms(bdpt_ctx *ctx, float *ms);
  * history are untouched.
  * BDPT_EINVAL: NULL parameters, dark not > 0 (NaN rejected), threshold negative or NaN, all outputs
  * NULL, a multi-device context.  BDPT_ESTATE: bdpt_noise_read_mark while no mark was ever stored;
- * bdpt_last_noise_ms before the first estimate.  Defaults: dark 0.01, threshold 0.05, remark 0. */
+ * bdpt_last_noise_ms before the first estimate.  Defaults: dark 0.01, threshold 0.05, remark 0.
+ * bdpt_noise_tile_pending: the last bdpt_noise_estimate's pending count per tile (tiles_x * tiles_y,
+ * row-major; their sum is the summary's pending_pixels), so that a caller can tell which tiles are
+ * settled (bdpt_path_passes_tiles).  BDPT_ESTATE before the first estimate, BDPT_EINVAL for NULL or a
+ * multi-device context. */
 #define BDPT_NOISE_TW 32
 #define BDPT_NOISE_TH 8
 typedef struct { float dark; float threshold; int remark; } bdpt_noise_params;
@@ -508,6 +536,7 @@ int  bdpt_noise_read_mark(bdpt_ctx *ctx, bdpt_vec *colors, unsigned *counter);
 int  bdpt_noise_write_mark(bdpt_ctx *ctx, const bdpt_vec *colors, const unsigned *counter);
 int  bdpt_noise_estimate(bdpt_ctx *ctx, const bdpt_noise_params *params, float *error_out,
                          float *tile_error, unsigned *tile_valid, bdpt_noise_summary *summary);
+int  bdpt_noise_tile_pending(bdpt_ctx *ctx, unsigned *tile_pending);
 int  bdpt_last_noise_ms(bdpt_ctx *ctx, float *ms);
 
 /* ---- optional display: HIP-GL interop ----
