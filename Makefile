@@ -57,8 +57,11 @@ $(BUILD)/bdpt_kernels_tiles.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(
 $(CSRC)/bdpt_jit_src.h: tools/embed_jit_sources.py $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h
 	python3 tools/embed_jit_sources.py $@
 
-CTX_DEPS := $(CSRC)/bdpt_ctx.h $(CSRC)/bdpt_device.h $(CSRC)/bdpt_plan.h $(CSRC)/bdpt_cpu.h include/bdpt.h
-$(BUILD)/bdpt_host.o: $(CSRC)/bdpt_host.cpp $(CTX_DEPS) $(CSRC)/bdpt_bvh.h $(CSRC)/bdpt_jit_src.h | $(BUILD)
+CTX_DEPS := $(CSRC)/bdpt_ctx.h $(CSRC)/bdpt_device.h $(CSRC)/bdpt_plan.h $(CSRC)/bdpt_jit_plan.h $(CSRC)/bdpt_cpu.h include/bdpt.h
+$(BUILD)/bdpt_host.o: $(CSRC)/bdpt_host.cpp $(CTX_DEPS) $(CSRC)/bdpt_bvh.h | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/bdpt_jit.o: $(CSRC)/bdpt_jit.cpp $(CTX_DEPS) $(CSRC)/bdpt_jit_src.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/bdpt_frame.o: $(CSRC)/bdpt_frame.cpp $(CTX_DEPS) | $(BUILD)
@@ -76,7 +79,7 @@ $(BUILD)/bdpt_util.o: $(CSRC)/bdpt_util.c include/bdpt.h | $(BUILD)
 $(BUILD)/bdpt_ckpt.o: $(CSRC)/bdpt_ckpt.c include/bdpt.h | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(LIB): $(BUILD)/bdpt_kernels.o $(BUILD)/bdpt_host.o $(BUILD)/bdpt_frame.o $(BUILD)/bdpt_bvh.o $(BUILD)/bdpt_cpu.o $(BUILD)/bdpt_util.o $(BUILD)/bdpt_ckpt.o $(BUILD)/bdpt_kernels_tiles.o
+$(LIB): $(BUILD)/bdpt_kernels.o $(BUILD)/bdpt_host.o $(BUILD)/bdpt_jit.o $(BUILD)/bdpt_frame.o $(BUILD)/bdpt_bvh.o $(BUILD)/bdpt_cpu.o $(BUILD)/bdpt_util.o $(BUILD)/bdpt_ckpt.o $(BUILD)/bdpt_kernels_tiles.o
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl
 

@@ -1,6 +1,6 @@
 // bdpt_ctx.h -- private to the host layer: the context behind include/bdpt.h's opaque bdpt_ctx, the
-// error helpers, and the few functions of bdpt_host.cpp that the frame services of bdpt_frame.cpp
-// call.  Nothing here is ABI.
+// error helpers, and the few functions that bdpt_host.cpp, bdpt_jit.cpp and the frame services of
+// bdpt_frame.cpp call across files.  Nothing here is ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_gl_interop.h>         // hipGraphicsResource_t (the optional display, 8(f)4)
@@ -14,6 +14,7 @@
 #include "bdpt_device.h"
 #include "bdpt_cpu.h"
 #include "bdpt_plan.h"
+#include "bdpt_jit_plan.h"
 
 // "The last call's time" of one frame service (bdpt_frame.cpp svc_*; read by bdpt_last_*_ms).
 struct bdpt_svc_clock {
@@ -141,15 +142,17 @@ struct bdpt_ctx {
     char jit_err[256] = {0};            // why the last specialisation fell back (diagnostics)
     int jit_waves = 0;                  // waves/SIMD bound of the last specialised build
     bool jit_zero_exit = false;         // the last specialised build has the black-surface exit
-    // jit_path_kernel's answer per [fused / pass streams / pools][paired loads] for the current scene, specialise
-    // switch and JIT environment (jit_env_key): a call then resolves its kernel without rebuilding the option
-    // strings (tens of microseconds per call, which the one-pass-per-call pattern pays every call)
+    // jit_path_kernel's answer per variant (bdpt_jit_variant::index) for the current scene and
+    // specialise switch (jit_forget) and the environment it was built under (env, compared by
+    // value): a call then resolves its kernel without rebuilding the option strings (tens of
+    // microseconds per call, which the one-pass-per-call pattern pays every call)
     struct jit_memo_t {
         bool valid = false, zero_exit = false;
         hipFunction_t fn = nullptr;
         int waves = 0;
-        std::string flags, err;
-    } jit_memo[6][2];                   // ([4], [5]: the fused and pass-stream builds for tile lists)
+        bdpt_jit_env env;
+        std::string err;
+    } jit_memo[kJitVariants];
     int last_features = 0;              // BDPT_FEAT_* of the last path-pass launch
     unsigned rand_seed = 0;             // seed of the current MT607 table (rand_ready)
     char err[512] = {0};
@@ -216,7 +219,8 @@ inline int fail(bdpt_ctx* c, int code, const char* fmt, ...) {
             return fail((ctx), BDPT_EHIP, "%s: %s", #call, hipGetErrorString(e_));            \
     } while (0)
 
-// Defined in bdpt_host.cpp, used by bdpt_frame.cpp too (hidden: not part of the library's exports).
+// Defined in bdpt_host.cpp, used by bdpt_frame.cpp and bdpt_jit.cpp too (hidden: not part of the
+// library's exports).
 namespace bdpt_host __attribute__((visibility("hidden"))) {
 // Make the context's stream wait for the last fold: before anything on it touches colors / counter / pixels.
 int join_fold(bdpt_ctx* c);
@@ -226,4 +230,17 @@ void camera_args(const bdpt_ctx* c, const bdpt_camera& cam, bdpt_path_args& a);
 void bvh_args(const bdpt_ctx* c, bdpt_path_args& a);
 // After the stream has drained: BDPT_EHIP once if a units launch left the frame invalid.
 int units_verdict(bdpt_ctx* c);
+// The two planner switches (bdpt_path_env) that the specialised builds depend on as well:
+// BDPT_UNITS at this moment, and BDPT_FUSED_MAX_PASSES as read once per process.
+int units_env();
+int fused_max_passes();
+
+// Defined in bdpt_jit.cpp: the scene-specialised path kernels (what they build is in bdpt_jit_plan.h).
+// The specialised kernel of a variant for the context's scene, compiled on first use; nullptr =
+// the precompiled instance runs (reason in c->jit_err).  Sets c->jit_err / jit_waves / jit_zero_exit.
+hipFunction_t jit_path_kernel(bdpt_ctx* c, const bdpt_jit_variant& v);
+void jit_forget(bdpt_ctx* c);           // the scene or the specialise switch changed: resolve afresh
+void jit_release(bdpt_ctx* c);          // unload the context's code objects (destroy)
+bdpt_jit_env jit_env();                 // the builds' environment inputs, read now
+bool jit_srec_enabled();                // jit_env().srec_enabled()
 }  // namespace bdpt_host

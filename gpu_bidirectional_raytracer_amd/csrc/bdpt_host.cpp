@@ -6,12 +6,12 @@
 // HIP stream.  Every HIP call is checked; failures return BDPT_EHIP with the HIP message in
 // bdpt_last_error() (the reference prints and continues; the host shell decides).
 //
-// Here: contexts, scene upload, run-time compilation, the path passes, multi-device contexts,
-// checkpoints and the display.  The context itself is in bdpt_ctx.h; the frame services (feature
-// buffers, denoiser, reprojection, preview, noise estimate) are in bdpt_frame.cpp.
+// Here: contexts, scene upload, the path passes, multi-device contexts, checkpoints and the
+// display.  The context itself is in bdpt_ctx.h; the run-time compile of the scene-specialised
+// path kernels is in bdpt_jit.cpp, and the frame services (feature buffers, denoiser,
+// reprojection, preview, noise estimate) are in bdpt_frame.cpp.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
-#include <hip/hiprtc.h>
 #include <hip/hip_gl_interop.h>         // hipGraphicsGLRegisterBuffer (the optional display, 8(f)4)
 #include <rccl/rccl.h>                 // types and prototypes only: librccl is opened with dlopen
 #include <math.h>
@@ -19,7 +19,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/stat.h>
 #include <unistd.h>
 #include <algorithm>
 #include <limits>
@@ -62,8 +61,7 @@ extern "C" void bdpt_gamma_thresholds(float thr[256]);
 
 static int upload_scene(bdpt_ctx* c) {
     c->tuner.reset();                                       // re-measure the stream mode
-    for (auto& row : c->jit_memo)                           // the specialised kernels change too
-        for (auto& m : row) m.valid = false;
+    jit_forget(c);                                          // the specialised kernels change too
     const unsigned n = (unsigned)c->spheres.size();
     // queued path passes may still read the scene buffers freed / rewritten below (pooled
     // launches on the pstreams: the last fold follows them all)
@@ -179,7 +177,7 @@ static void release(bdpt_ctx* c) {
         if (s.ev0) (void)hipEventDestroy(s.ev0);
         if (s.ev1) (void)hipEventDestroy(s.ev1);
     }
-    for (hipModule_t m : c->jit_mods) (void)hipModuleUnload(m);
+    jit_release(c);
     for (int b = 0; b < 2; b++) {
         if (c->rb_path_ev[b]) (void)hipEventDestroy(c->rb_path_ev[b]);
         if (c->rb_fold_ev[b]) (void)hipEventDestroy(c->rb_fold_ev[b]);
@@ -191,209 +189,12 @@ static void release(bdpt_ctx* c) {
     if (c->stream) (void)hipStreamDestroy(c->stream);
 }
 
-// ---- scene-specialised path kernels (run-time compiled with hipRTC) -------------------------
-// For scenes of <= 64 spheres (not BVH-traversed) the path kernel is recompiled with the scene folded in
-// (bdpt_kernels.hip BDPT_JIT): the sphere geometry {p, rad^2} as exact hex-float literals and the
-// emitter mask become compile-time constants, so a coordinate difference p - o that several
-// spheres share is formed once per ray (cornell's 9 spheres have 15 distinct coordinates, not
-// 27) and the scalar scene loads go away: +7 % on cornell.  The float operations are the same in
-// the same order, so results are bit-identical to the precompiled kernels
-// (tests/test_gpu_specialize.py).  hipRTC is opened with dlopen; when it is missing or a compile
-// fails, the precompiled instance runs (bdpt_last_specialized() says which one did).  A build that
-// needs scratch (register spills) at 6 waves/SIMD is rebuilt at 5.  Code objects are cached per
-// context and on disk ($BDPT_JIT_CACHE, else $HOME/.cache/bdpt-jit), keyed by a hash of the
-// sources, the options, the hipRTC version and the device's gfx arch; the cache directory must be
-// owned by the user and closed to others (created 0700), else nothing is read from or written to
-// disk.  A compile takes ~1 s.
-#include "bdpt_jit_src.h"
-
-namespace {
-struct rtc_api {
-    bool ok = false;
-    decltype(&hiprtcCreateProgram) create = nullptr;
-    decltype(&hiprtcAddNameExpression) add_name = nullptr;
-    decltype(&hiprtcCompileProgram) compile = nullptr;
-    decltype(&hiprtcGetLoweredName) lowered = nullptr;
-    decltype(&hiprtcGetCodeSize) code_size = nullptr;
-    decltype(&hiprtcGetCode) code = nullptr;
-    decltype(&hiprtcGetProgramLogSize) log_size = nullptr;
-    decltype(&hiprtcGetProgramLog) log = nullptr;
-    decltype(&hiprtcDestroyProgram) destroy = nullptr;
-    int major = 0, minor = 0;                    // hiprtcVersion (part of the cache key)
-};
-
-const rtc_api& rtc() {
-    static const rtc_api api = [] {
-        rtc_api r;
-        const char* libs[] = {"libhiprtc.so.7", "libhiprtc.so", "/opt/rocm/lib/libhiprtc.so.7",
-                              "/opt/rocm/lib/libhiprtc.so"};
-        void* h = nullptr;
-        for (const char* l : libs)
-            if ((h = dlopen(l, RTLD_NOW | RTLD_LOCAL))) break;
-        if (!h) return r;
-#define BDPT_RTC_SYM(f, n) r.f = (decltype(r.f))dlsym(h, n)
-        BDPT_RTC_SYM(create, "hiprtcCreateProgram");
-        BDPT_RTC_SYM(add_name, "hiprtcAddNameExpression");
-        BDPT_RTC_SYM(compile, "hiprtcCompileProgram");
-        BDPT_RTC_SYM(lowered, "hiprtcGetLoweredName");
-        BDPT_RTC_SYM(code_size, "hiprtcGetCodeSize");
-        BDPT_RTC_SYM(code, "hiprtcGetCode");
-        BDPT_RTC_SYM(log_size, "hiprtcGetProgramLogSize");
-        BDPT_RTC_SYM(log, "hiprtcGetProgramLog");
-        BDPT_RTC_SYM(destroy, "hiprtcDestroyProgram");
-#undef BDPT_RTC_SYM
-        auto version = (decltype(&hiprtcVersion))dlsym(h, "hiprtcVersion");
-        r.ok = r.create && r.add_name && r.compile && r.lowered && r.code_size && r.code &&
-               r.log_size && r.log && r.destroy && version &&
-               version(&r.major, &r.minor) == HIPRTC_SUCCESS;
-        return r;
-    }();
-    return api;
-}
-
-uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
-    const unsigned char* b = (const unsigned char*)p;
-    for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ull;
-    return h;
-}
-
-std::string hexf(float v) {                     // exact float literal
-    // %a prints "inf" / "nan", which are no literals: rad * rad overflows from rad = 1.85e19 on
-    if (std::isinf(v)) return v < 0.f ? "(-__builtin_inff())" : "__builtin_inff()";
-    if (v != v) return "__builtin_nanf(\"\")";
-    char b[48];
-    snprintf(b, sizeof b, "%af", (double)v);
-    return b;
-}
-
-// The on-disk cache directory, created 0700 if missing; "" (no disk cache) unless it is a
-// directory owned by this user that neither group nor others can write.
-std::string jit_cache_dir() {
-    std::string dir;
-    if (const char* d = getenv("BDPT_JIT_CACHE")) dir = d;
-    else if (const char* home = getenv("HOME")) dir = std::string(home) + "/.cache/bdpt-jit";
-    else return "";
-    std::string d;                                           // mkdir -p, 0700
-    for (size_t i = 0; i <= dir.size(); i++) {
-        if ((i == dir.size() || dir[i] == '/') && !d.empty()) mkdir(d.c_str(), 0700);
-        if (i < dir.size()) d += dir[i];
-    }
-    struct stat st;
-    if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode) || st.st_uid != getuid() ||
-        (st.st_mode & (S_IWGRP | S_IWOTH)))
-        return "";
-    return dir;
-}
-
-bool read_file(const std::string& path, std::vector<char>& out) {
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) return false;
-    struct stat st;
-    if (fstat(fileno(f), &st) != 0 || st.st_uid != getuid() || !S_ISREG(st.st_mode)) {
-        fclose(f);
-        return false;
-    }
-    out.resize(st.st_size > 0 ? (size_t)st.st_size : 0);
-    const bool ok = st.st_size > 0 && fread(out.data(), 1, out.size(), f) == out.size();
-    fclose(f);
-    return ok;
-}
-
-// Write to a private temporary file and rename it into place only if every byte reached it.
-void write_file_atomic(const std::string& path, const std::vector<char>& data) {
-    const std::string tmp = path + ".tmp." + std::to_string((long)getpid());
-    FILE* f = fopen(tmp.c_str(), "wb");
-    if (!f) return;
-    bool ok = fwrite(data.data(), 1, data.size(), f) == data.size();
-    ok = (fflush(f) == 0) && ok;
-    ok = (fclose(f) == 0) && ok;
-    if (ok) ok = rename(tmp.c_str(), path.c_str()) == 0;
-    if (!ok) unlink(tmp.c_str());
-}
-}  // namespace
-
-// Compile (or fetch from the disk cache) and load one specialised build; nullptr on failure
-// (reason in c->jit_err).
-static hipFunction_t jit_build(bdpt_ctx* c, const std::string& name, const std::vector<std::string>& opts) {
-    const rtc_api& api = rtc();
-    std::string key = name;
-    for (const std::string& o : opts) key += " " + o;
-    const auto it = c->jit_fns.find(key);
-    if (it != c->jit_fns.end()) return it->second;
-
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) {
-        (void)hipGetLastError();
-        snprintf(c->jit_err, sizeof c->jit_err, "hipGetDeviceProperties failed");
-        return nullptr;
-    }
-    uint64_t h = 1469598103934665603ull;
-    h = fnv1a(h, kJitMain, sizeof kJitMain);
-    for (int i = 0; i < kJitNumHeaders; i++) h = fnv1a(h, kJitHeaders[i], strlen(kJitHeaders[i]));
-    h = fnv1a(h, key.data(), key.size());
-    const int ver[2] = {api.major, api.minor};
-    h = fnv1a(h, ver, sizeof ver);
-    h = fnv1a(h, prop.gcnArchName, strnlen(prop.gcnArchName, sizeof prop.gcnArchName));
-    char hex[40];
-    snprintf(hex, sizeof hex, "%016llx", (unsigned long long)h);
-    const std::string dir = jit_cache_dir();
-    const std::string path = dir.empty() ? "" : dir + "/path_" + hex + ".hsaco";
-    const std::string name_path = path + ".name";
-    std::vector<char> code, lowered;
-    if (path.empty() || !read_file(path, code) || !read_file(name_path, lowered)) {
-        hiprtcProgram prog = nullptr;
-        if (api.create(&prog, kJitMain, kJitMainName, kJitNumHeaders, kJitHeaders, kJitHeaderNames) != HIPRTC_SUCCESS) {
-            snprintf(c->jit_err, sizeof c->jit_err, "hiprtcCreateProgram failed");
-            return nullptr;
-        }
-        api.add_name(prog, name.c_str());
-        std::vector<const char*> o;
-        for (const std::string& x : opts) o.push_back(x.c_str());
-        const hiprtcResult rc = api.compile(prog, (int)o.size(), o.data());
-        const char* low = nullptr;
-        size_t sz = 0;
-        if (rc != HIPRTC_SUCCESS || api.lowered(prog, name.c_str(), &low) != HIPRTC_SUCCESS || !low ||
-            api.code_size(prog, &sz) != HIPRTC_SUCCESS || sz == 0) {
-            size_t ls = 0;
-            std::string log;
-            if (api.log_size(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
-                log.resize(ls);
-                api.log(prog, &log[0]);
-            }
-            snprintf(c->jit_err, sizeof c->jit_err, "hipRTC compile failed: %.200s", log.c_str());
-            api.destroy(&prog);
-            return nullptr;
-        }
-        code.resize(sz);
-        api.code(prog, code.data());
-        lowered.assign(low, low + strlen(low) + 1);
-        api.destroy(&prog);
-        if (!path.empty()) {
-            write_file_atomic(path, code);
-            write_file_atomic(name_path, lowered);
-        }
-    }
-    if (lowered.empty() || lowered.back() != '\0') lowered.push_back('\0');
-    hipModule_t mod = nullptr;
-    hipFunction_t fn = nullptr;
-    if (hipModuleLoadData(&mod, code.data()) != hipSuccess ||
-        hipModuleGetFunction(&fn, mod, lowered.data()) != hipSuccess) {
-        if (mod) (void)hipModuleUnload(mod);
-        (void)hipGetLastError();
-        snprintf(c->jit_err, sizeof c->jit_err, "loading the specialised code object failed");
-        return nullptr;
-    }
-    c->jit_mods.push_back(mod);
-    c->jit_fns[key] = fn;
-    return fn;
-}
-
 // Passes per launch of the fused S = 1 kernel.  Its workgroups stage a VLP (48 B) and a sid per
 // pass of the launch in LDS: 128 passes make 31.5 KB per workgroup.  Measured on caustic8 (one
 // session, two rounds, profiles/r03_s1_ab_fused.txt): 64 passes at 5 waves/SIMD (4-KB sincos
 // table) 48.8 Gs/s, 64 at 6 (2-KB table) 48.55, 128 at 6 48.2, 128 at 5 (round 2) 47.9.
 // BDPT_FUSED_MAX_PASSES overrides.
-static int fused_max_passes() {
+int bdpt_host::fused_max_passes() {
     static const int cap = [] {
         const char* e = getenv("BDPT_FUSED_MAX_PASSES");
         const int v = e ? atoi(e) : 64;
@@ -413,11 +214,9 @@ static int pool_env() {
     return v < 1 ? 0 : (v > 64 ? 64 : v);
 }
 
-// The specialised kernel for the context's scene and pass-stream mode, compiled on first use;
-// nullptr = use the precompiled instance (reason in c->jit_err).
 // Pass streams with the ordered fold inside the kernel (bdpt_kernels.hip BDPT_UNITS): BDPT_UNITS=P
 // forces it with ranges of P passes (experiments; 0 = never).
-static int units_env() {
+int bdpt_host::units_env() {
     const char* e = getenv("BDPT_UNITS");
     if (!e || !*e) return -1;
     const int v = atoi(e);
@@ -441,157 +240,6 @@ static bdpt_path_env path_env() {
     if (const char* v = getenv("BDPT_POOL_GRID")) e.pool_grid = std::min(atoi(v), 256);
     if (const char* v = getenv("BDPT_SMEM_PAD")) e.smem_pad = atoi(v);
     return e;
-}
-
-static hipFunction_t jit_path_kernel_build(bdpt_ctx* c, bool streams, bool pair, bool pool, bool units, bool tiles) {
-    const unsigned n = (unsigned)c->spheres.size();
-    if (!c->specialize || n < 1 || n > 64) return nullptr;          // kJitEmis is 64 bits
-    unsigned long long emis = 0;
-    for (unsigned i = 0; i < n; i++) {
-        const bdpt_vec& e = c->spheres[i].e;
-        if (!(e.x == 0.f && e.y == 0.f && e.z == 0.f)) emis |= 1ull << i;
-    }
-    if (!rtc().ok) {
-        snprintf(c->jit_err, sizeof c->jit_err, "hipRTC not found");
-        return nullptr;
-    }
-    std::string geom = "{";
-    for (unsigned i = 0; i < n; i++) {
-        const bdpt_sphere& sp = c->spheres[i];
-        const float rr = sp.rad * sp.rad;                    // as upload_scene forms it
-        geom += (i ? ",{" : "{") + hexf(sp.p.x) + "," + hexf(sp.p.y) + "," + hexf(sp.p.z) + "," + hexf(rr) + "}";
-    }
-    geom += "}";
-    // Black-surface exit (bdpt_kernels.hip BDPT_ZERO_EXIT): compiled in only when ending a path at
-    // a black non-emitter is provably exact for this scene (bdpt_util.c bdpt_zero_exit_safe).
-    const bool zero_exit = bdpt_zero_exit_safe(c->spheres.data(), n) != 0;
-    // Waves/SIMD the build targets: 6 for the pass-stream kernel, 5 for the fused S = 1 kernel
-    // (at 6 it fits without spills, but then the LDS formula below takes the 2-KB sincos table and
-    // caustic8 measured 0.6 % slower than 5 waves with the 4-KB table; fused_max_passes()).
-    const char* wenv = getenv(streams ? "BDPT_JIT_WAVES" : "BDPT_JIT_FUSED_WAVES");
-    int waves = wenv ? atoi(wenv) : (streams ? 6 : 5);
-    // (a launch over a tile list runs the instance with the tile-list code, bdpt_kernels.hip)
-    const std::string name = std::string(tiles ? "&bdpt_path_tiles_kernel_t<" : "&bdpt_path_kernel_t<") + std::to_string(n) +
-                             (streams ? ", true>" : ", false>");   // (BDPT_TILES=1 below gives the kernel that name)
-    const char* jflags = getenv("BDPT_JIT_FLAGS");
-    const bool user_coarse = jflags && strstr(jflags, "BDPT_SC_COARSE");   // experiments decide
-    bool coarse = false, pf_off = false;
-    for (;; waves--) {
-        const std::vector<std::string> opts = {
-            "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-            "-fno-gpu-flush-denormals-to-zero", "-DBDPT_JIT=1", "-DBDPT_JIT_N=" + std::to_string(n),
-            "-DBDPT_JIT_EMIS=" + std::to_string(emis) + "ull", "-DBDPT_JIT_GEOM=" + geom,
-            "-DBDPT_JIT_ZERO_SAFE=" + std::to_string(zero_exit ? 1 : 0),
-            "-DBDPT_WAVES_PER_SIMD=" + std::to_string(waves)};
-        std::vector<std::string> all = opts;
-        if (!streams) all.push_back("-DBDPT_FUSED_WAVES=" + std::to_string(waves));
-        if (!streams && !pair) all.push_back("-DBDPT_RNG_PAIR=0");
-        if (streams && pool) all.push_back("-DBDPT_POOL=1");
-        if (streams && units) all.push_back("-DBDPT_UNITS=1");
-        if (tiles) all.push_back("-DBDPT_TILES=1");
-        // VLP-only part-full shadow rounds over the non-emitters' list (BDPT_VAC_LIST): only where
-        // dropping the emitters saves a lane-group iteration (cornell: 8 of 9 spheres fit 4, 2, 1
-        // iterations instead of 5, 3, 2); elsewhere the staging costs (synthetic64 -0.4 %,
-        // profiles/r06_s24_ab_vac_list.txt)
-        bool vac_list = false;
-        for (unsigned k = 1; k <= 3; k++)
-            if ((1u << k) <= c->n_vac && (c->n_vac + (1u << k) - 1) >> k < (n + (1u << k) - 1) >> k) vac_list = true;
-        if (!vac_list) all.push_back("-DBDPT_VAC_LIST=0");
-        // Part-full shadow rounds as straight-line code (bdpt_kernels.hip BDPT_PF_UNROLL, on by
-        // default in these builds; BDPT_JIT_FLAGS below sets it either way): not in the pixel-pool
-        // build, which has not been measured with it, and not where the build with it spills at
-        // more than 5 waves/SIMD (pf_off, below: the bodies change the register allocation of the
-        // whole loop, and the in-kernel fold build of synthetic64 then needs scratch at 6)
-        const bool pf_user = jflags && strstr(jflags, "BDPT_PF_UNROLL");
-        if (!pf_user && ((streams && pool) || pf_off)) all.push_back("-DBDPT_PF_UNROLL=0");
-        if (const char* extra = getenv("BDPT_JIT_FLAGS")) {    // experiments: extra -D options
-            std::string tok;
-            for (const char* q = extra;; q++) {
-                if (*q == ' ' || *q == ',' || *q == 0) {
-                    if (!tok.empty()) all.push_back(tok);
-                    tok.clear();
-                    if (!*q) break;
-                } else {
-                    tok += *q;
-                }
-            }
-        }
-        if (coarse) all.push_back("-DBDPT_SC_COARSE=1");
-        hipFunction_t fn = jit_build(c, name, all);
-        if (!fn) return nullptr;
-        // The 4-KB sincos table costs a workgroup per CU when LDS bounds the count (large
-        // scenes: 16 B per sphere; the fused kernel: a VLP and a sid per pass of the launch);
-        // then take the 2-KB table of even entries (bdpt_math.h).  Estimated with the launches'
-        // LDS formula (bdpt_plan.h) over a table of 5 per sphere: one pass slot for the pass-stream kernel, fused_max_passes() for the fused.
-        int stat = 0;
-        if (!coarse && !user_coarse &&
-            hipFuncGetAttribute(&stat, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, fn) == hipSuccess) {
-            const size_t slots = units ? (size_t)std::max(units_env(), 16) : streams ? 1 : (size_t)fused_max_passes();
-            const size_t dyn = bdpt_path_smem(5 * (size_t)n, slots, 0, 0);
-            const size_t lds = 160 * 1024, fine = lds / (dyn + stat), half = lds / (dyn + stat - 2048);
-            if (fine < (size_t)waves && half > fine) {
-                coarse = true;
-                waves++;                                      // same wave count, coarse table
-                continue;
-            }
-        }
-        (void)hipGetLastError();
-        int scratch = 0;
-        if (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, fn) != hipSuccess) {
-            (void)hipGetLastError();
-            scratch = 0;
-        }
-        // a build that spills above the floor is tried once more at the same wave count with the
-        // lane-group loop in place of the straight-line part-full rounds
-        if (scratch != 0 && waves > 5 && !pf_off && !pf_user && !(streams && pool) && !getenv("BDPT_JIT_SCRATCH_OK")) {
-            pf_off = true;
-            waves++;
-            continue;
-        }
-        // spill-free, or the 5-wave floor (BDPT_JIT_SCRATCH_OK: keep a spilling build; experiments)
-        if (scratch == 0 || waves <= 5 || getenv("BDPT_JIT_SCRATCH_OK")) {
-            c->jit_err[0] = 0;
-            c->jit_waves = waves;
-            c->jit_zero_exit = zero_exit;
-            return fn;
-        }
-    }
-}
-
-static void jit_forget(bdpt_ctx* c) {                   // the scene or the specialise switch changed
-    for (auto& row : c->jit_memo)
-        for (auto& m : row) m.valid = false;
-}
-
-// Every environment input of jit_path_kernel_build, as one memo key: an in-process A/B that
-// changes any of them gets a fresh build (BDPT_FUSED_MAX_PASSES is read once per process).
-static std::string jit_env_key() {
-    std::string k;
-    for (const char* v : {"BDPT_JIT_FLAGS", "BDPT_JIT_WAVES", "BDPT_JIT_FUSED_WAVES", "BDPT_JIT_SCRATCH_OK"}) {
-        const char* e = getenv(v);
-        k += e ? e : "";
-        k += '\x1f';
-    }
-    return k;
-}
-
-static hipFunction_t jit_path_kernel(bdpt_ctx* c, bool streams, bool pair = true, bool pool = false,
-                                     bool units = false, bool tiles = false) {
-    const std::string key = jit_env_key();
-    bdpt_ctx::jit_memo_t& m = c->jit_memo[tiles ? (streams ? 5 : 4) : streams ? (units ? 3 : pool ? 2 : 1) : 0][pair];
-    if (m.valid && m.flags == key) {
-        snprintf(c->jit_err, sizeof c->jit_err, "%s", m.err.c_str());
-        if (m.fn) { c->jit_waves = m.waves; c->jit_zero_exit = m.zero_exit; }
-        return m.fn;
-    }
-    hipFunction_t fn = jit_path_kernel_build(c, streams, pair, streams && pool, streams && units, tiles);
-    m.valid = true;
-    m.fn = fn;
-    m.waves = c->jit_waves;
-    m.zero_exit = c->jit_zero_exit;
-    m.flags = key;
-    m.err = c->jit_err;
-    return fn;
 }
 
 // Make the context's stream wait for the last pass-stream fold (issued on fstream): call before
@@ -935,19 +583,6 @@ static int ensure_srec(bdpt_ctx* c) {
     return BDPT_OK;
 }
 
-// Whether the specialised pass-stream kernels are built with sample records (bdpt_kernels.hip
-// BDPT_SREC, on by default in those builds): an experiment's -DBDPT_SREC=0 in BDPT_JIT_FLAGS turns
-// them off, and the host must then hand those kernels the sin/cos planes.
-static bool jit_srec_enabled() {
-    const char* f = getenv("BDPT_JIT_FLAGS");
-    bool on = true;
-    for (const char* q = f ? strstr(f, "-DBDPT_SREC") : nullptr; q; q = strstr(q + 1, "-DBDPT_SREC")) {
-        const char* v = q + strlen("-DBDPT_SREC");
-        on = *v == '=' ? atoi(v + 1) != 0 : true;
-    }
-    return on;
-}
-
 static int one_light_pass(bdpt_ctx* c, int current_sample) {
     if (!c) return BDPT_EINVAL;
     if (c->cpu) {
@@ -1127,6 +762,15 @@ struct path_kernels {
 // Resolve the specialised kernels (a compile on first use) and build the derived table the call's
 // pass-stream kernels read, both before the timed region starts.
 static int resolve_path_kernels(bdpt_ctx* c, const bdpt_plan& plan, int npass, bdpt_path_args& a, path_kernels& k) {
+    // a kind's variant for this call: over the call's tile list if it has one (a masked call never
+    // wants pools or units, bdpt_plan.h), the fused kernel with the planned pairing
+    auto variant = [&plan](int kind) {
+        bdpt_jit_variant v;
+        v.kind = kind;
+        v.pair = kind == BDPT_KERNEL_FUSED ? plan.pair : true;
+        v.tiles = plan.ntiles >= 0;
+        return v;
+    };
     for (int p0 = 0; plan.launches > 0 && p0 < npass; p0 += plan.chunk) {
         const int np = npass - p0 < plan.chunk ? npass - p0 : plan.chunk;
         const bool st = (plan.S < np ? plan.S : np) > 1;
@@ -1134,12 +778,11 @@ static int resolve_path_kernels(bdpt_ctx* c, const bdpt_plan& plan, int npass, b
         k.any_streams |= st;
         if (plan.bvh) continue;
         hipFunction_t& pool = k.jf[BDPT_KERNEL_POOL], &units = k.jf[BDPT_KERNEL_UNITS];
-        if (st && plan.want_pool && !pool) pool = jit_path_kernel(c, true, true, true);
-        if (st && plan.want_units && !units) units = jit_path_kernel(c, true, true, false, true);
-        const bool tiles = plan.ntiles >= 0;
+        if (st && plan.want_pool && !pool) pool = jit_path_kernel(c, variant(BDPT_KERNEL_POOL));
+        if (st && plan.want_units && !units) units = jit_path_kernel(c, variant(BDPT_KERNEL_UNITS));
         if (st && !pool && !units && !k.jf[BDPT_KERNEL_STREAMS])
-            k.jf[BDPT_KERNEL_STREAMS] = jit_path_kernel(c, true, true, false, false, tiles);
-        if (!st && !k.jf[BDPT_KERNEL_FUSED]) k.jf[BDPT_KERNEL_FUSED] = jit_path_kernel(c, false, plan.pair, false, false, tiles);
+            k.jf[BDPT_KERNEL_STREAMS] = jit_path_kernel(c, variant(BDPT_KERNEL_STREAMS));
+        if (!st && !k.jf[BDPT_KERNEL_FUSED]) k.jf[BDPT_KERNEL_FUSED] = jit_path_kernel(c, variant(BDPT_KERNEL_FUSED));
     }
     // the derived table (the pooled build reads neither): sample records for a specialised build
     // that has them, else the sin/cos planes -- built if the table changed since they last were

@@ -54,7 +54,7 @@ namespace {
 //                   the closest hit is one v_min3_u32 per sphere, a shadow test one unsigned
 //                   compare.  Rule checked by tests/test_ikey_rule.py.  profiles/r03_s33_ab_ikey.txt
 //  BDPT_SREC        pre 0, jit 1.  tests/test_gpu_sample_records.py builds =0; the host reads the
-//                   flag back (bdpt_host.cpp jit_srec_enabled) to fill the right table.  Pass streams
+//                   flag back (bdpt_jit_plan.h srec_enabled) to fill the right table.  Pass streams
 //                   without pixel pools load one 32-B sample record per segment
 //                   (bdpt_sample_records_kernel, bdpt_math.h bdpt_sample_record): the cosine
 //                   direction's three coefficients and the NEE light sample, computed once per

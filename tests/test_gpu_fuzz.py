@@ -2,7 +2,7 @@
 kernel kinds) against the oracle, bit for bit.  The reference scenes fix a few geometries; these
 vary what the specialised kernels' exact shortcuts depend on: wall boxes of radius 1e3 to 1e5
 (det skips only for the small spheres), black surfaces with and without the host's black-exit
-proof (bdpt_host.cpp jit_path_kernel), zero to three emitters, every material (DIFF, SPEC, REFR,
+proof (bdpt_jit.cpp jit_path_kernel), zero to three emitters, every material (DIFF, SPEC, REFR,
 the LITE tag), spheres that overlap or contain the camera, and cameras inside and outside the
 box.  Reference: device.cu:80-154 (sphere tests), :457-542 (NEE + VLP), :544-791 (path)."""
 import os

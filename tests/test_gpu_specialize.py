@@ -1,5 +1,5 @@
 """Scene-specialised path kernels (run-time compiled with the sphere geometry folded in,
-bdpt_host.cpp jit_path_kernel) give bit-identical frames to the precompiled kernels, with and
+bdpt_jit.cpp jit_path_kernel) give bit-identical frames to the precompiled kernels, with and
 without pass streams, on every scene kind the specialisation covers (1..64 spheres, one or
 several emitters, refractive / specular / diffuse)."""
 import os

@@ -1,4 +1,4 @@
-"""Scene-specialised kernels (bdpt_host.cpp jit_path_kernel) on the CPU: the sources embedded in
+"""Scene-specialised kernels (bdpt_jit.cpp jit_path_kernel) on the CPU: the sources embedded in
 libbdpt.so are the current csrc/ files, and an offline hipcc build of the specialised source
 (tools/jit_codegen_check.py, same options as the run-time compile) succeeds for several scenes
 within the 80-VGPR / 6-wave bound, without spilling, and without any write through the scalar
