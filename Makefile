@@ -142,7 +142,7 @@ endif
 ASAN_FLAGS := -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -g -O1 -ffp-contract=off
 ASAN_DIR   := tests/native/_asan
 asan: $(ASAN_DIR)/smallpt_asan $(ASAN_DIR)/oracle_asan $(ASAN_DIR)/aov_asan $(ASAN_DIR)/denoise_asan $(ASAN_DIR)/reproject_asan \
-      $(ASAN_DIR)/preview_asan $(ASAN_DIR)/noise_asan $(ASAN_DIR)/tiles_asan
+      $(ASAN_DIR)/preview_asan $(ASAN_DIR)/noise_asan $(ASAN_DIR)/tiles_asan $(ASAN_DIR)/denoise_noise_asan
 
 $(ASAN_DIR):
 	mkdir -p $(ASAN_DIR)
@@ -157,7 +157,9 @@ $(ASAN_DIR)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h |
 # tests/native/asan_cpu_abi.cpp.  It used to be a chain of files, each including the one before and
 # adding a service's entry points, with asan_cpu_abi_noise.cpp on top; a tests/ tree that still has
 # the chain (the sanitizer tests as they stood before the layer became one file) builds its top.
-ASAN_ABI_SRC := $(firstword $(wildcard tests/native/asan_cpu_abi_noise.cpp) tests/native/asan_cpu_abi.cpp)
+# asan_cpu_abi_denoise_noise.cpp is the top now: it includes asan_cpu_abi_noise.cpp and adds
+# bdpt_denoise_noise (smallpt --denoise-noise).
+ASAN_ABI_SRC := $(firstword $(wildcard tests/native/asan_cpu_abi_denoise_noise.cpp) $(wildcard tests/native/asan_cpu_abi_noise.cpp) tests/native/asan_cpu_abi.cpp)
 $(ASAN_DIR)/asan_cpu_abi.o: $(ASAN_ABI_SRC) $(wildcard tests/native/asan_cpu_abi*.cpp) $(CSRC)/bdpt_cpu.h include/bdpt.h | $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -std=c++17 -c $< -o $@
 
@@ -189,6 +191,10 @@ $(ASAN_DIR)/preview_asan: tests/native/preview_asan.cpp $(CSRC)/bdpt_cpu.h inclu
 
 # the CPU backend's noise estimate (bdpt_cpu_noise_*) driven directly; tests/test_noise_asan.py
 $(ASAN_DIR)/noise_asan: tests/native/noise_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
+	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
+
+# the CPU backend's noise-guided denoiser (bdpt_cpu_denoise_noise) driven directly; tests/test_denoise_noise_asan.py
+$(ASAN_DIR)/denoise_noise_asan: tests/native/denoise_noise_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
 	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
 
 # the CPU backend's masked path passes (bdpt_cpu_path_passes with a tile mask) driven directly; tests/test_tiles_asan.py

@@ -19,7 +19,7 @@ import numpy as np
 
 from ._lib import (BDPT_OK, CHOICES, COUNTER_CAP, DEFAULT_DAT, DIFF, FEATURES, KEY_DOWN, KEY_LEFT, KEY_PAGE_DOWN,
                    KEY_PAGE_UP, KEY_RIGHT, KEY_UP, LIGHT_POINTS, LITE, RAND_N, REFR, SCENE_DIR, SPEC,
-                   DENOISE_MATERIALS, AovBuffers, BdptError, Camera, DenoiseParams, LightPath, NoiseParams, NoiseSummary, PassState, PreviewParams,
+                   DENOISE_MATERIALS, AovBuffers, BdptError, Camera, DenoiseNoiseParams, DenoiseParams, LightPath, NoiseParams, NoiseSummary, PassState, PreviewParams,
                    RandState, ReprojectParams, Sphere, Vec, lib)
 
 __all__ = [
@@ -659,6 +659,37 @@ class Renderer:
         self._chk(lib.bdpt_last_noise_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
+    # -- noise-guided denoiser (no reference counterpart; include/bdpt.h bdpt_denoise_noise)
+    def denoise_noise(self, levels: int = 4, normal_power: int = 5, sigma_color: float = 0.5,
+                      noise_sigma: float = 1.0, materials: str = "diffuse", pixels: bool = False,
+                      variance: bool = False):
+        """denoise() with a colour stop that follows the measured noise: where the mark (noise_mark,
+        or noise_estimate(remark=True)) gives a pixel a variance estimate -- |B - A|^2 mn / (cnt - mn),
+        valid as for noise_estimate, averaged over the 5 x 5 neighbours on the same sphere -- two
+        pixels' colours stop each other by t / (t + |dc|^2) with t = noise_sigma^2 (v_p + v_q) + 1e-12,
+        and the variance is carried through the levels; where it does not, by denoise()'s
+        sigma_color.  A converged frame is therefore left alone and a noisy one filtered hard.
+        Without a mark, or with one that is valid nowhere, the result is denoise()'s, bit for bit.
+        Returns the [H, W, 3] float32 frame; with pixels=True and / or variance=True a tuple
+        (frame[, rgba [H, W, 4] uint8][, variance [H, W] float32, -1 where there is none]).  Reads
+        the accumulation, the counters and the mark; changes nothing of the context."""
+        prm = DenoiseNoiseParams(int(levels), int(normal_power), float(sigma_color), DENOISE_MATERIALS[materials],
+                                 float(noise_sigma))
+        col = np.empty((self.height, self.width, 3), np.float32)
+        px = np.empty((self.height, self.width, 4), np.uint8) if pixels else None
+        var = np.empty((self.height, self.width), np.float32) if variance else None
+        self._chk(lib.bdpt_denoise_noise(self._h, ctypes.byref(prm), _ptr(col), _ptr(px) if pixels else None,
+                                         _ptr(var) if variance else None))
+        if not pixels and not variance:
+            return col
+        return (col,) + ((px,) if pixels else ()) + ((var,) if variance else ())
+
+    def last_denoise_noise_ms(self) -> float:
+        """Device time (ms) of the last denoise_noise call's kernels alone, without the read-back."""
+        ms = ctypes.c_float()
+        self._chk(lib.bdpt_last_denoise_noise_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
     def device_buffers(self) -> Tuple[int, int, int]:
         c, n, p = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         self._chk(lib.bdpt_device_buffers(self._h, ctypes.byref(c), ctypes.byref(n), ctypes.byref(p)))
@@ -761,7 +792,8 @@ class SmallPT:
             self.UpdateRendering(npass, tiles)
 
     def RenderUntil(self, threshold: float = 0.05, max_passes: int = 4096, batch: int = 8,
-                    dark: float = 0.01, pixels: bool = False, adaptive: bool = False, min_passes: int = 0) -> dict:
+                    dark: float = 0.01, pixels: bool = False, adaptive: bool = False, min_passes: int = 0,
+                    denoise: bool = False, **denoise_params) -> dict:
         """Render until the frame is good enough instead of a fixed number of passes (no reference
         counterpart): IdleFunc(batch), then Renderer.noise_estimate(remark=True), repeated.  Stops
         as converged when some pixel is valid, none is pending and no tile's error is over
@@ -781,17 +813,32 @@ class SmallPT:
         current_sample a tile retired at, 0: not retired), retired_error (float32, its error then)
         and pixel_passes (the sum over batches of batch x pixels rendered).  The frame is noisier
         than the unmasked one at the same stop: that one oversamples the easy tiles (DESIGN.md 4h;
-        min_passes guards tiles that look settled after very few passes)."""
+        min_passes guards tiles that look settled after very few passes).
+
+        denoise=True also returns the frame through the noise-guided filter as `denoised`
+        (Renderer.denoise_noise(**denoise_params); its variance plane as `denoised_variance`).  A pixel that has just re-marked has no fresh
+        samples and so no variance estimate, so on this path every check estimates with remark=False
+        first; when the loop is about to stop it filters and returns, with the mark the filter
+        used still in place, otherwise it repeats the estimate with remark=True.  Passes, estimate
+        and frame are those of the call without it.  Not with adaptive=True."""
         if batch < 1:
             raise ValueError("batch must be >= 1")
+        if denoise and adaptive:
+            raise ValueError("denoise=True is not available with adaptive=True")
+        if denoise_params and not denoise:
+            raise TypeError(f"unexpected arguments without denoise=True: {sorted(denoise_params)}")
         if adaptive:
             return self._render_until_adaptive(threshold, max_passes, batch, dark, pixels, min_passes)
         while True:
             self.IdleFunc(batch)
-            est = self.renderer.noise_estimate(dark=dark, threshold=threshold, remark=True, pixels=pixels)
+            est = self.renderer.noise_estimate(dark=dark, threshold=threshold, remark=not denoise, pixels=pixels)
             converged = est["valid_pixels"] > 0 and est["pending_pixels"] == 0 and est["tiles_over"] == 0
             if converged or self.current_sample >= max_passes:
+                if denoise:
+                    est["denoised"], est["denoised_variance"] = self.renderer.denoise_noise(variance=True, **denoise_params)
                 break
+            if denoise:
+                self.renderer.noise_estimate(dark=dark, threshold=threshold, remark=True)
         est["passes"] = self.current_sample
         est["converged"] = bool(converged)
         return est
@@ -909,12 +956,15 @@ class SmallPT:
         save_ppm(path, self.pixels(), binary)
         return path
 
-    def SaveDenoisedPPM(self, path: Optional[str] = None, binary: bool = False, **params) -> str:
+    def SaveDenoisedPPM(self, path: Optional[str] = None, binary: bool = False, noise: bool = False, **params) -> str:
         """SavePPM of the denoised frame (Renderer.denoise(**params)); without a path, SavePPM's
-        file name with `_denoised` before `.ppm`."""
+        file name with `_denoised` before `.ppm`.  noise=True: of the noise-guided filter's frame
+        (Renderer.denoise_noise(**params)), named `_denoised_noise`."""
         if path is None:
-            path = ppm_name(self.total_time, self.current_sample)[:-len(".ppm")] + "_denoised.ppm"
-        _, px = self.renderer.denoise(pixels=True, **params)
+            suffix = "_denoised_noise.ppm" if noise else "_denoised.ppm"
+            path = ppm_name(self.total_time, self.current_sample)[:-len(".ppm")] + suffix
+        call = self.renderer.denoise_noise if noise else self.renderer.denoise
+        _, px = call(pixels=True, **params)
         save_ppm(path, px, binary)
         return path
 

@@ -59,6 +59,12 @@ class DenoiseParams(ctypes.Structure):
                 ("materials", ctypes.c_int)]
 
 
+class DenoiseNoiseParams(ctypes.Structure):
+    """bdpt_denoise_noise_params."""
+    _fields_ = [("levels", ctypes.c_int), ("normal_power", ctypes.c_int), ("sigma_color", ctypes.c_float),
+                ("materials", ctypes.c_int), ("noise_sigma", ctypes.c_float)]
+
+
 DENOISE_MATERIALS = {"diffuse": 0, "all": 1}               # BDPT_DENOISE_DIFFUSE / BDPT_DENOISE_ALL
 
 
@@ -182,6 +188,8 @@ _SIGS = [
     ("bdpt_noise_estimate", ctypes.c_int, [_P, ctypes.POINTER(NoiseParams), _P, _P, _P, ctypes.POINTER(NoiseSummary)]),
     ("bdpt_noise_tile_pending", ctypes.c_int, [_P, _P]),
     ("bdpt_last_noise_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
+    ("bdpt_denoise_noise", ctypes.c_int, [_P, ctypes.POINTER(DenoiseNoiseParams), _P, _P, _P]),
+    ("bdpt_last_denoise_noise_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_gl_register_pbo", ctypes.c_int, [_P, ctypes.c_uint]),
     ("bdpt_gl_publish", ctypes.c_int, [_P]),
     ("bdpt_gl_unregister", ctypes.c_int, [_P]),

@@ -944,6 +944,129 @@ bool bdpt_cpu_noise_tile_pending(const bdpt_cpu_ctx* c, unsigned* tile_pending) 
     return true;
 }
 
+// Noise-guided denoiser (include/bdpt.h bdpt_denoise_noise): a plain restatement of
+// the definition there -- the raw variance from the mark, its 5x5 prefilter, then bdpt_denoise's
+// levels with the colour stop scaled by the two pixels' variances and the variance carried along.
+// fp32, no contraction, in exactly this order; the HIP kernels (bdpt_dnoise_pack_kernel,
+// bdpt_dnoise_prefilter_kernel, bdpt_dnoise_level_t) form the same bits.  Threaded over rows.
+void bdpt_cpu_denoise_noise(const bdpt_cpu_ctx* c, const bdpt_denoise_noise_params* p, bdpt_vec* colors_out,
+                            unsigned char* rgba_out, float* variance_out) {
+    const int W = c->W, H = c->H;
+    const size_t np = (size_t)W * H;
+    std::vector<int> id(np);
+    std::vector<bdpt_vec> nrm(np);
+    bdpt_aov_buffers g;
+    memset(&g, 0, sizeof g);
+    g.id = id.data();
+    g.normal = nrm.data();
+    bdpt_cpu_render_aov(c, 0, 0, W, H, 0, 0u, &g);
+    for (size_t i = 0; i < np; i++)                       // an ineligible pixel: id -1
+        if (id[i] >= 0 && p->materials == BDPT_DENOISE_DIFFUSE && c->scene.s[id[i]].refl != BDPT_DIFF) id[i] = -1;
+    static const float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
+    const bool stored = !c->mark.empty();
+    std::vector<float> v0(np), var(np), vnext(np);
+    for (size_t i = 0; i < np; i++) {                     // the raw variance
+        const unsigned cnt = c->counter[i], mn = stored ? c->mark[i].n : 0u;
+        v0[i] = -1.0f;
+        if (mn > 0u && cnt > mn && 2ull * (cnt - mn) >= mn) {
+            const V3 d = of(c->colors[i]) - of(c->mark[i].c);
+            const float a = (float)mn, n = (float)cnt;
+            v0[i] = dot(d, d) * (a / (n - a));
+        }
+    }
+    parallel_rows(0, H, c->threads, [&](int y) {          // the prefilter
+        for (int x = 0; x < W; x++) {
+            const size_t i = (size_t)y * W + x;
+            var[i] = v0[i];
+            if (id[i] < 0) continue;
+            float sv = 0.f, sh = 0.f;
+            bool used = false;
+            for (int j = 0; j < 5; j++) {
+                const int qy = y + (j - 2);
+                if (qy < 0 || qy >= H) continue;
+                for (int t = 0; t < 5; t++) {
+                    const int qx = x + (t - 2);
+                    if (qx < 0 || qx >= W) continue;
+                    const size_t q = (size_t)qy * W + qx;
+                    if (id[q] != id[i] || v0[q] < 0.f) continue;
+                    sv = sv + (hk[j] * hk[t]) * v0[q];
+                    sh = sh + hk[j] * hk[t];
+                    used = true;
+                }
+            }
+            var[i] = used ? sv / sh : -1.0f;
+        }
+    });
+    const float isc0 = 1.0f / (p->sigma_color * p->sigma_color);
+    const float s2 = p->noise_sigma * p->noise_sigma, eps = BDPT_DENOISE_NOISE_EPS;
+    std::vector<bdpt_vec> ping(c->colors), pong(np);
+    for (int k = 0; k < p->levels; k++) {
+        const int s = 1 << k;
+        const float isc = isc0 * (float)(1 << (2 * k));
+        const bdpt_vec* cur = ping.data();
+        bdpt_vec* out = pong.data();
+        parallel_rows(0, H, c->threads, [&](int y) {
+            for (int x = 0; x < W; x++) {
+                const size_t i = (size_t)y * W + x;
+                const bdpt_vec cp = cur[i];
+                const float v_p = var[i];
+                if (id[i] < 0) {
+                    out[i] = cp;
+                    vnext[i] = v_p;
+                    continue;
+                }
+                const bool has_p = !(v_p < 0.f);
+                const V3 n_p = of(nrm[i]);
+                float sw = 0.f, sv = 0.f;
+                V3 sc = v3(0.f, 0.f, 0.f);
+                for (int j = 0; j < 5; j++) {
+                    const int qy = y + (j - 2) * s;
+                    if (qy < 0 || qy >= H) continue;
+                    for (int t = 0; t < 5; t++) {
+                        const int qx = x + (t - 2) * s;
+                        if (qx < 0 || qx >= W) continue;
+                        const size_t q = (size_t)qy * W + qx;
+                        if (id[q] != id[i]) continue;
+                        const float d = dot(n_p, of(nrm[q]));
+                        float wn = d > 0.f ? d : 0.f;
+                        for (int r = 0; r < p->normal_power; r++) wn = wn * wn;
+                        const V3 cq = of(cur[q]);
+                        const V3 dc = cq - of(cp);
+                        const float e2 = dot(dc, dc);
+                        const float v_q = var[q];
+                        const bool has_q = !(v_q < 0.f);
+                        float wc;
+                        if (has_p && has_q) {
+                            const float tt = s2 * (v_p + v_q) + eps;
+                            wc = tt * (1.f / (tt + e2));
+                        } else {
+                            wc = 1.f / (1.f + e2 * isc);
+                        }
+                        const float w = ((hk[j] * hk[t]) * wn) * wc;
+                        sw = sw + w;
+                        sc = sc + w * cq;
+                        if (has_p) sv = sv + (w * w) * (has_q ? v_q : v_p);
+                    }
+                }
+                const float r = 1.f / sw;
+                out[i] = {sc.x * r, sc.y * r, sc.z * r};
+                vnext[i] = has_p ? (sv * r) * r : v_p;
+            }
+        });
+        ping.swap(pong);
+        var.swap(vnext);
+    }
+    if (colors_out) memcpy(colors_out, ping.data(), sizeof(bdpt_vec) * np);
+    if (variance_out) memcpy(variance_out, var.data(), sizeof(float) * np);
+    if (rgba_out)
+        for (size_t i = 0; i < np; i++) {
+            rgba_out[4 * i] = (unsigned char)to_int8(ping[i].x, c->thr);
+            rgba_out[4 * i + 1] = (unsigned char)to_int8(ping[i].y, c->thr);
+            rgba_out[4 * i + 2] = (unsigned char)to_int8(ping[i].z, c->thr);
+            rgba_out[4 * i + 3] = 0;
+        }
+}
+
 // The frame's summary from the tile arrays in row-major order: the one statement of it, shared by
 // both backends (and the sanitizer build's context layer).
 void bdpt_noise_summarize(const float* tile_sum, const float* tile_error, const unsigned* tile_valid,

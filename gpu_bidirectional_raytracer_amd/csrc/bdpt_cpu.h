@@ -48,6 +48,9 @@ void bdpt_cpu_noise_read_mark(const bdpt_cpu_ctx* c, bdpt_vec* colors, unsigned*
 void bdpt_cpu_noise_write_mark(bdpt_cpu_ctx* c, const bdpt_vec* colors, const unsigned* counter);
 void bdpt_cpu_noise_estimate(bdpt_cpu_ctx* c, const bdpt_noise_params* p, float* error_out, float* tile_sum,
                              float* tile_error, unsigned* tile_valid, unsigned* tile_pending);
+// noise-guided denoiser (include/bdpt.h bdpt_denoise_noise); the caller has checked parameters and camera
+void bdpt_cpu_denoise_noise(const bdpt_cpu_ctx* c, const bdpt_denoise_noise_params* p, bdpt_vec* colors_out,
+                            unsigned char* rgba_out, float* variance_out);
 // the last estimate's pending count per tile (bdpt_noise_tile_pending); false before the first estimate
 bool bdpt_cpu_noise_tile_pending(const bdpt_cpu_ctx* c, unsigned* tile_pending);
 // the frame's summary from the tile arrays: host code shared by both backends

@@ -22,7 +22,7 @@ struct bdpt_svc_clock {
     bool ran = false;
     float cpu_ms = 0.f;                 // CPU backend: wall time of the last call
 };
-enum { kSvcAov = 0, kSvcDenoise, kSvcReproject, kSvcPreview, kSvcNoise, kSvcCount };
+enum { kSvcAov = 0, kSvcDenoise, kSvcReproject, kSvcPreview, kSvcNoise, kSvcDenoiseNoise, kSvcCount };
 
 struct bdpt_ctx {
     int device = 0;
@@ -177,7 +177,7 @@ struct bdpt_ctx {
     size_t aov_cap = 0;
     int aov_traversal = 0;              // BDPT_TRAVERSE_* of the last bdpt_render_aov (0: none yet)
     // the frame services' clocks, by kSvc*: bdpt_render_aov (the kernel alone), bdpt_denoise,
-    // capture / bdpt_reproject, bdpt_preview_denoise, bdpt_noise_estimate
+    // capture / bdpt_reproject, bdpt_preview_denoise, bdpt_noise_estimate, bdpt_denoise_noise
     bdpt_svc_clock svc[kSvcCount];
     // denoiser (bdpt_denoise): guide, ping and pong records of the whole frame in one allocation
     // (3 x 16 B per pixel), made on the first call -- the frame size never changes

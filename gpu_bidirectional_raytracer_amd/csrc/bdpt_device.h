@@ -21,7 +21,9 @@
 //             pong colours; made on the first call                                  48 B/pixel
 //   d_hist    float4[4][W*H] + 20 B/pixel  reprojection (bdpt_reproject): two sets of history records
 //             {gpos, gid}, {hc, hm} and the packed results; made on first use        84 B/pixel
-//   bdpt_preview_denoise works in d_dn (the count in the colour records' .w) and d_hist's results
+//   bdpt_preview_denoise works in d_dn (the count in the colour records' .w) and d_hist's results;
+//   bdpt_denoise_noise works in d_dn (the variance in .w) and reads d_mark, the noise estimate's
+//   uint4[W*H] records {mc, mn}; its packed results and variance plane go into d_aov
 #ifndef BDPT_DEVICE_H
 #define BDPT_DEVICE_H
 
@@ -213,6 +215,30 @@ struct bdpt_preview_args {
     uchar4* rgba;
     const float* gamma_thr;
 };
+
+// The noise-guided denoiser (bdpt_dnoise_pack_kernel, bdpt_dnoise_prefilter_kernel, bdpt_dnoise_level_t;
+// include/bdpt.h bdpt_denoise_noise).  The denoiser's records and tiles: `cur` / `nxt` are {colour,
+// variance v, -1: none}; the pack kernel writes {B, raw v0} into ping, the prefilter reads it and
+// writes {B, v} into pong, where the levels start.  The last level may write the packed results
+// (out3, variance: float[W*H], rgba; any may be nullptr).
+struct bdpt_dnoise_args {
+    int W, H;
+    int step;                       // 2^k
+    float isc;                      // isc_0 * 4^k
+    float s2;                       // noise_sigma^2
+    int rows;                       // 1: a wave covers 64 x 1 pixels, 0: 8 x 8
+    const float4* guide;
+    const float4* cur;
+    float4* nxt;                    // nullptr on a last level
+    bdpt_dev_vec* out3;
+    float* variance;
+    uchar4* rgba;
+    const float* gamma_thr;
+};
+#define BDPT_DEV_DNOISE_EPS 1e-12f      // BDPT_DENOISE_NOISE_EPS (include/bdpt.h)
+// the prefilter stages a 32 x 8 tile and its halo of 2 pixels: sphere id and raw variance
+#define BDPT_DNP_LDS_W (BDPT_DN_BTW + 4)
+#define BDPT_DNP_LDS_H (BDPT_DN_BTH + 4)
 
 // Temporal reprojection (bdpt_history_pack_kernel / bdpt_reproject_kernel; include/bdpt.h
 // bdpt_reproject).  Context-owned history, made on first use: two sets (ping-pong: a capture reads

@@ -27,6 +27,10 @@ extern "C" __global__ void bdpt_reproject_kernel(bdpt_reproject_args);
 extern "C" const void* bdpt_preview_level_table[2][7];   // [LDS staging][normal_power]
 extern "C" __global__ void bdpt_noise_mark_kernel(const bdpt_dev_vec*, const unsigned*, uint4*, int);
 extern "C" __global__ void bdpt_noise_kernel(bdpt_noise_args);
+extern "C" __global__ void bdpt_dnoise_pack_kernel(const int*, const bdpt_dev_vec*, const bdpt_dev_vec*, const unsigned*,
+                                                   const uint4*, int, const bdpt_dev_sphere*, int, float4*, float4*, int);
+extern "C" __global__ void bdpt_dnoise_prefilter_kernel(const float4*, const float4*, float4*, int, int);
+extern "C" const void* bdpt_dnoise_level_table[2][7];    // [LDS staging][normal_power]
 static_assert(BDPT_NOISE_BTW == BDPT_NOISE_TW && BDPT_NOISE_BTH == BDPT_NOISE_TH, "the kernel's tile is the ABI's");
 
 // ---- the shared scaffold ---------------------------------------------------------------------
@@ -140,6 +144,8 @@ static frame_outs wanted(const frame_outs& have, const void* colors_out, const v
     return {colors_out ? have.out3 : nullptr, weight_out ? have.weight : nullptr, rgba_out ? have.rgba : nullptr};
 }
 static void set_outs(bdpt_denoise_args& v, const frame_outs& o) { v.out3 = o.out3; v.rgba = o.rgba; }
+// (the noise-guided denoiser's variance plane travels in the `weight` slot)
+static void set_outs(bdpt_dnoise_args& v, const frame_outs& o) { v.out3 = o.out3; v.variance = o.weight; v.rgba = o.rgba; }
 template <class Args>
 static void set_outs(Args& v, const frame_outs& o) { v.out3 = o.out3; v.weight = o.weight; v.rgba = o.rgba; }
 
@@ -309,6 +315,69 @@ int bdpt_denoise(bdpt_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out
 
 int bdpt_last_denoise_ms(bdpt_ctx* c, float* ms) {
     return svc_last_ms(c, kSvcDenoise, ms, "bdpt_last_denoise_ms: no frame denoised");
+}
+
+// ---- noise-guided denoiser (include/bdpt.h bdpt_denoise_noise) ------------------
+// bdpt_denoise's sequence with the variance in the colour records' .w: the unjittered whole-frame
+// bdpt_aov_kernel, bdpt_dnoise_pack_kernel (guide records + {B, raw variance} into ping),
+// bdpt_dnoise_prefilter_kernel (ping -> pong), the levels from pong, then the read-back.  The packed
+// results go where the feature planes were, the variance plane into the 5th word of a pixel's 12
+// there.  The mark is only read (a context without one: every pixel without an estimate).  Only
+// d_aov and d_dn are written.
+int bdpt_denoise_noise(bdpt_ctx* c, const bdpt_denoise_noise_params* p, bdpt_vec* colors_out, unsigned char* rgba_out,
+                       float* variance_out) {
+    if (!c) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_denoise_noise: multi-device contexts are not denoised (upload the assembled frame to a one-device context)");
+    if (!p) return fail(c, BDPT_EINVAL, "bdpt_denoise_noise: no parameters");
+    if (!colors_out && !rgba_out) return fail(c, BDPT_EINVAL, "bdpt_denoise_noise: no output buffer");
+    if (int rc = filter_check(c, "bdpt_denoise_noise", p->levels, 1, p->normal_power, p->sigma_color)) return rc;
+    if (p->materials != BDPT_DENOISE_DIFFUSE && p->materials != BDPT_DENOISE_ALL)
+        return fail(c, BDPT_EINVAL, "bdpt_denoise_noise: materials %d", p->materials);
+    if (!(p->noise_sigma > 0.f && p->noise_sigma < INFINITY))
+        return fail(c, BDPT_EINVAL, "bdpt_denoise_noise: noise_sigma must be > 0 and finite");
+    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_denoise_noise: camera not set");
+    if (c->cpu) {
+        svc_cpu(c, kSvcDenoiseNoise, [&] { bdpt_cpu_denoise_noise(c->cpu, p, colors_out, rgba_out, variance_out); });
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t np = (size_t)c->W * c->H;
+    dn_bufs d;
+    if (int rc = dn_alloc(c, "bdpt_denoise_noise", &d)) return rc;
+    if (int rc = join_fold(c)) return rc;
+    if (int rc = svc_begin(c, kSvcDenoiseNoise)) return rc;
+    bdpt_aov_args av;
+    if (int rc = aov_frame(c, c->cam, &av)) return rc;
+    hipLaunchKernelGGL(bdpt_dnoise_pack_kernel, lane_grid(np), dim3(256), 0, c->stream, (const int*)av.id,
+                       (const bdpt_dev_vec*)av.normal, (const bdpt_dev_vec*)c->d_colors, (const unsigned*)c->d_counter,
+                       (const uint4*)c->d_mark, (int)c->mark_live, (const bdpt_dev_sphere*)c->d_sph,
+                       (int)(p->materials == BDPT_DENOISE_ALL), d.guide, d.ping, (int)np);
+    HIPCHK(c, hipGetLastError());
+    // (experiments: BDPT_DNOISE_PREFILTER=0 leaves the prefilter out -- the levels then read the raw
+    // variances, which is not the definition -- so that scripts/denoise_noise_time.py can time its share)
+    bool prefilter = true;
+    if (const char* e = getenv("BDPT_DNOISE_PREFILTER")) prefilter = atoi(e) != 0;
+    if (prefilter) {
+        hipLaunchKernelGGL(bdpt_dnoise_prefilter_kernel, tile_grid(c->W, c->H, BDPT_DN_BTW, BDPT_DN_BTH), dim3(256), 0,
+                           c->stream, (const float4*)d.guide, (const float4*)d.ping, d.pong, c->W, c->H);
+        HIPCHK(c, hipGetLastError());
+    }
+    // words 0..2 of a pixel's 12 in d_aov, the 4th and the 5th
+    const frame_outs want = wanted({(bdpt_dev_vec*)c->d_aov, c->d_aov + 4 * c->aov_cap, (uchar4*)(c->d_aov + 3 * c->aov_cap)},
+                                   colors_out, variance_out, rgba_out);
+    bdpt_dnoise_args v;
+    memset(&v, 0, sizeof(v));
+    v.s2 = p->noise_sigma * p->noise_sigma;
+    const dn_bufs from_pong = {d.guide, d.pong, d.ping};     // the levels start at the prefilter's output
+    if (int rc = run_levels(c, v, bdpt_dnoise_level_table, p->levels, p->normal_power, p->sigma_color,
+                            prefilter ? from_pong : d, want))
+        return rc;
+    if (int rc = svc_end(c, kSvcDenoiseNoise)) return rc;
+    return read_outs(c, want, colors_out, variance_out, rgba_out);
+}
+
+int bdpt_last_denoise_noise_ms(bdpt_ctx* c, float* ms) {
+    return svc_last_ms(c, kSvcDenoiseNoise, ms, "bdpt_last_denoise_noise_ms: no frame denoised");
 }
 
 // ---- temporal reprojection (include/bdpt.h bdpt_reproject) ---------------------

@@ -49,7 +49,7 @@ __device__ __forceinline__ float pv_clampc(float w) { return w == 0.f ? 0.f : fm
 // The level kernels of both filters.  bdpt_preview_denoise (include/bdpt.h) runs
 // bdpt_aov_kernel once, bdpt_reproject_kernel writing its {o, clampc(tot)} record into the ping
 // buffer and the guide record next to it, then one level per level as the denoiser does: its level
-// kernels are the denoiser's with the count in the colour record's .w (COUNTS below) -- the same
+// kernels are the denoiser's with the count in the colour record's .w (kLvCounts below) -- the same
 // 32-byte records, tiles and LDS staging.  Numerics as above; a_p + a_q lies in [2^-20, 2^41],
 // inside the fast reciprocal's range, and sw / su is the library division.
 
@@ -93,55 +93,97 @@ __device__ __forceinline__ void pv_tap(float hw, float isc, float c2, f3 n_p, f3
     sc = add(sc, smul(w, q));
 }
 
-// One pixel's result: the next buffer's record (COUNTS: with the count a, else .w = 0) and the
-// packed results the last level was asked for.
-template <bool COUNTS, class Args>
+// one used tap of bdpt_denoise_noise (include/bdpt.h): the colour stop from the two
+// variances where both pixels have one (v < 0: none), else the denoiser's; the centre's variance is
+// carried as sum w^2 v
+template <int NP>
+__device__ __forceinline__ void nz_tap(float hw, float isc, float s2, f3 n_p, f3 c_p, float v_p, float4 gq, float4 cq,
+                                       float& sv, float& sw, f3& sc) {
+    const float d = dot(n_p, mk(gq.x, gq.y, gq.z));
+    float wn = d > 0.f ? d : 0.f;
+#pragma unroll
+    for (int r = 0; r < NP; r++) wn = wn * wn;
+    const f3 q = mk(cq.x, cq.y, cq.z);
+    const f3 dc = sub(q, c_p);
+    const float e2 = dot(dc, dc);
+    const float v_q = cq.w;
+    const bool has_p = !(v_p < 0.f), has_q = !(v_q < 0.f);
+    float wc;
+    if (has_p && has_q) {
+        const float t = s2 * (v_p + v_q) + BDPT_DEV_DNOISE_EPS;
+        wc = t * rcp_rn(t + e2);
+    } else {
+        wc = rcp_rn_ge1(1.f + e2 * isc);
+    }
+    const float w = (hw * wn) * wc;
+    sw = sw + w;
+    sc = add(sc, smul(w, q));
+    if (has_p) sv = sv + (w * w) * (has_q ? v_q : v_p);
+}
+
+// What the colour record's .w carries through the levels: nothing (bdpt_denoise), the sample count
+// (bdpt_preview_denoise) or the variance (bdpt_denoise_noise).
+constexpr int kLvPlain = 0, kLvCounts = 1, kLvNoise = 2;
+
+// One pixel's result: the next buffer's record (with the count or the variance a; plain: .w = 0)
+// and the packed results the last level was asked for.
+template <int MODE, class Args>
 __device__ __forceinline__ void level_store(const Args& v, int i, f3 o, float a) {
-    if (v.nxt) v.nxt[i] = make_float4(o.x, o.y, o.z, COUNTS ? a : 0.f);
+    if (v.nxt) v.nxt[i] = make_float4(o.x, o.y, o.z, MODE != kLvPlain ? a : 0.f);
     if (v.out3) {
         bdpt_dev_vec ov;
         ov.x = o.x; ov.y = o.y; ov.z = o.z;
         v.out3[i] = ov;
     }
-    if constexpr (COUNTS) {
+    if constexpr (MODE == kLvCounts) {
         if (v.weight) v.weight[i] = a;
+    }
+    if constexpr (MODE == kLvNoise) {
+        if (v.variance) v.variance[i] = a;
     }
     if (v.rgba) v.rgba[i] = bdpt_dev_to_rgba(o.x, o.y, o.z, v.gamma_thr);
 }
 
-// one tap that passed the id test; COUNTS: used only where the tap has a count
-template <int NP, bool COUNTS, class Args>
+// one tap that passed the id test; counts: used only where the tap has a count.  su: the second sum
+// (counts: of u; noise: of w^2 v)
+template <int NP, int MODE, class Args>
 __device__ __forceinline__ void level_tap(const Args& v, float hw, f3 n_p, f3 c_p, float a_p, float4 gq, float4 cq,
                                           float& su, float& sw, f3& sc, bool& used) {
-    if constexpr (COUNTS) {
+    if constexpr (MODE == kLvCounts) {
         if (!(cq.w > 0.f)) return;
         pv_tap<NP>(hw, v.isc, v.c2, n_p, c_p, a_p, gq, cq, su, sw, sc);
         used = true;
+    } else if constexpr (MODE == kLvNoise) {
+        nz_tap<NP>(hw, v.isc, v.s2, n_p, c_p, a_p, gq, cq, su, sw, sc);
     } else {
         dn_tap<NP>(hw, v.isc, n_p, c_p, gq, cq, sw, sc);
     }
 }
 
-// the centre's result from the sums; `used` (COUNTS): at least one tap counted, else the centre is
-// copied through
-template <bool COUNTS, class Args>
+// the centre's result from the sums; `used` (counts): at least one tap counted, else the centre is
+// copied through; noise: the variance of the weighted mean, (sum w^2 v) / (sum w)^2, where the
+// centre had one
+template <int MODE, class Args>
 __device__ __forceinline__ void level_finish(const Args& v, int i, bool used, f3 c_p, float a_p, float su, float sw,
                                              f3 sc) {
-    if constexpr (COUNTS) {
+    if constexpr (MODE == kLvCounts) {
         if (!used) {
-            level_store<true>(v, i, c_p, a_p);
+            level_store<MODE>(v, i, c_p, a_p);
             return;
         }
-        level_store<true>(v, i, smul(rcp_rn(sw), sc), pv_clampc(sw / su));
+        level_store<MODE>(v, i, smul(rcp_rn(sw), sc), pv_clampc(sw / su));
+    } else if constexpr (MODE == kLvNoise) {
+        const float r = rcp_rn(sw);
+        level_store<MODE>(v, i, smul(r, sc), !(a_p < 0.f) ? (su * r) * r : a_p);
     } else {
-        level_store<false>(v, i, smul(rcp_rn(sw), sc), 0.f);
+        level_store<MODE>(v, i, smul(rcp_rn(sw), sc), 0.f);
     }
 }
 
 // One level, taps straight from L1 / L2: one lane per pixel, two 16-byte loads per tap (guide
 // record and colour), one 16-byte store.  Wave tiles 8 x 8 or 64 x 1
 // (v.rows), as in bdpt_aov_kernel.  The 25 taps are unrolled, j outer and i inner as defined.
-template <int NP, bool COUNTS, class Args>
+template <int NP, int MODE, class Args>
 __device__ __forceinline__ void level_direct(const Args& v) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = v.rows ? (int)blockIdx.x * BDPT_DN_ROW_BTW + lane
@@ -152,10 +194,10 @@ __device__ __forceinline__ void level_direct(const Args& v) {
     const int i = y * v.W + x;
     const float4 gp = v.guide[i], cp4 = v.cur[i];
     const f3 c_p = mk(cp4.x, cp4.y, cp4.z);
-    const float a_p = cp4.w;                             // COUNTS: the centre's count
+    const float a_p = cp4.w;                             // the centre's count or variance
     const int gid = __float_as_int(gp.w);
-    if (gid < 0) {                                       // copied through (COUNTS: colour and count)
-        level_store<COUNTS>(v, i, c_p, a_p);
+    if (gid < 0) {                                       // copied through, colour and .w
+        level_store<MODE>(v, i, c_p, a_p);
         return;
     }
     const f3 n_p = mk(gp.x, gp.y, gp.z);
@@ -182,16 +224,16 @@ __device__ __forceinline__ void level_direct(const Args& v) {
 #pragma unroll
         for (int t = 0; t < 5; t++)
             if (in[t] && __float_as_int(gq[t].w) == gid)
-                level_tap<NP, COUNTS>(v, hk[j] * hk[t], n_p, c_p, a_p, gq[t], cq[t], su, sw, sc, used);
+                level_tap<NP, MODE>(v, hk[j] * hk[t], n_p, c_p, a_p, gq[t], cq[t], su, sw, sc, used);
     }
-    level_finish<COUNTS>(v, i, used, c_p, a_p, su, sw, sc);
+    level_finish<MODE>(v, i, used, c_p, a_p, su, sw, sc);
 }
 
 // The same level with the 32 x 8 tile and its halo of 2 * step <= 4 pixels staged in LDS (steps 1
 // and 2, where neighbouring lanes share most taps): every record of the region is loaded from
 // memory once per workgroup, coalesced, and the 25 taps are ds reads.  Positions outside the
 // frame hold the id -2, which no eligible centre has.  Kept or not by measurement: DESIGN.md 4d.
-template <int NP, bool COUNTS, class Args>
+template <int NP, int MODE, class Args>
 __device__ __forceinline__ void level_staged(const Args& v) {
     __shared__ float4 sg[BDPT_DN_LDS_W * BDPT_DN_LDS_H], scol[BDPT_DN_LDS_W * BDPT_DN_LDS_H];
     const int halo = 2 * v.step;                         // <= 4 (the host launches steps 1 and 2 only)
@@ -219,7 +261,7 @@ __device__ __forceinline__ void level_staged(const Args& v) {
     const float a_p = cp4.w;
     const int gid = __float_as_int(gp.w);
     if (gid < 0) {
-        level_store<COUNTS>(v, i, c_p, a_p);
+        level_store<MODE>(v, i, c_p, a_p);
         return;
     }
     const f3 n_p = mk(gp.x, gp.y, gp.z);
@@ -234,20 +276,24 @@ __device__ __forceinline__ void level_staged(const Args& v) {
             const int q = li + (j - 2) * v.step * rw + (t - 2) * v.step;
             const float4 gq = sg[q];
             if (__float_as_int(gq.w) != gid) continue;
-            level_tap<NP, COUNTS>(v, hk[j] * hk[t], n_p, c_p, a_p, gq, scol[q], su, sw, sc, used);
+            level_tap<NP, MODE>(v, hk[j] * hk[t], n_p, c_p, a_p, gq, scol[q], su, sw, sc, used);
         }
     }
-    level_finish<COUNTS>(v, i, used, c_p, a_p, su, sw, sc);
+    level_finish<MODE>(v, i, used, c_p, a_p, su, sw, sc);
 }
 
 template <int NP>
-__global__ __launch_bounds__(256) void bdpt_denoise_level_t(bdpt_denoise_args v) { level_direct<NP, false>(v); }
+__global__ __launch_bounds__(256) void bdpt_denoise_level_t(bdpt_denoise_args v) { level_direct<NP, kLvPlain>(v); }
 template <int NP>
-__global__ __launch_bounds__(256) void bdpt_denoise_level_lds_t(bdpt_denoise_args v) { level_staged<NP, false>(v); }
+__global__ __launch_bounds__(256) void bdpt_denoise_level_lds_t(bdpt_denoise_args v) { level_staged<NP, kLvPlain>(v); }
 template <int NP>
-__global__ __launch_bounds__(256) void bdpt_preview_level_t(bdpt_preview_args v) { level_direct<NP, true>(v); }
+__global__ __launch_bounds__(256) void bdpt_preview_level_t(bdpt_preview_args v) { level_direct<NP, kLvCounts>(v); }
 template <int NP>
-__global__ __launch_bounds__(256) void bdpt_preview_level_lds_t(bdpt_preview_args v) { level_staged<NP, true>(v); }
+__global__ __launch_bounds__(256) void bdpt_preview_level_lds_t(bdpt_preview_args v) { level_staged<NP, kLvCounts>(v); }
+template <int NP>
+__global__ __launch_bounds__(256) void bdpt_dnoise_level_t(bdpt_dnoise_args v) { level_direct<NP, kLvNoise>(v); }
+template <int NP>
+__global__ __launch_bounds__(256) void bdpt_dnoise_level_lds_t(bdpt_dnoise_args v) { level_staged<NP, kLvNoise>(v); }
 
 // host-side launch tables: [LDS staging][normal_power]
 #define BDPT_LEVEL_ROW(K) \
@@ -257,7 +303,89 @@ extern "C" const void* bdpt_denoise_level_table[2][7] = {BDPT_LEVEL_ROW(bdpt_den
                                                          BDPT_LEVEL_ROW(bdpt_denoise_level_lds_t)};
 extern "C" const void* bdpt_preview_level_table[2][7] = {BDPT_LEVEL_ROW(bdpt_preview_level_t),
                                                          BDPT_LEVEL_ROW(bdpt_preview_level_lds_t)};
+extern "C" const void* bdpt_dnoise_level_table[2][7] = {BDPT_LEVEL_ROW(bdpt_dnoise_level_t),
+                                                        BDPT_LEVEL_ROW(bdpt_dnoise_level_lds_t)};
 #undef BDPT_LEVEL_ROW
+
+// ---------------------------------------------------------------------------------------------
+// The noise-guided denoiser's own kernels (include/bdpt.h bdpt_denoise_noise; no
+// reference counterpart).  Host sequence on the context's stream: bdpt_aov_kernel,
+// bdpt_dnoise_pack_kernel, bdpt_dnoise_prefilter_kernel, then the bdpt_dnoise_level_t instances
+// above, ping-pong from the prefilter's output.  Numerics as for the denoiser; a / (n - a) and
+// sv / sh are the compiler's correctly rounded divisions (denormals kept).
+
+// Guide records as bdpt_denoise_pack_kernel writes them, and {B, raw variance v0 or -1} into the
+// ping buffer.  mark: the noise estimate's records, nullptr while none was ever stored; live = 0:
+// the mark is cleared (every count reads 0).
+extern "C" __global__ __launch_bounds__(256) void bdpt_dnoise_pack_kernel(
+    const int* __restrict__ id, const bdpt_dev_vec* __restrict__ normal, const bdpt_dev_vec* __restrict__ colors,
+    const unsigned* __restrict__ counter, const uint4* __restrict__ mark, int live,
+    const bdpt_dev_sphere* __restrict__ sph, int all_materials, float4* __restrict__ guide,
+    float4* __restrict__ ping, int count) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    int g = id[i];
+    if (g >= 0 && !all_materials && sph[g].refl != BDPT_DEV_DIFF) g = -1;
+    const bdpt_dev_vec n = normal[i];
+    guide[i] = make_float4(n.x, n.y, n.z, __int_as_float(g));
+    const bdpt_dev_vec B = colors[i];
+    float v0 = -1.0f;
+    if (mark && live) {
+        const uint4 rec = mark[i];
+        const unsigned cnt = counter[i], mn = rec.w;
+        // 2*(cnt - mn) >= mn without the overflow, as in bdpt_noise_kernel
+        if (mn > 0u && cnt > mn && cnt - mn >= (mn >> 1) + (mn & 1u)) {
+            const f3 d = sub(mk(B.x, B.y, B.z), mk(__uint_as_float(rec.x), __uint_as_float(rec.y), __uint_as_float(rec.z)));
+            const float a = (float)mn, nf = (float)cnt;
+            v0 = dot(d, d) * (a / (nf - a));
+        }
+    }
+    ping[i] = make_float4(B.x, B.y, B.z, v0);
+}
+
+// The prefilter: one lane per pixel of a 32 x 8 tile; the tile's sphere ids and raw variances with
+// a halo of 2 pixels are staged in LDS (8 B per position, loaded once per workgroup), the 25 taps
+// are ds reads.  Positions outside the frame hold the id -2, which no eligible centre has.
+extern "C" __global__ __launch_bounds__(256) void bdpt_dnoise_prefilter_kernel(const float4* __restrict__ guide,
+                                                                                const float4* __restrict__ cur,
+                                                                                float4* __restrict__ nxt, int W, int H) {
+    __shared__ float2 sv0[BDPT_DNP_LDS_W * BDPT_DNP_LDS_H];   // {bits: id, v0}
+    constexpr int rw = BDPT_DNP_LDS_W, rh = BDPT_DNP_LDS_H;
+    const int bx0 = (int)blockIdx.x * BDPT_DN_BTW - 2, by0 = (int)blockIdx.y * BDPT_DN_BTH - 2;
+    for (int k = threadIdx.x; k < rw * rh; k += 256) {
+        const int ry = k / rw, rx = k - ry * rw;
+        const int gx = bx0 + rx, gy = by0 + ry;
+        float2 e = make_float2(__int_as_float(-2), -1.0f);
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) e = make_float2(guide[gy * W + gx].w, cur[gy * W + gx].w);
+        sv0[k] = e;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lx = wave * 8 + (lane & 7), ly = lane >> 3;
+    const int x = (int)blockIdx.x * BDPT_DN_BTW + lx, y = (int)blockIdx.y * BDPT_DN_BTH + ly;
+    if (x >= W || y >= H) return;
+    const int i = y * W + x, li = (ly + 2) * rw + lx + 2;
+    float4 rec = cur[i];
+    const int gid = __float_as_int(sv0[li].x);
+    if (gid >= 0) {
+        constexpr float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
+        float sv = 0.f, sh = 0.f;
+        bool used = false;
+#pragma unroll
+        for (int j = 0; j < 5; j++) {
+#pragma unroll
+            for (int t = 0; t < 5; t++) {
+                const float2 e = sv0[li + (j - 2) * rw + (t - 2)];
+                if (__float_as_int(e.x) != gid || e.y < 0.f) continue;
+                sv = sv + (hk[j] * hk[t]) * e.y;
+                sh = sh + hk[j] * hk[t];
+                used = true;
+            }
+        }
+        rec.w = used ? sv / sh : -1.0f;
+    }
+    nxt[i] = rec;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Temporal reprojection (include/bdpt.h bdpt_reproject; no reference counterpart).

@@ -7,7 +7,7 @@
  *           [--device D | --gpus N | --devices D0,D1,...] [--tile ROWS] [--seed S] [--dat PATH]
  *           [--denoise [--denoise-levels N] [--denoise-sigma S] [--denoise-all] [--denoise-count N]]
  *           [--reproject [--reproject-history N] [--reproject-tol T]]
- *           [--until E [--max-spp N] [--adaptive [--min-spp N]]]
+ *           [--until E [--max-spp N] [--adaptive [--min-spp N]]] [--denoise-noise [S]]
  *
  * Without positional arguments the built-in CornellSpheres scene is used (smallpt_cpu.c:400).
  * Like the reference, width/height get +1 (smallpt_cpu.c:409-410).  The first frame runs the
@@ -42,6 +42,12 @@
  * none of its pixels is pending, its error is at most E and --min-spp passes (default 0) are done;
  * the report line then also says how many pixel-passes that took.  The frame is noisier than the
  * one plain --until leaves, which oversamples the easy tiles.
+ * --denoise-noise [S] writes --out from the noise-guided filter's frame (bdpt_denoise_noise: the
+ * --denoise-* options apply, S is noise_sigma, default 1): the colour stop follows the variance the
+ * noise estimate's mark measures, so a converged frame is left alone.  With --until E every check
+ * then estimates without re-marking first and re-marks only when the render goes on, so the filter
+ * finds the last check's mark; not with --adaptive.  After --spp alone no mark exists, and the file
+ * equals --denoise's.  One device (or the CPU) only.
  */
 #include "smallpt_app.h"
 
@@ -54,7 +60,8 @@ int main(int argc, char **argv)
     unsigned seed = 1;
     const char *pos[3] = {0, 0, 0}, *out = NULL, *keys = "", *dat = "assets/data/MersenneTwister.dat";
     const char *ckpt = NULL, *resume = NULL;
-    int denoise = 0;
+    int denoise = 0, denoise_noise = 0;
+    float noise_sigma = 1.f;
     bdpt_denoise_params dn = {4, 5, 0.5f, BDPT_DENOISE_DIFFUSE};
     float count_ref = 8.f;
     int until = 0, max_spp = 4096, adaptive = 0, min_spp = 0;
@@ -81,6 +88,14 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[a], "--dat") && a + 1 < argc) dat = argv[++a];
         else if (!strcmp(argv[a], "--p6")) p6 = 1;
         else if (!strcmp(argv[a], "--denoise")) denoise = 1;
+        else if (!strcmp(argv[a], "--denoise-noise")) {
+            denoise_noise = 1;
+            if (a + 1 < argc) {                                /* an optional number follows */
+                char *end;
+                const float v = strtof(argv[a + 1], &end);
+                if (end != argv[a + 1] && !*end) { noise_sigma = v; a++; }
+            }
+        }
         else if (!strcmp(argv[a], "--denoise-levels") && a + 1 < argc) dn.levels = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--denoise-sigma") && a + 1 < argc) dn.sigma_color = strtof(argv[++a], NULL);
         else if (!strcmp(argv[a], "--denoise-all")) dn.materials = BDPT_DENOISE_ALL;
@@ -101,6 +116,10 @@ int main(int argc, char **argv)
     fprintf(stderr, "Usage: %s <window width> <window height> <scene file>\n", argv[0]);
     if (denoise && ndev) {
         fprintf(stderr, "--denoise needs one device (--device D, or -1 for the CPU)\n");
+        return 1;
+    }
+    if (denoise_noise && (ndev || adaptive || h.reuse_history || denoise)) {
+        fprintf(stderr, "--denoise-noise needs one device and goes without --adaptive, --reproject and --denoise\n");
         return 1;
     }
     if (h.reuse_history && ndev) {
@@ -184,7 +203,7 @@ int main(int argc, char **argv)
     int until_failed = 0;
     if (until) {
         if ((adaptive ? render_until_adaptive(&h, &nz, max_spp, batch, min_spp)
-                      : render_until(&h, &nz, max_spp, batch)) < 0) until_failed = 1;
+                      : render_until(&h, &nz, max_spp, batch, denoise_noise)) < 0) until_failed = 1;
     } else {
         for (int done = 0; done < spp; done += batch)
             update_rendering(&h, spp - done < batch ? spp - done : batch);
@@ -193,7 +212,7 @@ int main(int argc, char **argv)
         key(&h, (unsigned char)*k);
         if (until) {
             if ((adaptive ? render_until_adaptive(&h, &nz, max_spp, batch, min_spp)
-                          : render_until(&h, &nz, max_spp, batch)) < 0) until_failed = 1;
+                          : render_until(&h, &nz, max_spp, batch, denoise_noise)) < 0) until_failed = 1;
         } else {
             for (int done = 0; done < spp; done += batch)
                 update_rendering(&h, spp - done < batch ? spp - done : batch);
@@ -203,6 +222,9 @@ int main(int argc, char **argv)
         bdpt_preview_params pv = {h.rp, dn.levels, dn.normal_power, dn.sigma_color, count_ref};
         pv.rp.materials = dn.materials;
         rc = save_denoised_preview_ppm(&h, out, p6, &pv);
+    } else if (out && denoise_noise) {
+        const bdpt_denoise_noise_params dnn = {dn.levels, dn.normal_power, dn.sigma_color, dn.materials, noise_sigma};
+        rc = save_denoised_noise_ppm(&h, out, p6, &dnn);
     } else if (out)
         rc = denoise ? save_denoised_ppm(&h, out, p6, &dn)
                      : h.reuse_history ? save_preview_ppm(&h, out, p6) : save_ppm(&h, out, p6);

@@ -128,6 +128,20 @@ __attribute__((unused)) static int save_denoised_ppm(host *h, const char *path, 
     return rc;
 }
 
+/* --denoise-noise: the same file from the noise-guided filter's pixels (bdpt_denoise_noise) */
+__attribute__((unused)) static int save_denoised_noise_ppm(host *h, const char *path, int binary,
+                                                           const bdpt_denoise_noise_params *dn)
+{
+    unsigned char *rgba = malloc(4 * (size_t)h->width * h->height);
+    int rc = rgba ? bdpt_denoise_noise(h->ctx, dn, NULL, rgba, NULL) : BDPT_ENOMEM;
+    if (rc == BDPT_OK)
+        rc = binary ? bdpt_save_ppm_binary(path, rgba, h->width, h->height)
+                    : bdpt_save_ppm(path, rgba, h->width, h->height);
+    report(h, rc, "Noise-guided denoised SavePPM");
+    free(rgba);
+    return rc;
+}
+
 /* --reproject: the same file from the preview's pixels (bdpt_reproject) */
 __attribute__((unused)) static int save_preview_ppm(host *h, const char *path, int binary)
 {
@@ -159,19 +173,32 @@ __attribute__((unused)) static int save_denoised_preview_ppm(host *h, const char
  * (bdpt_noise_estimate with remark after every batch: some pixel valid, none pending, no tile over
  * the threshold) or max_spp passes are rendered; one report line on stderr.  Returns 1 when
  * converged, 0 when not, -1 on an error. */
-__attribute__((unused)) static int render_until(host *h, const bdpt_noise_params *np, int max_spp, int batch)
+/* keep_mark (--denoise-noise): a pixel that has just re-marked has no fresh samples and so no
+ * variance for bdpt_denoise_noise, so every check estimates without remark first and re-marks (a
+ * second estimate) only when the loop goes on: the mark the last check used stays in place. */
+__attribute__((unused)) static int render_until(host *h, const bdpt_noise_params *np, int max_spp, int batch,
+                                                int keep_mark)
 {
     bdpt_noise_summary s;
     int converged = 0;
     memset(&s, 0, sizeof s);
     const int first = h->current_sample;
-    do {
+    bdpt_noise_params look = *np;
+    if (keep_mark) look.remark = 0;
+    for (;;) {
         update_rendering(h, batch);
-        const int rc = bdpt_noise_estimate(h->ctx, np, NULL, NULL, NULL, &s);
+        int rc = bdpt_noise_estimate(h->ctx, &look, NULL, NULL, NULL, &s);
         report(h, rc, "Noise estimate");
         if (rc != BDPT_OK) return -1;
         converged = s.valid_pixels > 0 && s.pending_pixels == 0 && s.tiles_over == 0;
-    } while (!converged && h->current_sample < max_spp);
+        if (converged || h->current_sample >= max_spp) break;
+        if (keep_mark) {
+            bdpt_noise_summary again;
+            rc = bdpt_noise_estimate(h->ctx, np, NULL, NULL, NULL, &again);
+            report(h, rc, "Noise re-mark");
+            if (rc != BDPT_OK) return -1;
+        }
+    }
     fprintf(stderr, "Until %g: %d passes (%d in this render), %s, worst tile %.9g, mean %.17g\n", (double)np->threshold,
             h->current_sample, h->current_sample - first, converged ? "converged" : "not converged",
             (double)s.max_tile, s.mean);

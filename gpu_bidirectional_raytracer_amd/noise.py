@@ -2,7 +2,7 @@
 
     python -m gpu_bidirectional_raytracer_amd.noise <width> <height> <scene> --out PREFIX
                                   [--until E] [--max-spp N] [--batch B] [--device D] [--ppm]
-                                  [--adaptive [--min-spp N]]
+                                  [--adaptive [--min-spp N]] [--denoise [--noise-sigma S]]
 
 Sizes get +1 like `smallpt` (smallpt_cpu.c:409-410).  SmallPT.RenderUntil: batches of B passes
 (default 8), after each a noise estimate with re-marking (Renderer.noise_estimate), until some pixel
@@ -16,6 +16,10 @@ passes and converged.  --ppm also writes PREFIX_error.ppm, a grey heat map throu
 not rendered again once none of its pixels is pending and its error is at most E); the archive then
 also holds retired_at and retired_error [tiles_y, tiles_x], pixel_passes, and counter [H, W], the
 passes every pixel got.
+--denoise (not with --adaptive) also filters the frame the loop stops at with the noise-guided
+denoiser (RenderUntil(denoise=True, noise_sigma=S), default S = 1: the mark the last check used is
+still in place) and adds denoised [H, W, 3] float32 and variance [H, W] float32 (-1 where there is
+none) to the archive.
 """
 from __future__ import annotations
 
@@ -63,12 +67,17 @@ def main(argv=None) -> int:
     ap.add_argument("--ppm", action="store_true", help="also write PREFIX_error.ppm, a grey heat map")
     ap.add_argument("--adaptive", action="store_true", help="stop every 32 x 8 tile on its own")
     ap.add_argument("--min-spp", type=int, default=0, metavar="N", help="--adaptive: no tile stops before N passes")
+    ap.add_argument("--denoise", action="store_true", help="also write the noise-guided denoiser's frame and variance")
+    ap.add_argument("--noise-sigma", type=float, default=1.0, metavar="S", help="--denoise: noise_sigma (default 1)")
     args = ap.parse_args(argv)
+    if args.denoise and args.adaptive:
+        ap.error("--denoise does not go with --adaptive")
 
     app = SmallPT(args.width, args.height, args.scene, device=args.device)
     try:
         est = app.RenderUntil(args.until, max_passes=args.max_spp, batch=args.batch, pixels=True,
-                              adaptive=args.adaptive, min_passes=args.min_spp)
+                              adaptive=args.adaptive, min_passes=args.min_spp,
+                              **(dict(denoise=True, noise_sigma=args.noise_sigma) if args.denoise else {}))
         counter = app.colors()[1] if args.adaptive else None
     finally:
         app.FreeBuffers()
@@ -76,6 +85,8 @@ def main(argv=None) -> int:
     if args.adaptive:
         extra = dict(retired_at=est["retired_at"], retired_error=est["retired_error"],
                      pixel_passes=np.int64(est["pixel_passes"]), counter=counter)
+    if args.denoise:
+        extra = dict(denoised=est["denoised"], variance=est["denoised_variance"])
     np.savez_compressed(args.out + ".npz", error=est["error"], tile_error=est["tile_error"],
                         tile_valid=est["tile_valid"], summary=summary_record(est, args.until), **extra)
     if args.ppm:

@@ -539,6 +539,65 @@ int  bdpt_noise_estimate(bdpt_ctx *ctx, const bdpt_noise_params *params, float *
 int  bdpt_noise_tile_pending(bdpt_ctx *ctx, unsigned *tile_pending);
 int  bdpt_last_noise_ms(bdpt_ctx *ctx, float *ms);
 
+/* ---- noise-guided denoiser: bdpt_denoise with a colour stop that follows the measured variance
+ * (no reference counterpart) ----
+ * bdpt_denoise stops at colour edges with one absolute constant, which suits a frame of a few passes
+ * and over-blurs a converged one.  Here the stop of every pair of pixels is scaled by the variance
+ * of their running means, estimated from the noise estimate's mark: with A the mean of the mn marked
+ * samples and B the mean of all cnt, |B - A|^2 * mn / (cnt - mn) estimates Var(B) without bias.
+ * Guides, eligibility, h, levels and steps are bdpt_denoise's.  fp32, no contraction, in the order
+ * written; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; 1/x is the correctly rounded reciprocal and
+ * a / b the correctly rounded IEEE division; denormals are kept; a tap that is not used is skipped,
+ * not weighted by zero; non-finite radiance is not special.  The GPU, the CPU backend and the tests'
+ * numpy statement form the same bits.  A variance v "is none" iff v < 0 (stored as -1.0f; an
+ * estimate is >= +0 or NaN); has(v) = !(v < 0).
+ *   raw       per pixel p: B = colors[p], cnt = counter[p] as they stand, A = mc[p], mn = mn[p] (the
+ *             mark of bdpt_noise_estimate; a context without a stored mark, or with a cleared one,
+ *             has mn = 0 everywhere).  p has an estimate iff mn > 0, cnt > mn and 2*(cnt - mn) >= mn
+ *             in 64-bit integers (bdpt_noise_estimate's rule):
+ *               a = (float)mn;  n = (float)cnt;  d = B - A;  e2 = dot(d, d)
+ *               v0[p] = e2 * (a / (n - a))
+ *             otherwise v0[p] = -1.
+ *   prefilter one statistic per pixel is too noisy to use alone.  An ineligible p keeps v[p] = v0[p].
+ *             For an eligible centre p: sv = sh = +0; for j = 0..4 (dy = j-2), for i = 0..4
+ *             (dx = i-2), a tap q inside the frame with id[q] == id[p] and has(v0[q]) adds
+ *               sv = sv + (h[j]*h[i]) * v0[q];  sh = sh + h[j]*h[i]
+ *             and v[p] = sv / sh; no tap counted: v[p] = -1.
+ *   level k   = 0 .. levels-1, step s = 2^k, isc_k as for bdpt_denoise, s2 = noise_sigma*noise_sigma,
+ *             eps = BDPT_DENOISE_NOISE_EPS.  An ineligible pixel is copied through, colour and
+ *             variance.  For an eligible centre p: sw = sv = +0, sc = (+0, +0, +0); for j = 0..4
+ *             (rows, outer), for i = 0..4, a tap q inside the frame with id[q] == id[p] adds
+ *               d  = dot(n_p, n_q);  wn = max(d, 0), then wn = wn*wn normal_power times
+ *               dc = cur[q] - cur[p];  e2 = dot(dc, dc)
+ *               has(v[p]) and has(v[q]):  t = s2 * (v[p] + v[q]) + eps;  wc = t * (1 / (t + e2))
+ *               otherwise:                wc = 1 / (1 + e2*isc_k)          (bdpt_denoise's stop)
+ *               w  = ((h[j]*h[i]) * wn) * wc
+ *               sw = sw + w;  sc = sc + w*cur[q]
+ *               has(v[p]):  sv = sv + (w*w) * (has(v[q]) ? v[q] : v[p])
+ *             and r = 1/sw, out = sc * r; the centre's new variance is (sv * r) * r where has(v[p]),
+ *             and stays -1 where not.  Level k+1 reads level k's colours and variances.
+ * Why: two means of one true colour differ by a variance of v[p] + v[q], so a colour distance is an
+ * edge in proportion to it; there is no 4^k factor on that branch because the carried variance
+ * itself shrinks as the filter averages (sum w^2 v / (sum w)^2 is the variance of the weighted mean of
+ * independent taps).  Consequence: while no pixel has an estimate -- no mark stored, a cleared mark,
+ * a mark that is valid nowhere -- every tap takes the second branch and the call returns
+ * bdpt_denoise's bits for the same levels, normal_power, sigma_color and materials.
+ *   levels 1..8, normal_power 0..6, sigma_color > 0 (+inf allowed), noise_sigma > 0 and finite.
+ *   Defaults: levels 4, normal_power 5, sigma_color 0.5, noise_sigma 1, materials DIFFUSE.
+ * colors_out, rgba_out: as bdpt_denoise's, either may be NULL, not both.  variance_out (or NULL):
+ * W*H floats, the carried variance after the last level, -1 where there is none.  Synchronous,
+ * ordered after whatever is queued; it only reads the accumulation, the counters and the mark and
+ * writes nothing but its own buffers.  BDPT_EINVAL: NULL or out-of-range parameters, colors_out and
+ * rgba_out both NULL, a multi-device context.  BDPT_ESTATE: no camera set.
+ * bdpt_last_denoise_noise_ms: device time of the last successful call's kernels alone (HIP events;
+ * wall time on the CPU backend), BDPT_ESTATE before the first. */
+#define BDPT_DENOISE_NOISE_EPS 1e-12f
+typedef struct { int levels; int normal_power; float sigma_color; int materials;
+                 float noise_sigma; } bdpt_denoise_noise_params;
+int  bdpt_denoise_noise(bdpt_ctx *ctx, const bdpt_denoise_noise_params *params, bdpt_vec *colors_out,
+                        unsigned char *rgba_out, float *variance_out);
+int  bdpt_last_denoise_noise_ms(bdpt_ctx *ctx, float *ms);
+
 /* ---- optional display: HIP-GL interop ----
  * The caller owns the window, its OpenGL context (current on the calling thread) and a
  * pixel-unpack buffer of at least 4*W*H bytes (glGenBuffers + glBufferData(GL_PIXEL_UNPACK_BUFFER,
