@@ -45,7 +45,7 @@ tests/native/plan_tiles_check: tests/native/plan_tiles_check.cpp $(CSRC)/bdpt_pl
 $(BUILD):
 	mkdir -p $(BUILD)
 
-$(BUILD)/bdpt_kernels.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h $(CSRC)/bdpt_frame_kernels.h | $(BUILD)
+$(BUILD)/bdpt_kernels.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h $(CSRC)/bdpt_frame_kernels.h $(CSRC)/bdpt_filter.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the same file once more for launches over a tile list (BDPT_TILES: only the generic and the BVH
@@ -70,7 +70,7 @@ $(BUILD)/bdpt_frame.o: $(CSRC)/bdpt_frame.cpp $(CTX_DEPS) | $(BUILD)
 $(BUILD)/bdpt_bvh.o: $(CSRC)/bdpt_bvh.cpp $(CSRC)/bdpt_bvh.h include/bdpt.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BUILD)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h | $(BUILD)
+$(BUILD)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h $(CSRC)/bdpt_filter.h include/bdpt.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/bdpt_util.o: $(CSRC)/bdpt_util.c include/bdpt.h | $(BUILD)
@@ -150,7 +150,7 @@ $(ASAN_DIR):
 $(ASAN_DIR)/%.o: $(CSRC)/%.c include/bdpt.h | $(ASAN_DIR)
 	$(CC) $(ASAN_FLAGS) -std=gnu11 -c $< -o $@
 
-$(ASAN_DIR)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h | $(ASAN_DIR)
+$(ASAN_DIR)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h $(CSRC)/bdpt_filter.h include/bdpt.h | $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -std=c++17 -c $< -o $@
 
 # the HIP-free context layer: every entry point smallpt calls, the frame services included, in

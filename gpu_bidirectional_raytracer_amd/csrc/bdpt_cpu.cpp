@@ -8,6 +8,10 @@
 // device.cu:565-566, sin/cos as (float)f((double)x).  So its frames equal the GPU's bit for bit.
 // Work is spread over threads by pixel row (each pixel renders its passes in order, as the
 // running mean requires).
+//
+// The frame services (denoisers, reprojection, noise estimate) take what a pixel or a tap computes
+// from bdpt_filter.h, the one statement of it that the HIP kernels run too; this file is the host's
+// driver of it: rows over threads, plain arrays instead of packed records.
 #include "bdpt_cpu.h"
 
 #include <math.h>
@@ -18,6 +22,8 @@
 #include <atomic>
 #include <thread>
 #include <vector>
+
+#include "bdpt_filter.h"
 
 namespace {
 
@@ -114,6 +120,21 @@ unsigned to_int8(float v, const float* thr) {                // toInt (vec.h:34)
         if (v >= thr[k + step]) k += step;
     return k;
 }
+
+// n colours as RGBA8 through the gamma thresholds
+void to_rgba(const float* thr, const bdpt_vec* col, size_t n, unsigned char* rgba) {
+    for (size_t i = 0; i < n; i++) {
+        rgba[4 * i] = (unsigned char)to_int8(col[i].x, thr);
+        rgba[4 * i + 1] = (unsigned char)to_int8(col[i].y, thr);
+        rgba[4 * i + 2] = (unsigned char)to_int8(col[i].z, thr);
+        rgba[4 * i + 3] = 0;
+    }
+}
+
+// bdpt_filter.h's vector from the ABI's and from the path tracer's, and back
+inline f3 of3(const bdpt_vec& v) { return mk(v.x, v.y, v.z); }
+inline f3 of3(V3 v) { return mk(v.x, v.y, v.z); }
+inline bdpt_vec to_vec(f3 v) { return {v.x, v.y, v.z}; }
 
 int worker_count() {
     if (const char* e = getenv("BDPT_CPU_THREADS")) {
@@ -507,86 +528,115 @@ void bdpt_cpu_render_aov(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, in
     render_aov_cam(c, c->cam, x0, y0, w, h, jitter, sid, out);
 }
 
-// Edge-avoiding wavelet denoiser (include/bdpt.h bdpt_denoise): a plain restatement
-// of the definition there.  Guides: id and normal of the unjittered first hit (the loop above with
-// jitter = 0).  Level k filters with the 5x5 B3-spline taps at step 2^k; a tap counts when it is
-// inside the frame and shows the centre's sphere, weighted by the normals' cosine (squared
-// normal_power times) and by 1 / (1 + |dc|^2 * isc_k); ineligible pixels are copied through.
-// fp32, no contraction, in exactly this order -- the HIP kernel (bdpt_denoise_level_kernel) forms
-// the same bits.  Threaded over rows per level.  The caller has checked the parameters and the
-// camera; the context's own state is only read.
-void bdpt_cpu_denoise(const bdpt_cpu_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out,
-                      unsigned char* rgba_out) {
+namespace {
+// The unjittered whole-frame first hit under `cam`: the ids and the planes asked for.
+enum { kHitPos = 1, kHitT = 2, kHitNrm = 4 };
+struct FirstHit {
+    std::vector<int> id;
+    std::vector<float> t;
+    std::vector<bdpt_vec> pos, nrm;
+    FirstHit(const bdpt_cpu_ctx* c, const bdpt_camera& cam, int planes) {
+        const size_t np = (size_t)c->W * c->H;
+        bdpt_aov_buffers g;
+        memset(&g, 0, sizeof g);
+        id.resize(np);
+        g.id = id.data();
+        if (planes & kHitPos) { pos.resize(np); g.position = pos.data(); }
+        if (planes & kHitT) { t.resize(np); g.t = t.data(); }
+        if (planes & kHitNrm) { nrm.resize(np); g.normal = nrm.data(); }
+        render_aov_cam(c, cam, 0, 0, c->W, c->H, 0, 0u, &g);
+    }
+    // the ids as the filters' guide ids: an ineligible pixel gets -1
+    void to_guide_ids(const bdpt_cpu_ctx* c, int materials) {
+        for (int& g : id) g = guide_id(g, materials == BDPT_DENOISE_ALL, c->scene.s.data());
+    }
+};
+
+// The levels of the three a-trous filters (bdpt_filter.h lv_tap / lv_finish; MODE as the kernels'
+// kLvPlain / kLvCounts / kLvNoise), ping-pong from `ping` and, in the modes that carry a count or a
+// variance, `aping`; the result is left there.  Level l has step 2^l and isc0 * 4^l; kk is c2 or
+// s2.  A tap counts when it is inside the frame and shows the centre's sphere; an ineligible pixel
+// is copied through.  Threaded over rows per level.  (The tap loops are written out here and in the
+// prefilter: as a callback of a shared loop they are slower.)
+template <int MODE>
+void atrous_levels(const bdpt_cpu_ctx* c, const FirstHit& g, int levels, int normal_power, float sigma_color,
+                   float kk, std::vector<bdpt_vec>& ping, std::vector<float>& aping) {
     const int W = c->W, H = c->H;
-    const size_t np = (size_t)W * H;
-    std::vector<int> id(np);
-    std::vector<bdpt_vec> nrm(np);
-    bdpt_aov_buffers g;
-    memset(&g, 0, sizeof g);
-    g.id = id.data();
-    g.normal = nrm.data();
-    bdpt_cpu_render_aov(c, 0, 0, W, H, 0, 0u, &g);
-    for (size_t i = 0; i < np; i++)                       // an ineligible pixel: id -1
-        if (id[i] >= 0 && p->materials == BDPT_DENOISE_DIFFUSE && c->scene.s[id[i]].refl != BDPT_DIFF) id[i] = -1;
-    static const float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
-    const float isc0 = 1.0f / (p->sigma_color * p->sigma_color);
-    std::vector<bdpt_vec> ping(c->colors), pong(np);
-    for (int k = 0; k < p->levels; k++) {
-        const int s = 1 << k;
-        const float isc = isc0 * (float)(1 << (2 * k));
+    std::vector<bdpt_vec> pong(ping.size());
+    std::vector<float> apong(aping.size());
+    const float isc0 = 1.0f / (sigma_color * sigma_color);
+    for (int l = 0; l < levels; l++) {
+        const int step = 1 << l;
+        const float isc = isc0 * (float)(1 << (2 * l));
         const bdpt_vec* cur = ping.data();
+        const float* acur = aping.data();
         bdpt_vec* out = pong.data();
+        float* aout = apong.data();
         parallel_rows(0, H, c->threads, [&](int y) {
             for (int x = 0; x < W; x++) {
                 const size_t i = (size_t)y * W + x;
-                const bdpt_vec cp = cur[i];
-                if (id[i] < 0) {
-                    out[i] = cp;
-                    continue;
-                }
-                const V3 n_p = of(nrm[i]);
-                float sw = 0.f;
-                V3 sc = v3(0.f, 0.f, 0.f);
-                for (int j = 0; j < 5; j++) {
-                    const int qy = y + (j - 2) * s;
-                    if (qy < 0 || qy >= H) continue;
-                    for (int t = 0; t < 5; t++) {
-                        const int qx = x + (t - 2) * s;
-                        if (qx < 0 || qx >= W) continue;
-                        const size_t q = (size_t)qy * W + qx;
-                        if (id[q] != id[i]) continue;
-                        const float d = dot(n_p, of(nrm[q]));
-                        float wn = d > 0.f ? d : 0.f;
-                        for (int r = 0; r < p->normal_power; r++) wn = wn * wn;
-                        const V3 cq = of(cur[q]);
-                        const V3 dc = cq - of(cp);
-                        const float e2 = dot(dc, dc);
-                        const float wc = 1.f / (1.f + e2 * isc);
-                        const float w = ((hk[j] * hk[t]) * wn) * wc;
-                        sw = sw + w;
-                        sc = sc + w * cq;
+                const f3 c_p = of3(cur[i]);
+                float a_p = 0.f;
+                if constexpr (MODE != kLvPlain) a_p = acur[i];
+                f3 o = c_p;
+                float a = a_p;
+                if (g.id[i] >= 0) {
+                    const f3 n_p = of3(g.nrm[i]);
+                    float su = 0.f, sw = 0.f;
+                    f3 sc = mk(0.f, 0.f, 0.f);
+                    bool used = false;
+                    for (int j = 0; j < 5; j++) {
+                        const int qy = y + (j - 2) * step;
+                        if (qy < 0 || qy >= H) continue;
+                        for (int t = 0; t < 5; t++) {
+                            const int qx = x + (t - 2) * step;
+                            if (qx < 0 || qx >= W) continue;
+                            const size_t q = (size_t)qy * W + qx;
+                            if (g.id[q] != g.id[i]) continue;
+                            float a_q = 0.f;
+                            if constexpr (MODE != kLvPlain) a_q = acur[q];
+                            lv_tap<MODE>(b3_weight(j, t), normal_power, isc, kk, n_p, c_p, a_p, of3(g.nrm[q]),
+                                         of3(cur[q]), a_q, su, sw, sc, used);
+                        }
                     }
+                    o = lv_finish<MODE>(used, c_p, a_p, su, sw, sc, a);
                 }
-                const float r = 1.f / sw;
-                out[i] = {sc.x * r, sc.y * r, sc.z * r};
+                out[i] = to_vec(o);
+                if constexpr (MODE != kLvPlain) aout[i] = a;
             }
         });
         ping.swap(pong);
+        aping.swap(apong);
     }
-    if (colors_out) memcpy(colors_out, ping.data(), sizeof(bdpt_vec) * np);
-    if (rgba_out)
-        for (size_t i = 0; i < np; i++) {
-            rgba_out[4 * i] = (unsigned char)to_int8(ping[i].x, c->thr);
-            rgba_out[4 * i + 1] = (unsigned char)to_int8(ping[i].y, c->thr);
-            rgba_out[4 * i + 2] = (unsigned char)to_int8(ping[i].z, c->thr);
-            rgba_out[4 * i + 3] = 0;
-        }
 }
 
-// Temporal reprojection (include/bdpt.h bdpt_reproject): a plain restatement of the
-// definition there -- the current camera's unjittered first hit, its point projected into the
-// history's camera, four validated bilinear taps, the blend by sample count.  fp32, no
-// contraction, in exactly this order; the HIP kernel (bdpt_reproject_kernel) forms the same bits.
+// a service's frame to the caller's buffers, each optional
+void write_frame(const bdpt_cpu_ctx* c, const std::vector<bdpt_vec>& col, bdpt_vec* colors_out,
+                 unsigned char* rgba_out) {
+    if (colors_out) memcpy(colors_out, col.data(), sizeof(bdpt_vec) * col.size());
+    if (rgba_out) to_rgba(c->thr, col.data(), col.size(), rgba_out);
+}
+void write_plane(const std::vector<float>& a, float* out) {
+    if (out) memcpy(out, a.data(), sizeof(float) * a.size());
+}
+}  // namespace
+
+// Edge-avoiding wavelet denoiser (include/bdpt.h bdpt_denoise).  Guides: id and
+// normal of the unjittered first hit; then the plain levels.  The caller has checked the parameters
+// and the camera; the context's own state is only read.
+void bdpt_cpu_denoise(const bdpt_cpu_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out,
+                      unsigned char* rgba_out) {
+    FirstHit g(c, c->cam, kHitNrm);
+    g.to_guide_ids(c, p->materials);
+    std::vector<bdpt_vec> ping(c->colors);
+    std::vector<float> none;
+    atrous_levels<kLvPlain>(c, g, p->levels, p->normal_power, p->sigma_color, 0.f, ping, none);
+    write_frame(c, ping, colors_out, rgba_out);
+}
+
+// Temporal reprojection (include/bdpt.h bdpt_reproject): the current camera's
+// unjittered first hit, its point projected into the history's camera, four validated bilinear
+// taps, the blend by sample count -- bdpt_filter.h's rp_project, rp_tap, rp_history and rp_blend.
 bool bdpt_cpu_history_present(const bdpt_cpu_ctx* c) {
     return c->has_hist && c->hsph.size() == c->scene.s.size() &&
            memcmp(c->hsph.data(), c->scene.s.data(), sizeof(bdpt_sphere) * c->hsph.size()) == 0;
@@ -602,93 +652,45 @@ void bdpt_cpu_history_read(const bdpt_cpu_ctx* c, bdpt_vec* colors, float* weigh
 }
 
 namespace {
-// id, t, position and normal of the unjittered whole-frame first hit under `cam`
-struct FirstHit {
-    std::vector<int> id;
-    std::vector<float> t;
-    std::vector<bdpt_vec> pos, nrm;
-    FirstHit(const bdpt_cpu_ctx* c, const bdpt_camera& cam, bool guides_only) {
-        const size_t np = (size_t)c->W * c->H;
-        id.resize(np);
-        pos.resize(np);
-        bdpt_aov_buffers g;
-        memset(&g, 0, sizeof g);
-        g.id = id.data();
-        g.position = pos.data();
-        if (!guides_only) {
-            t.resize(np);
-            nrm.resize(np);
-            g.t = t.data();
-            g.normal = nrm.data();
-        }
-        render_aov_cam(c, cam, 0, 0, c->W, c->H, 0, 0u, &g);
-    }
-};
-
 // (out, weight_out) of the whole frame from the history present, if any
 void reproject_frame(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, const FirstHit& f,
                      std::vector<bdpt_vec>& out, std::vector<float>& wout) {
     const int W = c->W, H = c->H;
     const bool present = bdpt_cpu_history_present(c);
+    const bool all_materials = p->materials == BDPT_DENOISE_ALL;
     const bdpt_camera& c0 = c->hcam;
-    const V3 ux = unit(of(c0.x)), uy = unit(of(c0.y)), ud = unit(of(c0.dir)), o = of(c0.orig);
+    const f3 ux = of3(unit(of(c0.x))), uy = of3(unit(of(c0.y))), ud = of3(unit(of(c0.dir))), o = of3(c0.orig);
     const float inv_w = (float)(14. / W), inv_h = (float)(10.5 / H);
     const float hw = (float)((double)(inv_w * (float)W) / 2.), hh = (float)((double)(inv_h * (float)H) / 2.);
     const float sx = 1.f / inv_w, sy = 1.f / inv_h;
     parallel_rows(0, H, c->threads, [&](int y) {
         for (int x = 0; x < W; x++) {
             const size_t i = (size_t)y * W + x;
-            const V3 col = of(c->colors[i]);
-            const float n = (float)c->counter[i];
             const int id1 = f.id[i];
             float m = 0.f;
-            V3 h = v3(0.f, 0.f, 0.f);
-            if (present && id1 >= 0 && (p->materials == BDPT_DENOISE_ALL || c->scene.s[id1].refl == BDPT_DIFF)) {
-                const V3 P = of(f.pos[i]), N = of(f.nrm[i]);
-                const V3 v = P - o;
-                const float a = dot(v, ux), b = dot(v, uy), cz = dot(v, ud);
-                const float r = 1.f / cz;
-                const float kx = (10.f * a) * r, ky = (10.f * b) * r;
-                const float fx = (kx + hw) * sx, fy = (ky + hh) * sy;
-                if (fx >= -1.f && fx < (float)W && fy >= -1.f && fy < (float)H) {
+            f3 h = mk(0.f, 0.f, 0.f);
+            if (present && guide_id(id1, all_materials, c->scene.s.data()) >= 0) {
+                const f3 P = of3(f.pos[i]), N = of3(f.nrm[i]);
+                float fx, fy;
+                if (rp_project(P, o, ux, uy, ud, hw, hh, sx, sy, W, H, fx, fy)) {
                     const float xf = floorf(fx), yf = floorf(fy);
                     const float wx = fx - xf, wy = fy - yf;
-                    const int qx0 = (int)xf, qy0 = (int)yf;
+                    const int qx0 = (int)xf, qy0 = (int)yf;       // -1 .. W-1, -1 .. H-1
                     const float lim = p->plane_tol * f.t[i];
                     float sw = 0.f, sm = 0.f;
-                    V3 sc = v3(0.f, 0.f, 0.f);
+                    f3 sc = mk(0.f, 0.f, 0.f);
                     bool used = false;
-                    for (int dy = 0; dy < 2; dy++)
-                        for (int dx = 0; dx < 2; dx++) {
-                            const int qx = qx0 + dx, qy = qy0 + dy;
-                            const float bx = dx ? wx : 1.f - wx, by = dy ? wy : 1.f - wy;
-                            const float bw = bx * by;
-                            if (qx < 0 || qx >= W || qy < 0 || qy >= H || !(bw > 0.f)) continue;
-                            const size_t q = (size_t)qy * W + qx;
-                            if (c->gid[q] != id1 || !(c->hm[q] > 0.f)) continue;
-                            if (!(fabsf(dot(of(c->gpos[q]) - P, N)) <= lim)) continue;
-                            sw = sw + bw;
-                            sm = sm + bw * fminf(c->hm[q], p->max_history);
-                            sc = sc + bw * of(c->hc[q]);
-                            used = true;
-                        }
-                    if (used) {
-                        h = (1.f / sw) * sc;
-                        m = sm;
+                    for (int k = 0; k < 4; k++) {
+                        const int qx = qx0 + (k & 1), qy = qy0 + (k >> 1);
+                        const bool in = qx >= 0 && qx < W && qy >= 0 && qy < H;
+                        const size_t q = in ? (size_t)qy * W + qx : i;   // outside: the pixel's own, not used
+                        rp_tap(k, wx, wy, in, c->gid[q], of3(c->gpos[q]), of3(c->hc[q]), c->hm[q], id1, P, N, lim,
+                               p->max_history, sw, sm, sc, used);
                     }
+                    rp_history(used, sw, sm, sc, h, m);
                 }
             }
-            const float tot = n + m;
-            V3 res = col;
-            if (m == 0.f) {
-            } else if (n == 0.f) {
-                res = h;
-            } else {
-                const float rt = 1.f / tot;
-                res = v3((n * col.x + m * h.x) * rt, (n * col.y + m * h.y) * rt, (n * col.z + m * h.z) * rt);
-            }
-            out[i] = {res.x, res.y, res.z};
-            wout[i] = tot;
+            out[i] = to_vec(rp_blend(of3(c->colors[i]), (float)c->counter[i], h, m, wout[i]));
         }
     });
 }
@@ -697,125 +699,39 @@ void reproject_frame(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, cons
 void bdpt_cpu_reproject(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, bdpt_vec* colors_out,
                         float* weight_out, unsigned char* rgba_out) {
     const size_t np = (size_t)c->W * c->H;
-    const FirstHit f(c, c->cam, false);
+    const FirstHit f(c, c->cam, kHitPos | kHitT | kHitNrm);
     std::vector<bdpt_vec> out(np);
     std::vector<float> w(np);
     reproject_frame(c, p, f, out, w);
-    if (colors_out) memcpy(colors_out, out.data(), sizeof(bdpt_vec) * np);
-    if (weight_out) memcpy(weight_out, w.data(), sizeof(float) * np);
-    if (rgba_out)
-        for (size_t i = 0; i < np; i++) {
-            rgba_out[4 * i] = (unsigned char)to_int8(out[i].x, c->thr);
-            rgba_out[4 * i + 1] = (unsigned char)to_int8(out[i].y, c->thr);
-            rgba_out[4 * i + 2] = (unsigned char)to_int8(out[i].z, c->thr);
-            rgba_out[4 * i + 3] = 0;
-        }
+    write_frame(c, out, colors_out, rgba_out);
+    write_plane(w, weight_out);
 }
 
 // Count-weighted denoising of the reprojected preview (include/bdpt.h bdpt_preview_denoise;
-// DESIGN.md 4f): a plain restatement of the definition there.  The input is reproject_frame's
-// (out, tot); the guides are the first hit the reprojection has just used; a record's count is
-// clamped when the record is written.  fp32, no contraction, in exactly this order -- the HIP
-// kernels (bdpt_preview_level_t) form the same bits.  The caller has checked the parameters.
-static inline float preview_clampc(float w) { return w == 0.f ? 0.f : fminf(fmaxf(w, 0x1p-20f), 0x1p40f); }
-
+// DESIGN.md 4f).  The input is reproject_frame's (out, tot); the guides are the first hit the
+// reprojection has just used; a record's count is clamped when the record is written; then the
+// levels with counts.  levels == 0 is the reprojection itself.  The caller has checked the parameters.
 void bdpt_cpu_preview_denoise(const bdpt_cpu_ctx* c, const bdpt_preview_params* p, bdpt_vec* colors_out,
                               float* weight_out, unsigned char* rgba_out) {
-    const int W = c->W, H = c->H;
-    const size_t np = (size_t)W * H;
-    FirstHit f(c, c->cam, false);
-    std::vector<bdpt_vec> ping(np), pong(np);
-    std::vector<float> aping(np), apong(np);
+    const size_t np = (size_t)c->W * c->H;
+    FirstHit f(c, c->cam, kHitPos | kHitT | kHitNrm);
+    std::vector<bdpt_vec> ping(np);
+    std::vector<float> aping(np);
     reproject_frame(c, &p->rp, f, ping, aping);
-    std::vector<int>& id = f.id;
-    const std::vector<bdpt_vec>& nrm = f.nrm;
     if (p->levels > 0) {
-        for (size_t i = 0; i < np; i++) {                 // an ineligible pixel: id -1
-            if (id[i] >= 0 && p->rp.materials == BDPT_DENOISE_DIFFUSE && c->scene.s[id[i]].refl != BDPT_DIFF) id[i] = -1;
-            aping[i] = preview_clampc(aping[i]);
-        }
+        f.to_guide_ids(c, p->rp.materials);
+        for (float& a : aping) a = clampc(a);
+        atrous_levels<kLvCounts>(c, f, p->levels, p->normal_power, p->sigma_color, 2.f / p->count_ref, ping, aping);
     }
-    static const float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
-    const float isc0 = 1.0f / (p->sigma_color * p->sigma_color);
-    const float c2 = 2.f / p->count_ref;
-    for (int k = 0; k < p->levels; k++) {
-        const int s = 1 << k;
-        const float isc = isc0 * (float)(1 << (2 * k));
-        const bdpt_vec* cur = ping.data();
-        const float* acur = aping.data();
-        bdpt_vec* out = pong.data();
-        float* aout = apong.data();
-        parallel_rows(0, H, c->threads, [&](int y) {
-            for (int x = 0; x < W; x++) {
-                const size_t i = (size_t)y * W + x;
-                const bdpt_vec cp = cur[i];
-                const float a_p = acur[i];
-                if (id[i] < 0) {
-                    out[i] = cp;
-                    aout[i] = a_p;
-                    continue;
-                }
-                const V3 n_p = of(nrm[i]);
-                float su = 0.f, sw = 0.f;
-                V3 sc = v3(0.f, 0.f, 0.f);
-                bool used = false;
-                for (int j = 0; j < 5; j++) {
-                    const int qy = y + (j - 2) * s;
-                    if (qy < 0 || qy >= H) continue;
-                    for (int t = 0; t < 5; t++) {
-                        const int qx = x + (t - 2) * s;
-                        if (qx < 0 || qx >= W) continue;
-                        const size_t q = (size_t)qy * W + qx;
-                        const float a_q = acur[q];
-                        if (id[q] != id[i] || !(a_q > 0.f)) continue;
-                        const float d = dot(n_p, of(nrm[q]));
-                        float wn = d > 0.f ? d : 0.f;
-                        for (int r = 0; r < p->normal_power; r++) wn = wn * wn;
-                        const V3 cq = of(cur[q]);
-                        const V3 dc = cq - of(cp);
-                        const float e2 = dot(dc, dc);
-                        float wc = 1.f;
-                        if (a_p != 0.f) {
-                            const float g = ((a_p * a_q) * (1.f / (a_p + a_q))) * c2;
-                            wc = 1.f / (1.f + (e2 * isc) * g);
-                        }
-                        const float u = ((hk[j] * hk[t]) * wn) * wc;
-                        const float w = u * a_q;
-                        su = su + u;
-                        sw = sw + w;
-                        sc = sc + w * cq;
-                        used = true;
-                    }
-                }
-                if (!used) {
-                    out[i] = cp;
-                    aout[i] = a_p;
-                    continue;
-                }
-                const float r = 1.f / sw;
-                out[i] = {sc.x * r, sc.y * r, sc.z * r};
-                aout[i] = preview_clampc(sw / su);
-            }
-        });
-        ping.swap(pong);
-        aping.swap(apong);
-    }
-    if (colors_out) memcpy(colors_out, ping.data(), sizeof(bdpt_vec) * np);
-    if (weight_out) memcpy(weight_out, aping.data(), sizeof(float) * np);
-    if (rgba_out)
-        for (size_t i = 0; i < np; i++) {
-            rgba_out[4 * i] = (unsigned char)to_int8(ping[i].x, c->thr);
-            rgba_out[4 * i + 1] = (unsigned char)to_int8(ping[i].y, c->thr);
-            rgba_out[4 * i + 2] = (unsigned char)to_int8(ping[i].z, c->thr);
-            rgba_out[4 * i + 3] = 0;
-        }
+    write_frame(c, ping, colors_out, rgba_out);
+    write_plane(aping, weight_out);
 }
 
 // The new history is formed in buffers of its own while the old one is read, then swapped in; its
 // guides are the first hit the reprojection has just used (the current camera becomes C0).
 void bdpt_cpu_history_capture(bdpt_cpu_ctx* c, const bdpt_reproject_params* p) {
     const size_t np = (size_t)c->W * c->H;
-    FirstHit f(c, c->cam, false);
+    FirstHit f(c, c->cam, kHitPos | kHitT | kHitNrm);
     std::vector<bdpt_vec> out(np);
     std::vector<float> w(np);
     reproject_frame(c, p, f, out, w);
@@ -830,7 +746,7 @@ void bdpt_cpu_history_capture(bdpt_cpu_ctx* c, const bdpt_reproject_params* p) {
 
 void bdpt_cpu_history_write(bdpt_cpu_ctx* c, const bdpt_camera* cam, const bdpt_vec* colors, const float* weight) {
     const size_t np = (size_t)c->W * c->H;
-    FirstHit f(c, *cam, true);
+    FirstHit f(c, *cam, kHitPos);
     c->hc.assign(colors, colors + np);
     c->hm.assign(weight, weight + np);
     c->gid.swap(f.id);
@@ -856,12 +772,7 @@ void bdpt_cpu_write_lightpaths(bdpt_cpu_ctx* c, const bdpt_lightpath* lp) {
     memcpy(c->lp.data(), lp, sizeof(bdpt_lightpath) * BDPT_LIGHT_POINTS);
 }
 void bdpt_cpu_update_pixels(bdpt_cpu_ctx* c) {
-    for (size_t i = 0; i < c->colors.size(); i++) {
-        c->pixels[4 * i] = (unsigned char)to_int8(c->colors[i].x, c->thr);
-        c->pixels[4 * i + 1] = (unsigned char)to_int8(c->colors[i].y, c->thr);
-        c->pixels[4 * i + 2] = (unsigned char)to_int8(c->colors[i].z, c->thr);
-        c->pixels[4 * i + 3] = 0;
-    }
+    to_rgba(c->thr, c->colors.data(), c->colors.size(), c->pixels.data());
 }
 void bdpt_cpu_write_radiance(bdpt_cpu_ctx* c, const bdpt_vec* colors, const unsigned* counter) {
     memcpy(c->colors.data(), colors, sizeof(bdpt_vec) * c->colors.size());
@@ -870,9 +781,9 @@ void bdpt_cpu_write_radiance(bdpt_cpu_ctx* c, const bdpt_vec* colors, const unsi
     bdpt_cpu_noise_clear(c);
 }
 
-// Per-tile noise estimate (include/bdpt.h bdpt_noise_estimate): a plain restatement
-// of the definition there.  fp32, no contraction, in exactly this order; the HIP kernel
-// (bdpt_noise_kernel) forms the same bits.
+// Per-tile noise estimate (include/bdpt.h bdpt_noise_estimate): the mark rules and
+// the per-pixel error are bdpt_filter.h's; the tile's sum is the definition's adjacent-pair tree
+// over its 256 slots, which the HIP kernel's wave butterfly is checked against.
 bool bdpt_cpu_noise_stored(const bdpt_cpu_ctx* c) { return !c->mark.empty(); }
 void bdpt_cpu_noise_clear(bdpt_cpu_ctx* c) {
     for (auto& m : c->mark) m.n = 0u;                     // nothing while no mark was ever stored
@@ -907,26 +818,16 @@ void bdpt_cpu_noise_estimate(bdpt_cpu_ctx* c, const bdpt_noise_params* p, float*
                 const size_t i = (size_t)y * W + x;
                 const bdpt_vec B = c->colors[i];
                 const unsigned cnt = c->counter[i], mn = stored ? c->mark[i].n : 0u;
-                const bool ok = mn > 0u && cnt > mn && 2ull * (cnt - mn) >= mn;
                 float e = -1.0f;
-                if (ok) {
-                    const bdpt_vec A = c->mark[i].c;
-                    const float a = (float)mn, n = (float)cnt;
-                    const float dx = B.x - A.x, dy = B.y - A.y, dz = B.z - A.z;
-                    const float e1 = (fabsf(dx) + fabsf(dy)) + fabsf(dz);
-                    const float s = a / (n - a);
-                    const float f = sqrtf(s);
-                    const float lum = (B.x + B.y) + B.z;
-                    const float den = sqrtf(fmaxf(lum, p->dark));
-                    e = (e1 * f) / den;
+                if (mark_valid(cnt, mn)) {
+                    e = pixel_error(of3(B), of3(c->mark[i].c), cnt, mn, p->dark);
                     v[k] = e;
                     valid++;
-                } else if (cnt > 0u && cnt < BDPT_COUNTER_CAP) {
+                } else if (mark_growing(cnt)) {
                     pending++;
                 }
                 if (error_out) error_out[i] = e;
-                if (p->remark && cnt > 0u && cnt < BDPT_COUNTER_CAP && (unsigned long long)cnt >= 2ull * mn)
-                    c->mark[i] = {B, cnt};
+                if (p->remark && mark_take(cnt, mn)) c->mark[i] = {B, cnt};
             }
             for (int m = BDPT_NOISE_TW * BDPT_NOISE_TH; m > 1; m /= 2)   // adjacent pairs, eight rounds
                 for (int k = 0; k < m / 2; k++) v[k] = v[2 * k] + v[2 * k + 1];
@@ -944,41 +845,26 @@ bool bdpt_cpu_noise_tile_pending(const bdpt_cpu_ctx* c, unsigned* tile_pending) 
     return true;
 }
 
-// Noise-guided denoiser (include/bdpt.h bdpt_denoise_noise): a plain restatement of
-// the definition there -- the raw variance from the mark, its 5x5 prefilter, then bdpt_denoise's
-// levels with the colour stop scaled by the two pixels' variances and the variance carried along.
-// fp32, no contraction, in exactly this order; the HIP kernels (bdpt_dnoise_pack_kernel,
-// bdpt_dnoise_prefilter_kernel, bdpt_dnoise_level_t) form the same bits.  Threaded over rows.
+// Noise-guided denoiser (include/bdpt.h bdpt_denoise_noise): the raw variance from
+// the mark, its 5x5 prefilter, then the denoiser's levels with the colour stop scaled by the two
+// pixels' variances and the variance carried along.  Threaded over rows.
 void bdpt_cpu_denoise_noise(const bdpt_cpu_ctx* c, const bdpt_denoise_noise_params* p, bdpt_vec* colors_out,
                             unsigned char* rgba_out, float* variance_out) {
     const int W = c->W, H = c->H;
     const size_t np = (size_t)W * H;
-    std::vector<int> id(np);
-    std::vector<bdpt_vec> nrm(np);
-    bdpt_aov_buffers g;
-    memset(&g, 0, sizeof g);
-    g.id = id.data();
-    g.normal = nrm.data();
-    bdpt_cpu_render_aov(c, 0, 0, W, H, 0, 0u, &g);
-    for (size_t i = 0; i < np; i++)                       // an ineligible pixel: id -1
-        if (id[i] >= 0 && p->materials == BDPT_DENOISE_DIFFUSE && c->scene.s[id[i]].refl != BDPT_DIFF) id[i] = -1;
-    static const float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
+    FirstHit g(c, c->cam, kHitNrm);
+    g.to_guide_ids(c, p->materials);
     const bool stored = !c->mark.empty();
-    std::vector<float> v0(np), var(np), vnext(np);
+    std::vector<float> v0(np, -1.0f), var(np);
     for (size_t i = 0; i < np; i++) {                     // the raw variance
         const unsigned cnt = c->counter[i], mn = stored ? c->mark[i].n : 0u;
-        v0[i] = -1.0f;
-        if (mn > 0u && cnt > mn && 2ull * (cnt - mn) >= mn) {
-            const V3 d = of(c->colors[i]) - of(c->mark[i].c);
-            const float a = (float)mn, n = (float)cnt;
-            v0[i] = dot(d, d) * (a / (n - a));
-        }
+        if (mark_valid(cnt, mn)) v0[i] = raw_variance(of3(c->colors[i]), of3(c->mark[i].c), cnt, mn);
     }
     parallel_rows(0, H, c->threads, [&](int y) {          // the prefilter
         for (int x = 0; x < W; x++) {
             const size_t i = (size_t)y * W + x;
             var[i] = v0[i];
-            if (id[i] < 0) continue;
+            if (g.id[i] < 0) continue;
             float sv = 0.f, sh = 0.f;
             bool used = false;
             for (int j = 0; j < 5; j++) {
@@ -988,83 +874,17 @@ void bdpt_cpu_denoise_noise(const bdpt_cpu_ctx* c, const bdpt_denoise_noise_para
                     const int qx = x + (t - 2);
                     if (qx < 0 || qx >= W) continue;
                     const size_t q = (size_t)qy * W + qx;
-                    if (id[q] != id[i] || v0[q] < 0.f) continue;
-                    sv = sv + (hk[j] * hk[t]) * v0[q];
-                    sh = sh + hk[j] * hk[t];
-                    used = true;
+                    pf_tap(b3_weight(j, t), g.id[q] == g.id[i], v0[q], sv, sh, used);
                 }
             }
-            var[i] = used ? sv / sh : -1.0f;
+            var[i] = pf_finish(used, sv, sh);
         }
     });
-    const float isc0 = 1.0f / (p->sigma_color * p->sigma_color);
-    const float s2 = p->noise_sigma * p->noise_sigma, eps = BDPT_DENOISE_NOISE_EPS;
-    std::vector<bdpt_vec> ping(c->colors), pong(np);
-    for (int k = 0; k < p->levels; k++) {
-        const int s = 1 << k;
-        const float isc = isc0 * (float)(1 << (2 * k));
-        const bdpt_vec* cur = ping.data();
-        bdpt_vec* out = pong.data();
-        parallel_rows(0, H, c->threads, [&](int y) {
-            for (int x = 0; x < W; x++) {
-                const size_t i = (size_t)y * W + x;
-                const bdpt_vec cp = cur[i];
-                const float v_p = var[i];
-                if (id[i] < 0) {
-                    out[i] = cp;
-                    vnext[i] = v_p;
-                    continue;
-                }
-                const bool has_p = !(v_p < 0.f);
-                const V3 n_p = of(nrm[i]);
-                float sw = 0.f, sv = 0.f;
-                V3 sc = v3(0.f, 0.f, 0.f);
-                for (int j = 0; j < 5; j++) {
-                    const int qy = y + (j - 2) * s;
-                    if (qy < 0 || qy >= H) continue;
-                    for (int t = 0; t < 5; t++) {
-                        const int qx = x + (t - 2) * s;
-                        if (qx < 0 || qx >= W) continue;
-                        const size_t q = (size_t)qy * W + qx;
-                        if (id[q] != id[i]) continue;
-                        const float d = dot(n_p, of(nrm[q]));
-                        float wn = d > 0.f ? d : 0.f;
-                        for (int r = 0; r < p->normal_power; r++) wn = wn * wn;
-                        const V3 cq = of(cur[q]);
-                        const V3 dc = cq - of(cp);
-                        const float e2 = dot(dc, dc);
-                        const float v_q = var[q];
-                        const bool has_q = !(v_q < 0.f);
-                        float wc;
-                        if (has_p && has_q) {
-                            const float tt = s2 * (v_p + v_q) + eps;
-                            wc = tt * (1.f / (tt + e2));
-                        } else {
-                            wc = 1.f / (1.f + e2 * isc);
-                        }
-                        const float w = ((hk[j] * hk[t]) * wn) * wc;
-                        sw = sw + w;
-                        sc = sc + w * cq;
-                        if (has_p) sv = sv + (w * w) * (has_q ? v_q : v_p);
-                    }
-                }
-                const float r = 1.f / sw;
-                out[i] = {sc.x * r, sc.y * r, sc.z * r};
-                vnext[i] = has_p ? (sv * r) * r : v_p;
-            }
-        });
-        ping.swap(pong);
-        var.swap(vnext);
-    }
-    if (colors_out) memcpy(colors_out, ping.data(), sizeof(bdpt_vec) * np);
-    if (variance_out) memcpy(variance_out, var.data(), sizeof(float) * np);
-    if (rgba_out)
-        for (size_t i = 0; i < np; i++) {
-            rgba_out[4 * i] = (unsigned char)to_int8(ping[i].x, c->thr);
-            rgba_out[4 * i + 1] = (unsigned char)to_int8(ping[i].y, c->thr);
-            rgba_out[4 * i + 2] = (unsigned char)to_int8(ping[i].z, c->thr);
-            rgba_out[4 * i + 3] = 0;
-        }
+    std::vector<bdpt_vec> ping(c->colors);
+    atrous_levels<kLvNoise>(c, g, p->levels, p->normal_power, p->sigma_color, p->noise_sigma * p->noise_sigma, ping,
+                            var);
+    write_frame(c, ping, colors_out, rgba_out);
+    write_plane(var, variance_out);
 }
 
 // The frame's summary from the tile arrays in row-major order: the one statement of it, shared by

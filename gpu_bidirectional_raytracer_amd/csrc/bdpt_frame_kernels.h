@@ -3,127 +3,47 @@
 // file in its precompiled build only (never under BDPT_JIT), after the helpers used here: f3 and
 // its operations, rcp_rn, bdpt_sqrt_rn, bdpt_dev_to_rgba.  bdpt_aov_kernel, whose planes these
 // kernels read, stays there with the path kernel's traversal.
+//
+// What a pixel or a tap computes is stated once, in bdpt_filter.h, for these kernels and for the
+// CPU backend (bdpt_cpu.cpp); this file is the device's driver of it: tiles, LDS staging, a row's
+// loads batched before its taps, the wave reduction, and the launch tables.
+#define BDPT_FILTER_KERNELS 1    // f3, rcp_rn, bdpt_sqrt_rn and the BDPT_DEV_* constants are in scope
+#include "bdpt_filter.h"
 
 // ---------------------------------------------------------------------------------------------
 // Edge-avoiding wavelet denoiser (include/bdpt.h bdpt_denoise; no reference
 // counterpart).  Host sequence on the context's stream: bdpt_aov_kernel (unjittered, whole frame),
 // bdpt_denoise_pack_kernel, then one level kernel per level, ping-pong.
 //
-// Numerics: the definition in include/bdpt.h, operation for operation -- fp32, no contraction
-// (-ffp-contract=off), dot() in the order (x + y) + z, both divisions correctly rounded (rcp_rn:
+// Numerics: bdpt_filter.h with the device's reciprocals, both correctly rounded (rcp_rn:
 // v_rcp_f32 + one Newton step inside [2^-125, 2^125), the library division outside, e.g. for
 // 1 + e2 * isc = +inf).  Denormal intermediates are kept, not flushed: wn (a cosine squared up to
 // six times) and w underflow gradually, and the build keeps fp32 denormals (hipcc's default for
 // gfx9; the hipRTC flags of the specialised kernels say -fno-gpu-flush-denormals-to-zero
-// explicitly).  A tap that is not used adds nothing -- it is skipped, not weighted by zero.
+// explicitly).
 
-// Guide records and the first ping buffer.  gid: the first hit's sphere, or -1 where the pixel is
-// not to be filtered (a miss; with materials == DIFFUSE any sphere that is not DIFF).  Eligibility
-// is a function of the sphere, so "same sphere as an eligible centre" implies an eligible tap.
+// Guide records {normal, guide_id} and the first ping buffer.
 extern "C" __global__ __launch_bounds__(256) void bdpt_denoise_pack_kernel(
     const int* __restrict__ id, const bdpt_dev_vec* __restrict__ normal, const bdpt_dev_vec* __restrict__ colors,
     const bdpt_dev_sphere* __restrict__ sph, int all_materials, float4* __restrict__ guide,
     float4* __restrict__ ping, int count) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
-    int g = id[i];
-    if (g >= 0 && !all_materials && sph[g].refl != BDPT_DEV_DIFF) g = -1;
+    const int g = guide_id(id[i], all_materials, sph);
     const bdpt_dev_vec n = normal[i];
     guide[i] = make_float4(n.x, n.y, n.z, __int_as_float(g));
-    if (ping) {                                          // nullptr: the guide records alone
+    if (ping) {                                         // nullptr: the guide records alone
         const bdpt_dev_vec c = colors[i];
         ping[i] = make_float4(c.x, c.y, c.z, 0.f);
     }
 }
 
-// 1.f / x, correctly rounded, for x >= 1 or NaN (1 + a product that is non-negative or NaN): one
-// compare decides between the in-range sequence and the library division (+inf, NaN, >= 2^125)
-__device__ __forceinline__ float rcp_rn_ge1(float x) {
-    if (__builtin_expect(!(x < 0x1p125f), 0)) return 1.f / x;
-    return rcp_rn_inrange(x);
-}
-
-// clampc of bdpt_preview_denoise: a record's count, 0 or inside [2^-20, 2^40]
-__device__ __forceinline__ float pv_clampc(float w) { return w == 0.f ? 0.f : fminf(fmaxf(w, 0x1p-20f), 0x1p40f); }
-
-// The level kernels of both filters.  bdpt_preview_denoise (include/bdpt.h) runs
+// The level kernels of the three filters.  bdpt_preview_denoise (include/bdpt.h) runs
 // bdpt_aov_kernel once, bdpt_reproject_kernel writing its {o, clampc(tot)} record into the ping
 // buffer and the guide record next to it, then one level per level as the denoiser does: its level
-// kernels are the denoiser's with the count in the colour record's .w (kLvCounts below) -- the same
-// 32-byte records, tiles and LDS staging.  Numerics as above; a_p + a_q lies in [2^-20, 2^41],
-// inside the fast reciprocal's range, and sw / su is the library division.
-
-// one used tap: hw = h[j] * h[i] (an exact constant), NP squarings of the normal weight
-template <int NP>
-__device__ __forceinline__ void dn_tap(float hw, float isc, f3 n_p, f3 c_p, float4 gq, float4 cq, float& sw, f3& sc) {
-    const float d = dot(n_p, mk(gq.x, gq.y, gq.z));
-    float wn = d > 0.f ? d : 0.f;
-#pragma unroll
-    for (int r = 0; r < NP; r++) wn = wn * wn;
-    const f3 q = mk(cq.x, cq.y, cq.z);
-    const f3 dc = sub(q, c_p);
-    const float e2 = dot(dc, dc);
-    const float wc = rcp_rn_ge1(1.f + e2 * isc);        // e2 >= 0 and isc >= 0, or their product is NaN
-    const float w = (hw * wn) * wc;
-    sw = sw + w;
-    sc = add(sc, smul(w, q));
-}
-
-// one used tap with counts (a_q > 0); a centre without a count (a_p == 0) stops nothing: wc = 1.f
-template <int NP>
-__device__ __forceinline__ void pv_tap(float hw, float isc, float c2, f3 n_p, f3 c_p, float a_p, float4 gq, float4 cq,
-                                       float& su, float& sw, f3& sc) {
-    const float d = dot(n_p, mk(gq.x, gq.y, gq.z));
-    float wn = d > 0.f ? d : 0.f;
-#pragma unroll
-    for (int r = 0; r < NP; r++) wn = wn * wn;
-    const f3 q = mk(cq.x, cq.y, cq.z);
-    const f3 dc = sub(q, c_p);
-    const float e2 = dot(dc, dc);
-    const float a_q = cq.w;
-    float wc = 1.f;
-    if (a_p != 0.f) {
-        const float g = ((a_p * a_q) * rcp_rn_inrange(a_p + a_q)) * c2;
-        wc = rcp_rn_ge1(1.f + (e2 * isc) * g);           // the product is non-negative or NaN
-    }
-    const float u = (hw * wn) * wc;
-    const float w = u * a_q;
-    su = su + u;
-    sw = sw + w;
-    sc = add(sc, smul(w, q));
-}
-
-// one used tap of bdpt_denoise_noise (include/bdpt.h): the colour stop from the two
-// variances where both pixels have one (v < 0: none), else the denoiser's; the centre's variance is
-// carried as sum w^2 v
-template <int NP>
-__device__ __forceinline__ void nz_tap(float hw, float isc, float s2, f3 n_p, f3 c_p, float v_p, float4 gq, float4 cq,
-                                       float& sv, float& sw, f3& sc) {
-    const float d = dot(n_p, mk(gq.x, gq.y, gq.z));
-    float wn = d > 0.f ? d : 0.f;
-#pragma unroll
-    for (int r = 0; r < NP; r++) wn = wn * wn;
-    const f3 q = mk(cq.x, cq.y, cq.z);
-    const f3 dc = sub(q, c_p);
-    const float e2 = dot(dc, dc);
-    const float v_q = cq.w;
-    const bool has_p = !(v_p < 0.f), has_q = !(v_q < 0.f);
-    float wc;
-    if (has_p && has_q) {
-        const float t = s2 * (v_p + v_q) + BDPT_DEV_DNOISE_EPS;
-        wc = t * rcp_rn(t + e2);
-    } else {
-        wc = rcp_rn_ge1(1.f + e2 * isc);
-    }
-    const float w = (hw * wn) * wc;
-    sw = sw + w;
-    sc = add(sc, smul(w, q));
-    if (has_p) sv = sv + (w * w) * (has_q ? v_q : v_p);
-}
-
-// What the colour record's .w carries through the levels: nothing (bdpt_denoise), the sample count
-// (bdpt_preview_denoise) or the variance (bdpt_denoise_noise).
-constexpr int kLvPlain = 0, kLvCounts = 1, kLvNoise = 2;
+// kernels are the denoiser's with the count in the colour record's .w (kLvCounts) -- the same
+// 32-byte records, tiles and LDS staging.  bdpt_denoise_noise carries the variance
+// there (kLvNoise).  The taps and finishes are bdpt_filter.h's (lv_tap, lv_finish).
 
 // One pixel's result: the next buffer's record (with the count or the variance a; plain: .w = 0)
 // and the packed results the last level was asked for.
@@ -144,40 +64,28 @@ __device__ __forceinline__ void level_store(const Args& v, int i, f3 o, float a)
     if (v.rgba) v.rgba[i] = bdpt_dev_to_rgba(o.x, o.y, o.z, v.gamma_thr);
 }
 
-// one tap that passed the id test; counts: used only where the tap has a count.  su: the second sum
-// (counts: of u; noise: of w^2 v)
-template <int NP, int MODE, class Args>
-__device__ __forceinline__ void level_tap(const Args& v, float hw, f3 n_p, f3 c_p, float a_p, float4 gq, float4 cq,
-                                          float& su, float& sw, f3& sc, bool& used) {
-    if constexpr (MODE == kLvCounts) {
-        if (!(cq.w > 0.f)) return;
-        pv_tap<NP>(hw, v.isc, v.c2, n_p, c_p, a_p, gq, cq, su, sw, sc);
-        used = true;
-    } else if constexpr (MODE == kLvNoise) {
-        nz_tap<NP>(hw, v.isc, v.s2, n_p, c_p, a_p, gq, cq, su, sw, sc);
-    } else {
-        dn_tap<NP>(hw, v.isc, n_p, c_p, gq, cq, sw, sc);
-    }
+// the mode's constant next to isc: c2 (counts) or s2 (noise)
+template <int MODE, class Args>
+__device__ __forceinline__ float level_k(const Args& v) {
+    if constexpr (MODE == kLvCounts) return v.c2;
+    else if constexpr (MODE == kLvNoise) return v.s2;
+    else return 0.f;
 }
 
-// the centre's result from the sums; `used` (counts): at least one tap counted, else the centre is
-// copied through; noise: the variance of the weighted mean, (sum w^2 v) / (sum w)^2, where the
-// centre had one
+// one tap that passed the id test, from its guide and colour records
+template <int NP, int MODE, class Args>
+__device__ __forceinline__ void level_tap(const Args& v, int j, int t, f3 n_p, f3 c_p, float a_p, float4 gq, float4 cq,
+                                          float& su, float& sw, f3& sc, bool& used) {
+    lv_tap<MODE>(b3_weight(j, t), NP, v.isc, level_k<MODE>(v), n_p, c_p, a_p, mk(gq.x, gq.y, gq.z),
+                 mk(cq.x, cq.y, cq.z), cq.w, su, sw, sc, used);
+}
+
 template <int MODE, class Args>
 __device__ __forceinline__ void level_finish(const Args& v, int i, bool used, f3 c_p, float a_p, float su, float sw,
                                              f3 sc) {
-    if constexpr (MODE == kLvCounts) {
-        if (!used) {
-            level_store<MODE>(v, i, c_p, a_p);
-            return;
-        }
-        level_store<MODE>(v, i, smul(rcp_rn(sw), sc), pv_clampc(sw / su));
-    } else if constexpr (MODE == kLvNoise) {
-        const float r = rcp_rn(sw);
-        level_store<MODE>(v, i, smul(r, sc), !(a_p < 0.f) ? (su * r) * r : a_p);
-    } else {
-        level_store<MODE>(v, i, smul(rcp_rn(sw), sc), 0.f);
-    }
+    float a;
+    const f3 o = lv_finish<MODE>(used, c_p, a_p, su, sw, sc, a);
+    level_store<MODE>(v, i, o, a);
 }
 
 // One level, taps straight from L1 / L2: one lane per pixel, two 16-byte loads per tap (guide
@@ -201,7 +109,6 @@ __device__ __forceinline__ void level_direct(const Args& v) {
         return;
     }
     const f3 n_p = mk(gp.x, gp.y, gp.z);
-    constexpr float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
     float su = 0.f, sw = 0.f;
     f3 sc = mk(0.f, 0.f, 0.f);
     bool used = false;
@@ -224,7 +131,7 @@ __device__ __forceinline__ void level_direct(const Args& v) {
 #pragma unroll
         for (int t = 0; t < 5; t++)
             if (in[t] && __float_as_int(gq[t].w) == gid)
-                level_tap<NP, MODE>(v, hk[j] * hk[t], n_p, c_p, a_p, gq[t], cq[t], su, sw, sc, used);
+                level_tap<NP, MODE>(v, j, t, n_p, c_p, a_p, gq[t], cq[t], su, sw, sc, used);
     }
     level_finish<MODE>(v, i, used, c_p, a_p, su, sw, sc);
 }
@@ -265,7 +172,6 @@ __device__ __forceinline__ void level_staged(const Args& v) {
         return;
     }
     const f3 n_p = mk(gp.x, gp.y, gp.z);
-    constexpr float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
     float su = 0.f, sw = 0.f;
     f3 sc = mk(0.f, 0.f, 0.f);
     bool used = false;
@@ -276,7 +182,7 @@ __device__ __forceinline__ void level_staged(const Args& v) {
             const int q = li + (j - 2) * v.step * rw + (t - 2) * v.step;
             const float4 gq = sg[q];
             if (__float_as_int(gq.w) != gid) continue;
-            level_tap<NP, MODE>(v, hk[j] * hk[t], n_p, c_p, a_p, gq, scol[q], su, sw, sc, used);
+            level_tap<NP, MODE>(v, j, t, n_p, c_p, a_p, gq, scol[q], su, sw, sc, used);
         }
     }
     level_finish<MODE>(v, i, used, c_p, a_p, su, sw, sc);
@@ -311,8 +217,8 @@ extern "C" const void* bdpt_dnoise_level_table[2][7] = {BDPT_LEVEL_ROW(bdpt_dnoi
 // The noise-guided denoiser's own kernels (include/bdpt.h bdpt_denoise_noise; no
 // reference counterpart).  Host sequence on the context's stream: bdpt_aov_kernel,
 // bdpt_dnoise_pack_kernel, bdpt_dnoise_prefilter_kernel, then the bdpt_dnoise_level_t instances
-// above, ping-pong from the prefilter's output.  Numerics as for the denoiser; a / (n - a) and
-// sv / sh are the compiler's correctly rounded divisions (denormals kept).
+// above, ping-pong from the prefilter's output.  Numerics as for the denoiser; bdpt_filter.h's
+// a / (n - a) and sv / sh are the compiler's correctly rounded divisions (denormals kept).
 
 // Guide records as bdpt_denoise_pack_kernel writes them, and {B, raw variance v0 or -1} into the
 // ping buffer.  mark: the noise estimate's records, nullptr while none was ever stored; live = 0:
@@ -324,8 +230,7 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_dnoise_pack_kernel(
     float4* __restrict__ ping, int count) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
-    int g = id[i];
-    if (g >= 0 && !all_materials && sph[g].refl != BDPT_DEV_DIFF) g = -1;
+    const int g = guide_id(id[i], all_materials, sph);
     const bdpt_dev_vec n = normal[i];
     guide[i] = make_float4(n.x, n.y, n.z, __int_as_float(g));
     const bdpt_dev_vec B = colors[i];
@@ -333,12 +238,10 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_dnoise_pack_kernel(
     if (mark && live) {
         const uint4 rec = mark[i];
         const unsigned cnt = counter[i], mn = rec.w;
-        // 2*(cnt - mn) >= mn without the overflow, as in bdpt_noise_kernel
-        if (mn > 0u && cnt > mn && cnt - mn >= (mn >> 1) + (mn & 1u)) {
-            const f3 d = sub(mk(B.x, B.y, B.z), mk(__uint_as_float(rec.x), __uint_as_float(rec.y), __uint_as_float(rec.z)));
-            const float a = (float)mn, nf = (float)cnt;
-            v0 = dot(d, d) * (a / (nf - a));
-        }
+        const f3 A = mk(__uint_as_float(rec.x), __uint_as_float(rec.y), __uint_as_float(rec.z));
+        // formed by every lane and kept where the mark is valid: the record stays one 16-byte load
+        const float v = raw_variance(mk(B.x, B.y, B.z), A, cnt, mn);
+        if (mark_valid(cnt, mn)) v0 = v;
     }
     ping[i] = make_float4(B.x, B.y, B.z, v0);
 }
@@ -368,7 +271,6 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_dnoise_prefilter_kernel(c
     float4 rec = cur[i];
     const int gid = __float_as_int(sv0[li].x);
     if (gid >= 0) {
-        constexpr float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
         float sv = 0.f, sh = 0.f;
         bool used = false;
 #pragma unroll
@@ -376,13 +278,10 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_dnoise_prefilter_kernel(c
 #pragma unroll
             for (int t = 0; t < 5; t++) {
                 const float2 e = sv0[li + (j - 2) * rw + (t - 2)];
-                if (__float_as_int(e.x) != gid || e.y < 0.f) continue;
-                sv = sv + (hk[j] * hk[t]) * e.y;
-                sh = sh + hk[j] * hk[t];
-                used = true;
+                pf_tap(b3_weight(j, t), __float_as_int(e.x) == gid, e.y, sv, sh, used);
             }
         }
-        rec.w = used ? sv / sh : -1.0f;
+        rec.w = pf_finish(used, sv, sh);
     }
     nxt[i] = rec;
 }
@@ -391,9 +290,9 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_dnoise_prefilter_kernel(c
 // Temporal reprojection (include/bdpt.h bdpt_reproject; no reference counterpart).
 // Host sequence on the context's stream: bdpt_aov_kernel (unjittered, whole frame, under the
 // current camera), then bdpt_reproject_kernel; a capture also packs the planes into the next
-// history's guide records.  Numerics as for the denoiser above: the definition operation for
-// operation, fp32 without contraction, dot() as (x + y) + z, every reciprocal through rcp_rn
-// (library division outside [2^-125, 2^125): cz = 0, a denormal sw), denormals kept.
+// history's guide records.  Numerics as for the denoiser above: bdpt_filter.h's rp_project, rp_tap,
+// rp_history and rp_blend with every reciprocal through rcp_rn (library division outside
+// [2^-125, 2^125): cz = 0, a denormal sw), denormals kept.
 
 // History records from planes: guide = {position, id} (either pair of pointers may be null).
 extern "C" __global__ __launch_bounds__(256) void bdpt_history_pack_kernel(
@@ -427,21 +326,15 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_reproject_kernel(bdpt_rep
     const f3 c = mk(c3.x, c3.y, c3.z);
     const float n = (float)v.counter[i];
     const int id1 = v.id[i];
-    bool eligible = v.hguide != nullptr && id1 >= 0;
-    if (eligible && !v.all_materials) eligible = v.sph[id1].refl == BDPT_DEV_DIFF;
+    const int g1 = guide_id(id1, v.all_materials, v.sph);   // the pixel's sphere where it is eligible
     float m = 0.f;
     f3 h = mk(0.f, 0.f, 0.f);
-    if (eligible) {
+    if (v.hguide != nullptr && g1 >= 0) {
         const bdpt_dev_vec p3 = v.position[i], n3 = v.normal[i];
         const f3 P = mk(p3.x, p3.y, p3.z), N = mk(n3.x, n3.y, n3.z);
-        const f3 d = sub(P, mk(v.o[0], v.o[1], v.o[2]));
-        const float a = dot(d, mk(v.ux[0], v.ux[1], v.ux[2]));
-        const float b = dot(d, mk(v.uy[0], v.uy[1], v.uy[2]));
-        const float cz = dot(d, mk(v.ud[0], v.ud[1], v.ud[2]));
-        const float r = rcp_rn(cz);
-        const float kx = (10.f * a) * r, ky = (10.f * b) * r;
-        const float fx = (kx + v.hw) * v.sx, fy = (ky + v.hh) * v.sy;
-        if (fx >= -1.f && fx < (float)v.W && fy >= -1.f && fy < (float)v.H) {   // a NaN fails
+        float fx, fy;
+        if (rp_project(P, mk(v.o[0], v.o[1], v.o[2]), mk(v.ux[0], v.ux[1], v.ux[2]), mk(v.uy[0], v.uy[1], v.uy[2]),
+                       mk(v.ud[0], v.ud[1], v.ud[2]), v.hw, v.hh, v.sx, v.sy, v.W, v.H, fx, fy)) {
             const float xf = floorf(fx), yf = floorf(fy);
             const float wx = fx - xf, wy = fy - yf;
             const int qx0 = (int)xf, qy0 = (int)yf;       // -1 .. W-1, -1 .. H-1
@@ -460,37 +353,18 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_reproject_kernel(bdpt_rep
             f3 sc = mk(0.f, 0.f, 0.f);
             bool used = false;
 #pragma unroll
-            for (int k = 0; k < 4; k++) {                 // dy outer, dx inner, as defined
-                const float bx = (k & 1) ? wx : 1.f - wx, by = (k >> 1) ? wy : 1.f - wy;
-                const float bw = bx * by;
-                if (!in[k] || !(bw > 0.f) || __float_as_int(gq[k].w) != id1 || !(cq[k].w > 0.f)) continue;
-                if (!(fabsf(dot(sub(mk(gq[k].x, gq[k].y, gq[k].z), P), N)) <= lim)) continue;
-                sw = sw + bw;
-                sm = sm + bw * fminf(cq[k].w, v.max_history);
-                sc = add(sc, smul(bw, mk(cq[k].x, cq[k].y, cq[k].z)));
-                used = true;
-            }
-            if (used) {
-                h = smul(rcp_rn(sw), sc);
-                m = sm;
-            }
+            for (int k = 0; k < 4; k++)
+                rp_tap(k, wx, wy, in[k], __float_as_int(gq[k].w), mk(gq[k].x, gq[k].y, gq[k].z),
+                       mk(cq[k].x, cq[k].y, cq[k].z), cq[k].w, id1, P, N, lim, v.max_history, sw, sm, sc, used);
+            rp_history(used, sw, sm, sc, h, m);
         }
     }
-    const float tot = n + m;
-    f3 o = c;
-    if (m == 0.f) {
-    } else if (n == 0.f) {
-        o = h;
-    } else {
-        const float rt = rcp_rn(tot);
-        o = mk((n * c.x + m * h.x) * rt, (n * c.y + m * h.y) * rt, (n * c.z + m * h.z) * rt);
-    }
-    if (v.next) v.next[i] = make_float4(o.x, o.y, o.z, v.clamp_next ? pv_clampc(tot) : tot);
+    float tot;
+    const f3 o = rp_blend(c, n, h, m, tot);
+    if (v.next) v.next[i] = make_float4(o.x, o.y, o.z, v.clamp_next ? clampc(tot) : tot);
     if (v.dn_guide) {                                    // the denoiser's guide record of the pixel
-        int g = id1;
-        if (g >= 0 && !v.all_materials && v.sph[g].refl != BDPT_DEV_DIFF) g = -1;
         const bdpt_dev_vec n3 = v.normal[i];
-        v.dn_guide[i] = make_float4(n3.x, n3.y, n3.z, __int_as_float(g));
+        v.dn_guide[i] = make_float4(n3.x, n3.y, n3.z, __int_as_float(g1));
     }
     if (v.out3) {
         bdpt_dev_vec ov;
@@ -509,8 +383,9 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_reproject_kernel(bdpt_rep
 // 1 .. 32: fp32 addition is commutative, so every lane, lane 0 among them, holds the value of the
 // tree over the wave's 64 slots), the four wave partials meet in LDS as (p0 + p1) + (p2 + p3): the
 // tree's last two rounds.  Counts are a ballot and a popcount per wave.  No atomics; the frame's
-// summary is formed on the host from the tile arrays.  a / b is the compiler's correctly rounded
-// division (denormals kept), the roots are bdpt_sqrt_rn.
+// summary is formed on the host from the tile arrays.  The mark rules and the per-pixel error are
+// bdpt_filter.h's: a / b is the compiler's correctly rounded division (denormals kept), the roots
+// are bdpt_sqrt_rn.
 extern "C" __global__ __launch_bounds__(256) void bdpt_noise_mark_kernel(const bdpt_dev_vec* __restrict__ colors,
                                                                          const unsigned* __restrict__ counter,
                                                                          uint4* __restrict__ mark, int np) {
@@ -535,30 +410,22 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_noise_kernel(bdpt_noise_a
         uint4 rec = make_uint4(0u, 0u, 0u, 0u);
         if (v.mark) rec = v.mark[i];
         const unsigned mn = v.live ? rec.w : 0u;
-        // 2*(cnt - mn) >= mn without the overflow: cnt - mn >= ceil(mn / 2)
-        ok = mn > 0u && cnt > mn && cnt - mn >= (mn >> 1) + (mn & 1u);
-        const bool growing = cnt > 0u && cnt < BDPT_DEV_COUNTER_CAP;
-        pending = growing && !ok;
+        ok = mark_valid(cnt, mn);
+        pending = mark_growing(cnt) && !ok;
         float pe = -1.0f;
         if (ok) {
-            const float a = (float)mn, n = (float)cnt;
-            const float dx = B.x - __uint_as_float(rec.x), dy = B.y - __uint_as_float(rec.y),
-                        dz = B.z - __uint_as_float(rec.z);
-            const float e1 = (fabsf(dx) + fabsf(dy)) + fabsf(dz);
-            const float s = a / (n - a);
-            const float f = bdpt_sqrt_rn(s);
-            const float lum = (B.x + B.y) + B.z;
-            const float den = bdpt_sqrt_rn(fmaxf(lum, v.dark));
-            pe = (e1 * f) / den;
+            const f3 A = mk(__uint_as_float(rec.x), __uint_as_float(rec.y), __uint_as_float(rec.z));
+            pe = pixel_error(mk(B.x, B.y, B.z), A, cnt, mn, v.dark);
             e = pe;
         }
         if (v.error) v.error[i] = pe;
-        if (v.remark) {                                  // cnt >= 2*mn as (cnt >> 1) >= mn
-            const bool take = growing && (cnt >> 1) >= mn;
+        if (v.remark) {
             // a cleared mark becomes live again with this call: a pixel that does not take it
             // keeps its colour and stores the count 0 it was read with
-            if (take) v.mark[i] = make_uint4(__float_as_uint(B.x), __float_as_uint(B.y), __float_as_uint(B.z), cnt);
-            else if (!v.live) v.mark[i] = make_uint4(rec.x, rec.y, rec.z, 0u);
+            if (mark_take(cnt, mn))
+                v.mark[i] = make_uint4(__float_as_uint(B.x), __float_as_uint(B.y), __float_as_uint(B.z), cnt);
+            else if (!v.live)
+                v.mark[i] = make_uint4(rec.x, rec.y, rec.z, 0u);
         }
     }
     float s = e;
