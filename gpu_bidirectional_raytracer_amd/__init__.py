@@ -335,6 +335,13 @@ class Renderer:
     def synchronize(self) -> None:
         self._chk(lib.bdpt_synchronize(self._h))
 
+    def calls_in_flight(self) -> int:
+        """How many path_passes calls the device has not finished (0..4 per device; 0 on the CPU
+        backend).  Never waits: it tells whether the next call is queued behind running passes."""
+        n = ctypes.c_int()
+        self._chk(lib.bdpt_calls_in_flight(self._h, ctypes.byref(n)))
+        return n.value
+
     def last_path_ms(self) -> float:
         ms = ctypes.c_float()
         self._chk(lib.bdpt_last_path_ms(self._h, ctypes.byref(ms)))

@@ -148,6 +148,7 @@ _SIGS = [
     ("bdpt_path_passes", ctypes.c_int, [_P, _P, _P, ctypes.c_int]),
     ("bdpt_path_passes_tiles", ctypes.c_int, [_P, _P, _P, ctypes.c_int, _P]),
     ("bdpt_synchronize", ctypes.c_int, [_P]),
+    ("bdpt_calls_in_flight", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int)]),
     ("bdpt_last_path_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_path_timing", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]),

@@ -1703,6 +1703,31 @@ int bdpt_synchronize(bdpt_ctx* c) {
         if (int rc = one_synchronize(p)) return fail(c, rc, "device %d: %s", p->device, p->err);
     return BDPT_OK;
 }
+// How many path-pass calls the GPU has not finished: the ring slots not folded yet whose closing
+// event has not fired.  Only queries: no wait, no timing folded, nothing issued.
+static int one_calls_in_flight(bdpt_ctx* c, int* n) {
+    if (c->cpu) return BDPT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    for (const bdpt_ctx::call_slot& s : c->ring) {
+        if (!s.pending) continue;
+        const hipError_t e = hipEventQuery(s.ev1);
+        if (e == hipErrorNotReady) {
+            (void)hipGetLastError();                         // not-ready is an answer, not an error to keep
+            ++*n;
+        } else if (e != hipSuccess) {
+            return fail(c, BDPT_EHIP, "hipEventQuery: %s", hipGetErrorString(e));
+        }
+    }
+    return BDPT_OK;
+}
+int bdpt_calls_in_flight(bdpt_ctx* c, int* n) {
+    if (!c || !n) return BDPT_EINVAL;
+    *n = 0;
+    if (int rc = one_calls_in_flight(c, n)) return rc;
+    for (bdpt_ctx* p : c->peers)
+        if (int rc = one_calls_in_flight(p, n)) return fail(c, rc, "device %d: %s", p->device, p->err);
+    return BDPT_OK;
+}
 // Multi-device: the slowest device's time (the devices run concurrently); launches of devices[0].
 int bdpt_path_timing(bdpt_ctx* c, double* total_ms, long long* launches, int reset) {
     if (int rc = one_path_timing(c, total_ms, launches, reset)) return rc;

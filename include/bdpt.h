@@ -234,6 +234,12 @@ int  bdpt_path_passes(bdpt_ctx *ctx, const unsigned *sid, const int *vlp_index, 
 int  bdpt_path_passes_tiles(bdpt_ctx *ctx, const unsigned *sid, const int *vlp_index, int npass,
                             const unsigned char *tile_mask);
 int  bdpt_synchronize(bdpt_ctx *ctx);
+/* *n = the path-pass calls the device has not finished yet: calls whose timing is not folded and
+ * whose closing event has not fired (at most 4, the depth of the call ring; a multi-device context
+ * sums its devices).  Read-only: it never waits, issues nothing and folds no timing, so a caller
+ * can tell whether what it issues next is queued behind running passes.  0 on the CPU backend.
+ * BDPT_EINVAL for a NULL argument. */
+int  bdpt_calls_in_flight(bdpt_ctx *ctx, int *n);
 /* Device time (ms, HIP events on the context's stream) of the last bdpt_path_passes call. */
 int  bdpt_last_path_ms(bdpt_ctx *ctx, float *ms);
 /* Accumulated device time and kernel-launch count of all path-pass calls since the last reset
