@@ -25,6 +25,11 @@ them, hence the light pass at current_sample = 3 (table seed 15).  :562 and :619
 sid >= RAND_N - 5 - 26 - 25*i - 5*depth: wrap_sids() places that threshold on pixels inside the
 frame, for depth 0 and for later depths of one path (tests/test_ref_parity.py checks the
 arithmetic), and adds sid = RAND_N - 1, the largest value rand() % RAND_N can take.
+
+counts40 is no scene file: tests/count_scenes.py scene(40, (31, 32, 39)), 40 spheres with emitters
+on both sides of bit 32 of the specialised kernels' emitter mask, so that the oracle the sweep over
+sphere counts (tests/test_gpu_sphere_counts.py) compares with is itself held to the reference at
+such a count and layout.
 """
 import json
 import os
@@ -34,7 +39,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-for _p in (REPO, HERE):
+for _p in (REPO, HERE, os.path.dirname(HERE)):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
@@ -75,8 +80,18 @@ def _scene(name):
     return orig, target, sp
 
 
-def _case(name, scene, W, H, sid, vlp, current_sample=0, edit=None, colors0=None, counter0=None, note=""):
-    orig, target, sp = _scene(scene)
+def _count_scene(n, emitters):
+    """tests/count_scenes.py scene(n, emitters) as (orig, target, spheres)."""
+    import count_scenes
+    cam, sp = count_scenes.scene(n, emitters)
+    o, t = cam.orig, cam.target
+    return (np.array([o.x, o.y, o.z], np.float32), np.array([t.x, t.y, t.z], np.float32),
+            sp.astype(oracle.SPHERE_DTYPE))
+
+
+def _case(name, scene, W, H, sid, vlp, current_sample=0, edit=None, colors0=None, counter0=None, note="",
+          spheres=None):
+    orig, target, sp = _scene(scene) if spheres is None else spheres
     if edit is not None:
         edit(sp)
     cam = oracle.update_camera(orig, target, W, H)
@@ -131,6 +146,9 @@ def cases():
                           "would leave d_Rand uninitialised, smallpt_cpu.c:311-322)"))
     out.append(_case("three_emitters", "cornell_2luci", W20, H19, SCHED_SID[:6], SCHED_VLP[:6],
                      edit=_three_emitters, note="three unequal emitters, one of them the glass ball"))
+    out.append(_case("counts40", "count_scenes.scene(40, (31, 32, 39))", W20, H19, SCHED_SID[:6], SCHED_VLP[:6],
+                     spheres=_count_scene(40, (31, 32, 39)),
+                     note="40 spheres, emitters at indices 31, 32 and 39: both words of the emitter mask"))
     return out
 
 

@@ -396,7 +396,32 @@ static void envs() {
     CHECK(!flags("-DBDPT_SREC=1 -DBDPT_SREC=0").srec_enabled());
 }
 
-int main() {
+// The rules tests/count_scenes.py restates, as a table for tests/test_count_scenes_cpu.py (argument
+// "rules"): "vac <n> <n_vac> <vac_list>" for every 0 <= n_vac <= n <= 64 from bdpt_jit_scene, and
+// "pf <nl> <lg> <fits> <iters>" for every 1 <= nl <= 64, 1 <= lg <= 5 from the part-full rounds'
+// two functions.  Those live in device code; they are quoted here from bdpt_kernels.hip:450 and
+// :453 (BDPT_PF_MAX_IT: :124), and the Python test holds the quotation to that file's text.
+#define BDPT_PF_MAX_IT 8
+constexpr int pf_iters(int nl, int lg) { return (nl + (1 << lg) - 1) >> lg; }
+constexpr bool pf_fits(int nl, int lg) { return (1 << (lg - 1)) < nl && pf_iters(nl, lg) <= BDPT_PF_MAX_IT; }
+
+static void rules() {
+    for (unsigned n = 1; n <= 64; n++)
+        for (unsigned n_vac = 0; n_vac <= n; n_vac++) {
+            bdpt_jit_scene s;
+            s.n = n;
+            s.n_vac = n_vac;
+            printf("vac %u %u %d\n", n, n_vac, s.vac_list() ? 1 : 0);
+        }
+    for (int nl = 1; nl <= 64; nl++)
+        for (int lg = 1; lg <= 5; lg++) printf("pf %d %d %d %d\n", nl, lg, pf_fits(nl, lg) ? 1 : 0, pf_iters(nl, lg));
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "rules") {
+        rules();
+        return 0;
+    }
     scenes();
     options();
     first_attempts();

@@ -14,7 +14,11 @@ second of NEE rays only), caustic (3 spheres: lg reduced to 2) and synthetic64
 pools.  The pool build leaves the switch off by default, so it is also run with it on.  Every
 comparison is on the bits: colours, counters and pixels against the oracle (computed once per
 scene and frame) and against the flag-off build, and every run proves through last_features and
-device_mode that the specialised kernel of the mode ran."""
+device_mode that the specialised kernel of the mode ran.
+
+These four scenes fix the sphere count and the emitters' indices; the sweep over counts 1..64 and
+emitter positions (every (lane-group count, list) body, masked tails, both widths of the emitter
+mask) lives in tests/test_gpu_sphere_counts.py, over the scenes of tests/count_scenes.py."""
 import numpy as np
 import pytest
 
