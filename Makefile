@@ -142,7 +142,8 @@ endif
 ASAN_FLAGS := -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -g -O1 -ffp-contract=off
 ASAN_DIR   := tests/native/_asan
 asan: $(ASAN_DIR)/smallpt_asan $(ASAN_DIR)/oracle_asan $(ASAN_DIR)/aov_asan $(ASAN_DIR)/denoise_asan $(ASAN_DIR)/reproject_asan \
-      $(ASAN_DIR)/preview_asan $(ASAN_DIR)/noise_asan $(ASAN_DIR)/tiles_asan $(ASAN_DIR)/denoise_noise_asan
+      $(ASAN_DIR)/preview_asan $(ASAN_DIR)/noise_asan $(ASAN_DIR)/tiles_asan $(ASAN_DIR)/denoise_noise_asan \
+      $(ASAN_DIR)/chain_asan
 
 $(ASAN_DIR):
 	mkdir -p $(ASAN_DIR)
@@ -195,6 +196,11 @@ $(ASAN_DIR)/noise_asan: tests/native/noise_asan.cpp $(CSRC)/bdpt_cpu.h include/b
 
 # the CPU backend's noise-guided denoiser (bdpt_cpu_denoise_noise) driven directly; tests/test_denoise_noise_asan.py
 $(ASAN_DIR)/denoise_noise_asan: tests/native/denoise_noise_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
+	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
+
+# the CPU backend's chain buffers and the denoiser guided through them (bdpt_cpu_render_chain,
+# bdpt_cpu_denoise with BDPT_DENOISE_THROUGH) driven directly; tests/test_chain_asan.py
+$(ASAN_DIR)/chain_asan: tests/native/chain_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
 	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
 
 # the CPU backend's masked path passes (bdpt_cpu_path_passes with a tile mask) driven directly; tests/test_tiles_asan.py

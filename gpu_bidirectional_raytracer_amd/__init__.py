@@ -19,6 +19,7 @@ import numpy as np
 
 from ._lib import (BDPT_OK, CHOICES, COUNTER_CAP, DEFAULT_DAT, DIFF, FEATURES, KEY_DOWN, KEY_LEFT, KEY_PAGE_DOWN,
                    KEY_PAGE_UP, KEY_RIGHT, KEY_UP, LIGHT_POINTS, LITE, RAND_N, REFR, SCENE_DIR, SPEC,
+                   CHAIN_BRANCHES, CHAIN_KIND_DIFFUSE, CHAIN_KIND_EMITTER, CHAIN_KIND_EXHAUSTED, CHAIN_KIND_MISS, ChainBuffers,
                    DENOISE_MATERIALS, AovBuffers, BdptError, Camera, DenoiseNoiseParams, DenoiseParams, LightPath, NoiseParams, NoiseSummary, PassState, PreviewParams,
                    RandState, ReprojectParams, Sphere, Vec, lib)
 
@@ -26,7 +27,8 @@ __all__ = [
     "Vec", "Sphere", "Camera", "LightPath", "Renderer", "SmallPT", "PassScheduler", "read_scene",
     "default_scene", "update_camera", "camera_key", "sphere_key", "save_ppm", "ppm_name", "glibc_rand",
     "spheres_to_array", "RAND_N", "LIGHT_POINTS", "COUNTER_CAP", "DIFF", "SPEC", "REFR", "LITE",
-    "SCENE_DIR", "DEFAULT_DAT", "BdptError", "AOV_PLANES",
+    "SCENE_DIR", "DEFAULT_DAT", "BdptError", "AOV_PLANES", "CHAIN_PLANES", "CHAIN_KIND_DIFFUSE",
+    "CHAIN_KIND_EMITTER", "CHAIN_KIND_MISS", "CHAIN_KIND_EXHAUSTED",
 ]
 
 SPHERE_DTYPE = np.dtype([("rad", "<f4"), ("p", "<f4", 3), ("e", "<f4", 3), ("c", "<f4", 3),
@@ -36,6 +38,8 @@ LIGHTPATH_DTYPE = np.dtype([("hp", "<f4", 3), ("rad", "<f4", 3), ("nl", "<f4", 3
 
 
 AOV_PLANES = ("id", "t", "dp", "position", "normal", "dir")     # bdpt_aov_buffers, in its order
+CHAIN_PLANES = ("id", "first_id", "kind", "bounces", "t", "dp", "position", "normal", "dir",
+                "throughput")                                      # bdpt_chain_buffers, in its order
 
 
 def _ptr(a: np.ndarray) -> ctypes.c_void_p:
@@ -414,6 +418,13 @@ class Renderer:
         self._chk(lib.bdpt_read_rand(self._h, _ptr(t)))
         return t
 
+    def write_rand(self, table) -> None:
+        """Upload a whole random table ([RAND_N] float32; bdpt_write_rand): tests render on tables no
+        seed produces."""
+        t = np.ascontiguousarray(table, np.float32)
+        assert t.shape == (RAND_N,)
+        self._chk(lib.bdpt_write_rand(self._h, _ptr(t)))
+
     def read_sample_records(self) -> np.ndarray:
         """The sample records of the current table, [RAND_N - 5, 8] = {A, B, C, u2, X, Y, Z, u0} per
         position (include/bdpt.h bdpt_read_sample_records)."""
@@ -487,6 +498,34 @@ class Renderer:
         self._chk(lib.bdpt_last_aov_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
+    # -- chain buffers (no reference counterpart; include/bdpt.h bdpt_render_chain)
+    def render_chain(self, sid: Optional[int] = None, branch: str = "transmit",
+                     window: Optional[Tuple[int, int, int, int]] = None,
+                     planes: Sequence[str] = CHAIN_PLANES) -> dict:
+        """Every pixel's eye path up to its first non-specular vertex -- what the pixel shows through
+        mirrors and glass -- in the path kernel's arithmetic: a dict of id (the end sphere, -1 for a
+        miss or an exhausted chain), first_id (render_aov's id), kind (CHAIN_KIND_*), bounces
+        [h, w] int32, t (the summed distance), dp [h, w] float32 and position, normal (of the end
+        vertex), dir, throughput [h, w, 3] float32.  sid, window as for render_aov.  branch: what
+        glass does -- "transmit" refracts whenever refraction exists, "pass" takes the choice the
+        pass with that sid makes (needs sid).  Changes nothing else of the context."""
+        x0, y0, w, h = (0, 0, self.width, self.height) if window is None else (int(v) for v in window)
+        shape = (max(h, 0), max(w, 0))
+        out = {k: np.empty(shape + ((3,) if k in ("position", "normal", "dir", "throughput") else ()),
+                           np.int32 if k in ("id", "first_id", "kind", "bounces") else np.float32)
+               for k in CHAIN_PLANES if k in planes}
+        buf = ChainBuffers(**{k: a.ctypes.data for k, a in out.items()})
+        self._chk(lib.bdpt_render_chain(self._h, x0, y0, w, h, int(sid is not None), int(sid or 0),
+                                        CHAIN_BRANCHES.get(branch, -1) if isinstance(branch, str) else int(branch),
+                                        ctypes.byref(buf)))
+        return out
+
+    def last_chain_ms(self) -> float:
+        """Device time (ms) of the last render_chain kernel alone, without the read-back."""
+        ms = ctypes.c_float()
+        self._chk(lib.bdpt_last_chain_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
     # -- denoiser (no reference counterpart; include/bdpt.h bdpt_denoise)
     def denoise(self, levels: int = 4, normal_power: int = 5, sigma_color: float = 0.5,
                 materials: str = "diffuse", pixels: bool = False):
@@ -494,7 +533,9 @@ class Renderer:
         the unjittered first hit's sphere id and normal: `levels` a-trous levels (1..8, steps 1, 2,
         4, ...), the normals' cosine squared `normal_power` times (0..6), colour stopping
         1 / (1 + |dc|^2 4^k / sigma_color^2) (sigma_color > 0; inf: none).  materials="diffuse"
-        filters only pixels that show a DIFF sphere, "all" every hit; the others are copied through.
+        filters only pixels that show a DIFF sphere, "all" every hit; "through" takes the guides
+        from render_chain instead -- pixels whose chain through mirrors and glass ends on a diffuse
+        surface, matched by what they show and through what; the others are copied through.
         Returns the [H, W, 3] float32 frame, or (frame, rgba [H, W, 4] uint8 through read_pixels'
         thresholds) with pixels=True.  Changes nothing else of the context."""
         prm = DenoiseParams(int(levels), int(normal_power), float(sigma_color), DENOISE_MATERIALS[materials])

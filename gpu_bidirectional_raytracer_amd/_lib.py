@@ -53,6 +53,16 @@ class AovBuffers(ctypes.Structure):
                 ("position", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("dir", ctypes.c_void_p)]
 
 
+class ChainBuffers(ctypes.Structure):
+    """bdpt_chain_buffers: host pointers of the ten chain planes, NULL = not wanted."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("id", "first_id", "kind", "bounces", "t", "dp", "position", "normal",
+                                               "dir", "throughput")]
+
+
+CHAIN_BRANCHES = {"transmit": 0, "pass": 1}                 # BDPT_CHAIN_TRANSMIT / BDPT_CHAIN_PASS
+CHAIN_KIND_DIFFUSE, CHAIN_KIND_EMITTER, CHAIN_KIND_MISS, CHAIN_KIND_EXHAUSTED = range(4)   # BDPT_CHAIN_KIND_*
+
+
 class DenoiseParams(ctypes.Structure):
     """bdpt_denoise_params."""
     _fields_ = [("levels", ctypes.c_int), ("normal_power", ctypes.c_int), ("sigma_color", ctypes.c_float),
@@ -65,7 +75,7 @@ class DenoiseNoiseParams(ctypes.Structure):
                 ("materials", ctypes.c_int), ("noise_sigma", ctypes.c_float)]
 
 
-DENOISE_MATERIALS = {"diffuse": 0, "all": 1}               # BDPT_DENOISE_DIFFUSE / BDPT_DENOISE_ALL
+DENOISE_MATERIALS = {"diffuse": 0, "all": 1, "through": 3}  # BDPT_DENOISE_DIFFUSE / _ALL / _THROUGH (2: none)
 
 
 class ReprojectParams(ctypes.Structure):
@@ -155,6 +165,7 @@ _SIGS = [
     ("bdpt_read_radiance", ctypes.c_int, [_P, _P, _P]),
     ("bdpt_read_pixels", ctypes.c_int, [_P, _P]),
     ("bdpt_read_rand", ctypes.c_int, [_P, _P]),
+    ("bdpt_write_rand", ctypes.c_int, [_P, _P]),
     ("bdpt_read_lightpaths", ctypes.c_int, [_P, _P]),
     ("bdpt_read_sample_records", ctypes.c_int, [_P, _P]),
     ("bdpt_write_lightpaths", ctypes.c_int, [_P, _P]),
@@ -170,6 +181,9 @@ _SIGS = [
                                  ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_last_aov_traversal", ctypes.c_int, [_P]),
     ("bdpt_last_aov_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
+    ("bdpt_render_chain", ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_uint, ctypes.c_int, ctypes.POINTER(ChainBuffers)]),
+    ("bdpt_last_chain_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_denoise", ctypes.c_int, [_P, ctypes.POINTER(DenoiseParams), _P, _P]),
     ("bdpt_last_denoise_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_history_capture", ctypes.c_int, [_P, ctypes.POINTER(ReprojectParams)]),

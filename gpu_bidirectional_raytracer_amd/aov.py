@@ -1,7 +1,7 @@
 """First-hit feature buffers of a scene from the command line:
 
     python -m gpu_bidirectional_raytracer_amd.aov <width> <height> <scene> --out PREFIX
-                                                  [--sid N] [--device D] [--ppm]
+                                                  [--sid N] [--device D] [--ppm] [--through]
 
 Sizes get +1 like `smallpt` (smallpt_cpu.c:409-410).  Writes PREFIX.npz with the six arrays of
 Renderer.render_aov (id, t, dp, position, normal, dir; row 0 is the frame's bottom row, as in
@@ -9,6 +9,9 @@ read_radiance).  Without --sid the rays go through the pixel centres' unjittered
 --sid N they carry the jitter of a pass with that sid on the random table of the first light pass
 (seed 0).  --ppm also writes PREFIX_normal.ppm and PREFIX_id.ppm through save_ppm (bottom-up rows,
 as SavePPM).  No light pass and no path pass is rendered: checking a camera costs one cheap kernel.
+--through adds the chain planes of Renderer.render_chain -- what every pixel shows through mirrors
+and glass, glass transmitting -- to the .npz as chain_id, chain_first_id, ... chain_throughput, and
+with --ppm also writes PREFIX_through_normal.ppm, the end vertices' normals.
 """
 from __future__ import annotations
 
@@ -46,6 +49,7 @@ def main(argv=None) -> int:
     ap.add_argument("--sid", type=int, default=None, help="jitter of a pass with this sid (default: none)")
     ap.add_argument("--device", type=int, default=0, help="HIP ordinal, -1 = the CPU backend")
     ap.add_argument("--ppm", action="store_true", help="also write PREFIX_normal.ppm and PREFIX_id.ppm")
+    ap.add_argument("--through", action="store_true", help="add the chain planes (through mirrors and glass)")
     args = ap.parse_args(argv)
 
     W, H = args.width + 1, args.height + 1
@@ -55,10 +59,13 @@ def main(argv=None) -> int:
         if args.sid is not None:
             r.generate_rand(0)
         aov = r.render_aov(sid=args.sid)
-    np.savez_compressed(args.out + ".npz", **aov)
+        chain = r.render_chain(sid=args.sid) if args.through else {}
+    np.savez_compressed(args.out + ".npz", **aov, **{f"chain_{k}": v for k, v in chain.items()})
     if args.ppm:
         save_ppm(args.out + "_normal.ppm", normal_rgba(aov))
         save_ppm(args.out + "_id.ppm", id_rgba(aov))
+        if args.through:
+            save_ppm(args.out + "_through_normal.ppm", normal_rgba(chain))
     hit = aov["id"] >= 0
     print(f"{W}x{H}: {int(hit.sum())} of {hit.size} pixels hit {len(np.unique(aov['id'][hit]))} of "
           f"{len(spheres)} spheres -> {args.out}.npz", file=sys.stderr)

@@ -436,6 +436,90 @@ struct PathTracer {
         }
         return rad;
     }
+
+    // The eye path of sample() up to its first non-specular vertex (include/bdpt.h bdpt_render_chain):
+    // the same vertex arithmetic, stopped at the first emitter, diffuse surface or miss.  pass: glass
+    // takes pass sid's choice (rnd[j + 2] < P), else it transmits whenever refraction exists.
+    struct Chain {
+        int id = -1, first_id = -1, kind = BDPT_CHAIN_KIND_EXHAUSTED, bounces = 0;
+        float t = 0.f, dp = 0.f;
+        V3 pos = v3(0.f, 0.f, 0.f), nrm = v3(0.f, 0.f, 0.f), dir, thr = v3(1.f, 1.f, 1.f);
+    };
+    Chain chain(int x, int y, int W, bool jitter, unsigned sid, bool pass) const {
+        const unsigned base = 26u + (unsigned)(y * W + x) * 25u;
+        float u0 = 0.f, u1 = 0.f;                                // no jitter: both randoms +0
+        if (jitter) {
+            const unsigned kk = (base + sid) % (kRandN - 5u);
+            u0 = rnd[kk];
+            u1 = rnd[kk + 1];
+        }
+        V3 o, d;
+        camera_ray(x, y, u0, u1, &o, &d);
+        Chain r;
+        float len = 0.f, dp = 0.f;
+        V3 h = r.pos, normal = r.nrm;
+        for (unsigned depth = 0; depth <= 6; ++depth) {
+            float t;
+            unsigned id = 0;
+            const bool hit = sc.closest(o, d, &t, &id);
+            if (depth == 0) r.first_id = hit ? (int)id : -1;
+            if (!hit) {
+                r.kind = BDPT_CHAIN_KIND_MISS;
+                break;
+            }
+            const bdpt_sphere& S = sc.s[id];
+            len = len + t;
+            h = o + t * d;
+            normal = unit(h - of(S.p));
+            dp = dot(normal, d);
+            const V3 nl = (-1.f * (float)(dp > 0 ? 1 : -1)) * normal;
+            if (sc.emissive[id]) {                                   // :651, before the material
+                r.kind = BDPT_CHAIN_KIND_EMITTER;
+                r.id = (int)id;
+                break;
+            }
+            if (S.refl == BDPT_DIFF) {
+                r.kind = BDPT_CHAIN_KIND_DIFFUSE;
+                r.id = (int)id;
+                break;
+            }
+            r.bounces++;
+            const V3 refl = d - (2.f * dot(normal, d)) * normal;
+            o = h;
+            if (S.refl == BDPT_SPEC) {                               // :704-714
+                r.thr = r.thr * of(S.c);
+                d = refl;
+                continue;
+            }
+            const bool into = dot(normal, nl) > 0;                   // REFR / LITE :715-770
+            const float nc = 1.f, nt = 1.5f, nnt = into ? nc / nt : nt / nc;
+            const float ddn = dot(d, nl);
+            const float cos2t = 1.f - nnt * nnt * (1.f - ddn * ddn);
+            if (cos2t < 0.f) {
+                r.thr = r.thr * of(S.c);
+                d = refl;
+                continue;
+            }
+            const float kq = (float)(into ? 1 : -1) * (ddn * nnt + sqrtf(cos2t));
+            const V3 td = unit(nnt * d - kq * normal);
+            const float a = nt - nc, b = nt + nc, R0 = a * a / (b * b);
+            const float cc = 1 - (into ? -ddn : dot(td, normal));
+            const float Re = R0 + (1 - R0) * cc * cc * cc * cc * cc, Tr = 1.f - Re, P = .25f + .5f * Re;
+            if (pass && rnd[(base + depth * 5u + sid) % (kRandN - 5u) + 2] < P) {
+                r.thr = (Re / P) * r.thr * of(S.c);
+                d = refl;
+            } else {
+                r.thr = (Tr / (1.f - P)) * r.thr * of(S.c);
+                d = td;
+            }
+        }
+        r.t = len;
+        r.dir = d;
+        if (r.kind == BDPT_CHAIN_KIND_DIFFUSE || r.kind == BDPT_CHAIN_KIND_EMITTER) {
+            r.dp = dp; r.pos = h; r.nrm = normal;
+        }
+        return r;
+    }
 };
 }  // namespace
 
@@ -528,6 +612,31 @@ void bdpt_cpu_render_aov(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, in
     render_aov_cam(c, c->cam, x0, y0, w, h, jitter, sid, out);
 }
 
+// The eye path up to its first non-specular vertex (include/bdpt.h bdpt_render_chain) for the
+// window's pixels, packed [h][w].  The caller has checked the window, the branch, the camera and
+// (jitter) the table.
+void bdpt_cpu_render_chain(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid, int branch,
+                           const bdpt_chain_buffers* out) {
+    const PathTracer pt(c);
+    const int W = c->W;
+    parallel_rows(y0, y0 + h, c->threads, [&](int y) {
+        for (int x = x0; x < x0 + w; x++) {
+            const PathTracer::Chain r = pt.chain(x, y, W, jitter != 0, sid, branch == BDPT_CHAIN_PASS);
+            const size_t k = (size_t)(y - y0) * w + (x - x0);
+            if (out->id) out->id[k] = r.id;
+            if (out->first_id) out->first_id[k] = r.first_id;
+            if (out->kind) out->kind[k] = r.kind;
+            if (out->bounces) out->bounces[k] = r.bounces;
+            if (out->t) out->t[k] = r.t;
+            if (out->dp) out->dp[k] = r.dp;
+            if (out->position) out->position[k] = {r.pos.x, r.pos.y, r.pos.z};
+            if (out->normal) out->normal[k] = {r.nrm.x, r.nrm.y, r.nrm.z};
+            if (out->dir) out->dir[k] = {r.dir.x, r.dir.y, r.dir.z};
+            if (out->throughput) out->throughput[k] = {r.thr.x, r.thr.y, r.thr.z};
+        }
+    });
+}
+
 namespace {
 // The unjittered whole-frame first hit under `cam`: the ids and the planes asked for.
 enum { kHitPos = 1, kHitT = 2, kHitNrm = 4 };
@@ -549,6 +658,32 @@ struct FirstHit {
     // the ids as the filters' guide ids: an ineligible pixel gets -1
     void to_guide_ids(const bdpt_cpu_ctx* c, int materials) {
         for (int& g : id) g = guide_id(g, materials == BDPT_DENOISE_ALL, c->scene.s.data());
+    }
+    // The denoisers' guides by `materials`: the first hit's ids made guide ids, or
+    // (BDPT_DENOISE_THROUGH, include/bdpt.h) the key and end normal of the unjittered TRANSMIT chain.
+    struct Guides {};
+    FirstHit(const bdpt_cpu_ctx* c, int materials, Guides) {
+        if (materials != BDPT_DENOISE_THROUGH) {
+            *this = FirstHit(c, c->cam, kHitNrm);
+            to_guide_ids(c, materials);
+            return;
+        }
+        const size_t np = (size_t)c->W * c->H;
+        std::vector<int> kind(np), bounces(np), first(np);
+        id.resize(np);
+        nrm.resize(np);
+        bdpt_chain_buffers g;
+        memset(&g, 0, sizeof g);
+        g.id = id.data(); g.first_id = first.data(); g.kind = kind.data(); g.bounces = bounces.data();
+        g.normal = nrm.data();
+        bdpt_cpu_render_chain(c, 0, 0, c->W, c->H, 0, 0u, BDPT_CHAIN_TRANSMIT, &g);
+        const int n = (int)c->scene.n;
+        for (size_t i = 0; i < np; i++) {
+            int key = -1;
+            if (kind[i] == BDPT_CHAIN_KIND_DIFFUSE)
+                key = bounces[i] == 0 ? id[i] : n + ((bounces[i] - 1) * n + first[i]) * n + id[i];
+            id[i] = key;
+        }
     }
 };
 
@@ -626,8 +761,7 @@ void write_plane(const std::vector<float>& a, float* out) {
 // and the camera; the context's own state is only read.
 void bdpt_cpu_denoise(const bdpt_cpu_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out,
                       unsigned char* rgba_out) {
-    FirstHit g(c, c->cam, kHitNrm);
-    g.to_guide_ids(c, p->materials);
+    const FirstHit g(c, p->materials, FirstHit::Guides{});
     std::vector<bdpt_vec> ping(c->colors);
     std::vector<float> none;
     atrous_levels<kLvPlain>(c, g, p->levels, p->normal_power, p->sigma_color, 0.f, ping, none);
@@ -765,6 +899,10 @@ void bdpt_cpu_read_radiance(const bdpt_cpu_ctx* c, bdpt_vec* colors, unsigned* c
 }
 void bdpt_cpu_read_pixels(const bdpt_cpu_ctx* c, unsigned char* rgba) { memcpy(rgba, c->pixels.data(), c->pixels.size()); }
 void bdpt_cpu_read_rand(const bdpt_cpu_ctx* c, float* t) { memcpy(t, c->rnd.data(), sizeof(float) * kRandN); }
+void bdpt_cpu_write_rand(bdpt_cpu_ctx* c, const float* t) {
+    c->rnd.assign(t, t + kRandN);
+    c->rand_ready = true;
+}
 void bdpt_cpu_read_lightpaths(const bdpt_cpu_ctx* c, bdpt_lightpath* lp) {
     memcpy(lp, c->lp.data(), sizeof(bdpt_lightpath) * BDPT_LIGHT_POINTS);
 }
@@ -852,8 +990,7 @@ void bdpt_cpu_denoise_noise(const bdpt_cpu_ctx* c, const bdpt_denoise_noise_para
                             unsigned char* rgba_out, float* variance_out) {
     const int W = c->W, H = c->H;
     const size_t np = (size_t)W * H;
-    FirstHit g(c, c->cam, kHitNrm);
-    g.to_guide_ids(c, p->materials);
+    const FirstHit g(c, p->materials, FirstHit::Guides{});
     const bool stored = !c->mark.empty();
     std::vector<float> v0(np, -1.0f), var(np);
     for (size_t i = 0; i < np; i++) {                     // the raw variance

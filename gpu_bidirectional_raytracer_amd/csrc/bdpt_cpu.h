@@ -24,6 +24,15 @@ void bdpt_cpu_path_passes(bdpt_cpu_ctx* c, const unsigned* sid, const int* vlp, 
                           const unsigned char* tile_mask = nullptr);
 void bdpt_cpu_render_aov(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid,
                          const bdpt_aov_buffers* out);
+// the eye path up to its first non-specular vertex (include/bdpt.h bdpt_render_chain); the caller has
+// checked the window, the branch, the camera and (jitter) the table
+void bdpt_cpu_render_chain(const bdpt_cpu_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid, int branch,
+                           const bdpt_chain_buffers* out);
+// materials = BDPT_DENOISE_THROUGH: the largest guide key, 6 n^2 + n - 1, must fit an int
+// (include/bdpt.h: a scene with 6 n^2 + n > 2^31 - 1 is refused)
+inline bool bdpt_chain_keys_fit(unsigned n) {
+    return 6ull * n * n + n <= 0x7fffffffull;
+}
 void bdpt_cpu_denoise(const bdpt_cpu_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out,
                       unsigned char* rgba_out);
 // temporal reprojection (include/bdpt.h bdpt_reproject); the caller has checked parameters and camera
@@ -62,6 +71,7 @@ bool bdpt_cpu_camera_set(const bdpt_cpu_ctx* c);
 void bdpt_cpu_read_radiance(const bdpt_cpu_ctx* c, bdpt_vec* colors, unsigned* counter);
 void bdpt_cpu_read_pixels(const bdpt_cpu_ctx* c, unsigned char* rgba);
 void bdpt_cpu_read_rand(const bdpt_cpu_ctx* c, float* t);
+void bdpt_cpu_write_rand(bdpt_cpu_ctx* c, const float* t);
 void bdpt_cpu_read_lightpaths(const bdpt_cpu_ctx* c, bdpt_lightpath* lp);
 void bdpt_cpu_write_lightpaths(bdpt_cpu_ctx* c, const bdpt_lightpath* lp);
 void bdpt_cpu_update_pixels(bdpt_cpu_ctx* c);

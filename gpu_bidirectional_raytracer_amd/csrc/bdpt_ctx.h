@@ -22,7 +22,7 @@ struct bdpt_svc_clock {
     bool ran = false;
     float cpu_ms = 0.f;                 // CPU backend: wall time of the last call
 };
-enum { kSvcAov = 0, kSvcDenoise, kSvcReproject, kSvcPreview, kSvcNoise, kSvcDenoiseNoise, kSvcCount };
+enum { kSvcAov = 0, kSvcDenoise, kSvcReproject, kSvcPreview, kSvcNoise, kSvcDenoiseNoise, kSvcChain, kSvcCount };
 
 struct bdpt_ctx {
     int device = 0;
@@ -155,6 +155,7 @@ struct bdpt_ctx {
     } jit_memo[kJitVariants];
     int last_features = 0;              // BDPT_FEAT_* of the last path-pass launch
     unsigned rand_seed = 0;             // seed of the current MT607 table (rand_ready)
+    bool rand_uploaded = false;         // the table came from bdpt_write_rand: it has no seed
     char err[512] = {0};
     // multi-device context (bdpt_create_multi): this context renders on devices[0] and owns the
     // peer contexts of the other devices; the frame is assembled on devices[0] by a sum-reduce
@@ -176,8 +177,13 @@ struct bdpt_ctx {
     float* d_aov = nullptr;
     size_t aov_cap = 0;
     int aov_traversal = 0;              // BDPT_TRAVERSE_* of the last bdpt_render_aov (0: none yet)
+    // chain buffers (bdpt_render_chain): ten output planes of chain_cap pixels each in one allocation
+    // (BDPT_CHAIN_WORDS words per pixel), made on the first call and grown when a window needs more
+    float* d_chain = nullptr;
+    size_t chain_cap = 0;
     // the frame services' clocks, by kSvc*: bdpt_render_aov (the kernel alone), bdpt_denoise,
-    // capture / bdpt_reproject, bdpt_preview_denoise, bdpt_noise_estimate, bdpt_denoise_noise
+    // capture / bdpt_reproject, bdpt_preview_denoise, bdpt_noise_estimate, bdpt_denoise_noise,
+    // bdpt_render_chain (the kernel alone)
     bdpt_svc_clock svc[kSvcCount];
     // denoiser (bdpt_denoise): guide, ping and pong records of the whole frame in one allocation
     // (3 x 16 B per pixel), made on the first call -- the frame size never changes

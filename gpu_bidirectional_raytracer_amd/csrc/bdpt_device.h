@@ -17,6 +17,9 @@
 //   d_pixels  uchar4[W*H]           gamma-2.2 8-bit RGBA (== pixels_buf)
 //   d_aov     float[12][cap]        first-hit feature buffers (bdpt_aov_kernel): planes id, t, dp,
 //             position, normal, dir of the largest window asked for; made on first use  48 B/pixel
+//   d_chain   float[18][cap]        chain buffers (bdpt_chain_kernel): planes id, first_id, kind, bounces,
+//             t, dp, position, normal, dir, throughput of the largest window asked for; made on
+//             first use                                                              72 B/pixel
 //   d_dn      float4[3][W*H]        denoiser (bdpt_denoise): guide records {normal, id or -1}, ping and
 //             pong colours; made on the first call                                  48 B/pixel
 //   d_hist    float4[4][W*H] + 20 B/pixel  reprojection (bdpt_reproject): two sets of history records
@@ -168,6 +171,36 @@ struct bdpt_aov_args {
 #define BDPT_AOV_BVH_BTH 8
 #define BDPT_AOV_ROW_BTW 64
 #define BDPT_AOV_ROW_BTH 4
+
+// The eye path up to its first non-specular vertex (bdpt_chain_kernel; include/bdpt.h
+// bdpt_render_chain): bdpt_aov_kernel's window, jitter and traversal, the glass rule, and the ten
+// output planes, packed [h][w].  key_n > 0 (the denoisers' "through" guides): the id plane holds the
+// guide key of include/bdpt.h BDPT_DENOISE_THROUGH instead -- -1 unless the chain ends DIFFUSE.
+#define BDPT_DEV_CHAIN_DIFFUSE 0
+#define BDPT_DEV_CHAIN_EMITTER 1
+#define BDPT_DEV_CHAIN_MISS 2
+#define BDPT_DEV_CHAIN_EXHAUSTED 3
+struct bdpt_chain_args {
+    int x0, y0, w, h;               // the window inside the W x H frame (checked by the host)
+    int jitter;                     // 0: both camera randoms are +0.0f
+    unsigned sid;
+    int bvh;                        // 1: walls brute force + BVH (a.bvh_*), 0: the n-sphere scan
+    int rows;                       // 1: a wave covers 64 x 1 pixels, 0: 8 x 8
+    int pass;                       // 0: glass transmits whenever it can; 1: rnd[j + 2] < P reflects
+    int key_n;                      // 0: id is the end sphere; n: id is the guide key
+    const bdpt_dev_sphere* sph;     // materials (a per-lane load at the hit sphere's index)
+    int* id;
+    int* first_id;
+    int* kind;
+    int* bounces;
+    float* t;
+    float* dp;
+    bdpt_dev_vec* position;
+    bdpt_dev_vec* normal;
+    bdpt_dev_vec* dir;
+    bdpt_dev_vec* throughput;
+};
+#define BDPT_CHAIN_WORDS 18         // words per pixel of the ten planes
 
 // Edge-avoiding wavelet denoiser (bdpt_denoise_pack_kernel / bdpt_denoise_level_kernel;
 // include/bdpt.h bdpt_denoise).  Context-owned, 48 B per pixel, made on the first call:

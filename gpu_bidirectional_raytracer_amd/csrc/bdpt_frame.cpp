@@ -18,6 +18,7 @@
 using namespace bdpt_host;
 
 extern "C" __global__ void bdpt_aov_kernel(bdpt_path_args, bdpt_aov_args);
+extern "C" __global__ void bdpt_chain_kernel(bdpt_path_args, bdpt_chain_args);
 extern "C" __global__ void bdpt_denoise_pack_kernel(const int*, const bdpt_dev_vec*, const bdpt_dev_vec*,
                                                     const bdpt_dev_sphere*, int, float4*, float4*, int);
 extern "C" const void* bdpt_denoise_level_table[2][7];   // [LDS staging][normal_power]
@@ -79,19 +80,23 @@ static int svc_last_ms(bdpt_ctx* c, int s, float* ms, const char* none) {
 // inside the feature buffers' clock, which then covers the kernel alone); the caller has checked
 // the window, the camera and the table.  *vout holds the output planes on return.  The denoiser,
 // the reprojection and the preview take their guides from these planes (aov_frame).
-static int aov_launch(bdpt_ctx* c, const bdpt_camera& cam, int x0, int y0, int w, int h, int jitter, unsigned sid,
-                      bool timed, bdpt_aov_args* vout) {
-    const size_t np = (size_t)w * (size_t)h;
-    if (np > c->aov_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));           // an earlier call's copies are done anyway
-        if (c->d_aov) HIPCHK(c, hipFree(c->d_aov));
-        c->d_aov = nullptr;
-        c->aov_cap = 0;
-        if (hipMalloc(&c->d_aov, 12 * sizeof(float) * np) != hipSuccess)
-            return fail(c, BDPT_ENOMEM, "bdpt_render_aov: output planes (%zu B)", 12 * sizeof(float) * np);
-        c->aov_cap = np;
+// A context-owned plane buffer of `words` words per pixel, grown to np pixels on demand.
+static int planes_reserve(bdpt_ctx* c, const char* who, float** buf, size_t* cap, size_t np, size_t words) {
+    if (np <= *cap) return BDPT_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));               // an earlier call's copies are done anyway
+    if (*buf) HIPCHK(c, hipFree(*buf));
+    *buf = nullptr;
+    *cap = 0;
+    if (hipMalloc(buf, words * sizeof(float) * np) != hipSuccess) {
+        *buf = nullptr;
+        return fail(c, BDPT_ENOMEM, "%s: output planes (%zu B)", who, words * sizeof(float) * np);
     }
-    bdpt_path_args a;
+    *cap = np;
+    return BDPT_OK;
+}
+// The scene, camera and traversal arguments bdpt_aov_kernel and bdpt_chain_kernel share; returns
+// whether the BVH is traversed.
+static bool ray_args(bdpt_ctx* c, const bdpt_camera& cam, bdpt_path_args& a) {
     memset(&a, 0, sizeof(a));
     a.n = (unsigned)c->spheres.size();
     a.geom = c->d_geom;
@@ -99,6 +104,14 @@ static int aov_launch(bdpt_ctx* c, const bdpt_camera& cam, int x0, int y0, int w
     camera_args(c, cam, a);
     const bool bvh = c->has_bvh && c->traversal != BDPT_TRAVERSE_BRUTE;
     if (bvh) bvh_args(c, a);
+    return bvh;
+}
+static int aov_launch(bdpt_ctx* c, const bdpt_camera& cam, int x0, int y0, int w, int h, int jitter, unsigned sid,
+                      bool timed, bdpt_aov_args* vout) {
+    const size_t np = (size_t)w * (size_t)h;
+    if (int rc = planes_reserve(c, "bdpt_render_aov", &c->d_aov, &c->aov_cap, np, 12)) return rc;
+    bdpt_path_args a;
+    const bool bvh = ray_args(c, cam, a);
     bdpt_aov_args v;
     memset(&v, 0, sizeof(v));
     v.x0 = x0; v.y0 = y0; v.w = w; v.h = h;
@@ -131,6 +144,89 @@ static int aov_launch(bdpt_ctx* c, const bdpt_camera& cam, int x0, int y0, int w
 // the unjittered first hit of the whole frame under `cam`
 static int aov_frame(bdpt_ctx* c, const bdpt_camera& cam, bdpt_aov_args* av) {
     return aov_launch(c, cam, 0, 0, c->W, c->H, 0, 0u, false, av);
+}
+
+// bdpt_chain_kernel's arguments and its launch on the context's stream, as aov_launch's.  keys ==
+// false: the ten planes of bdpt_render_chain in d_chain (`timed`: inside the chain's clock).  keys:
+// the denoisers' "through" guides of the whole frame -- the guide key and the end normal, written
+// where aov_frame leaves the first hit's id and normal (d_aov), so the pack kernels read them there.
+// Wave tile: rows for the brute scan and 8 x 8 for the BVH, as measured;
+// BDPT_CHAIN_TILE = 8 / 64 overrides it for experiments.
+static int chain_launch(bdpt_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid, int branch, bool keys,
+                        bool timed, bdpt_chain_args* vout) {
+    const size_t np = (size_t)w * (size_t)h;
+    if (keys) {
+        if (int rc = planes_reserve(c, "bdpt_denoise", &c->d_aov, &c->aov_cap, np, 12)) return rc;
+    } else {
+        if (int rc = planes_reserve(c, "bdpt_render_chain", &c->d_chain, &c->chain_cap, np, BDPT_CHAIN_WORDS)) return rc;
+    }
+    bdpt_path_args a;
+    const bool bvh = ray_args(c, c->cam, a);
+    bdpt_chain_args v;
+    memset(&v, 0, sizeof(v));
+    v.x0 = x0; v.y0 = y0; v.w = w; v.h = h;
+    v.jitter = jitter != 0;
+    v.sid = sid;
+    v.bvh = bvh;
+    v.rows = !bvh;
+    if (const char* e = getenv("BDPT_CHAIN_TILE")) {
+        if (atoi(e) == 8) v.rows = 0;
+        if (atoi(e) == 64) v.rows = 1;
+    }
+    v.pass = branch == BDPT_CHAIN_PASS;
+    v.sph = c->d_sph;
+    if (keys) {
+        v.key_n = (int)c->spheres.size();
+        v.id = (int*)c->d_aov;
+        v.normal = (bdpt_dev_vec*)(c->d_aov + 6 * c->aov_cap);
+    } else {
+        float* base = c->d_chain;
+        const size_t cap = c->chain_cap;
+        v.id = (int*)base;
+        v.first_id = (int*)(base + cap);
+        v.kind = (int*)(base + 2 * cap);
+        v.bounces = (int*)(base + 3 * cap);
+        v.t = base + 4 * cap;
+        v.dp = base + 5 * cap;
+        v.position = (bdpt_dev_vec*)(base + 6 * cap);
+        v.normal = (bdpt_dev_vec*)(base + 9 * cap);
+        v.dir = (bdpt_dev_vec*)(base + 12 * cap);
+        v.throughput = (bdpt_dev_vec*)(base + 15 * cap);
+    }
+    const dim3 grid = v.rows ? tile_grid(w, h, BDPT_AOV_ROW_BTW, BDPT_AOV_ROW_BTH)
+                             : tile_grid(w, h, BDPT_AOV_BVH_BTW, BDPT_AOV_BVH_BTH);
+    if (timed)
+        if (int rc = svc_begin(c, kSvcChain)) return rc;
+    hipLaunchKernelGGL(bdpt_chain_kernel, grid, dim3(256), 0, c->stream, a, v);
+    HIPCHK(c, hipGetLastError());
+    if (timed)
+        if (int rc = svc_end(c, kSvcChain)) return rc;
+    *vout = v;
+    return BDPT_OK;
+}
+// The denoisers' guide planes of the whole frame, by `materials`: the unjittered first hit, or
+// (BDPT_DENOISE_THROUGH) the key and end normal of the unjittered TRANSMIT chain.  *all: what the
+// pack kernels' all_materials is -- a key is an eligible guide as it stands.
+static int guide_frame(bdpt_ctx* c, int materials, const int** id, const bdpt_dev_vec** normal, int* all) {
+    if (materials == BDPT_DENOISE_THROUGH) {
+        bdpt_chain_args cv;
+        if (int rc = chain_launch(c, 0, 0, c->W, c->H, 0, 0u, BDPT_CHAIN_TRANSMIT, true, false, &cv)) return rc;
+        *id = cv.id; *normal = cv.normal; *all = 1;
+        return BDPT_OK;
+    }
+    bdpt_aov_args av;
+    if (int rc = aov_frame(c, c->cam, &av)) return rc;
+    *id = av.id; *normal = av.normal; *all = materials == BDPT_DENOISE_ALL;
+    return BDPT_OK;
+}
+// bdpt_denoise / bdpt_denoise_noise: the `materials` values they take; "through" keys must fit an int
+static int materials_check(bdpt_ctx* c, const char* who, int materials) {
+    if (materials != BDPT_DENOISE_DIFFUSE && materials != BDPT_DENOISE_ALL && materials != BDPT_DENOISE_THROUGH)
+        return fail(c, BDPT_EINVAL, "%s: materials %d", who, materials);
+    if (materials == BDPT_DENOISE_THROUGH && !bdpt_chain_keys_fit((unsigned)c->spheres.size()))
+        return fail(c, BDPT_EINVAL, "%s: %zu spheres are too many for the guide keys of materials = through", who,
+                    c->spheres.size());
+    return BDPT_OK;
 }
 
 // The packed results of a call, on the device: what the last kernel writes and the read-back
@@ -272,9 +368,57 @@ int bdpt_last_aov_ms(bdpt_ctx* c, float* ms) {
     return svc_last_ms(c, kSvcAov, ms, "bdpt_last_aov_ms: no feature buffers rendered");
 }
 
+// ---- the eye path up to its first non-specular vertex (include/bdpt.h bdpt_render_chain;
+// DESIGN.md 4j) -----------------------------------------------------------------------------
+// bdpt_render_aov's sequence with bdpt_chain_kernel and its ten planes in d_chain.
+int bdpt_render_chain(bdpt_ctx* c, int x0, int y0, int w, int h, int jitter, unsigned sid, int branch,
+                      const bdpt_chain_buffers* out) {
+    if (!c) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_render_chain: multi-device contexts render no feature buffers");
+    if (!out) return fail(c, BDPT_EINVAL, "bdpt_render_chain: no output buffers");
+    if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 > c->W - w || y0 > c->H - h)
+        return fail(c, BDPT_EINVAL, "bdpt_render_chain: window %d,%d %dx%d is empty or outside the %dx%d frame", x0,
+                    y0, w, h, c->W, c->H);
+    if (sid >= (unsigned)BDPT_RAND_N) return fail(c, BDPT_EINVAL, "bdpt_render_chain: sid %u >= RAND_N", sid);
+    if (branch != BDPT_CHAIN_TRANSMIT && branch != BDPT_CHAIN_PASS)
+        return fail(c, BDPT_EINVAL, "bdpt_render_chain: branch %d", branch);
+    if (branch == BDPT_CHAIN_PASS && !jitter)
+        return fail(c, BDPT_EINVAL, "bdpt_render_chain: BDPT_CHAIN_PASS is the choice of a pass: it needs jitter");
+    if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_render_chain: camera not set");
+    if (jitter && !c->rand_ready)
+        return fail(c, BDPT_ESTATE, "bdpt_render_chain: jitter needs a random table (run the light pass first)");
+    if (c->cpu) {
+        svc_cpu(c, kSvcChain, [&] { bdpt_cpu_render_chain(c->cpu, x0, y0, w, h, jitter, sid, branch, out); });
+        return BDPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t np = (size_t)w * (size_t)h;
+    bdpt_chain_args v;
+    if (int rc = chain_launch(c, x0, y0, w, h, jitter, sid, branch, false, true, &v)) return rc;
+    auto back = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIPCHK(c, back(out->id, v.id, sizeof(int) * np));
+    HIPCHK(c, back(out->first_id, v.first_id, sizeof(int) * np));
+    HIPCHK(c, back(out->kind, v.kind, sizeof(int) * np));
+    HIPCHK(c, back(out->bounces, v.bounces, sizeof(int) * np));
+    HIPCHK(c, back(out->t, v.t, sizeof(float) * np));
+    HIPCHK(c, back(out->dp, v.dp, sizeof(float) * np));
+    HIPCHK(c, back(out->position, v.position, sizeof(bdpt_vec) * np));
+    HIPCHK(c, back(out->normal, v.normal, sizeof(bdpt_vec) * np));
+    HIPCHK(c, back(out->dir, v.dir, sizeof(bdpt_vec) * np));
+    HIPCHK(c, back(out->throughput, v.throughput, sizeof(bdpt_vec) * np));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BDPT_OK;
+}
+
+int bdpt_last_chain_ms(bdpt_ctx* c, float* ms) {
+    return svc_last_ms(c, kSvcChain, ms, "bdpt_last_chain_ms: no chain rendered");
+}
+
 // ---- edge-avoiding wavelet denoiser (include/bdpt.h bdpt_denoise) --------------
-// The unjittered whole-frame bdpt_aov_kernel, bdpt_denoise_pack_kernel (guide records + the first
-// ping buffer), the levels, then the read-back.  The packed results go where the feature planes
+// The guides (the unjittered whole-frame bdpt_aov_kernel, or bdpt_chain_kernel's keys for
+// materials = through), bdpt_denoise_pack_kernel (guide records + the first ping buffer), the levels, then the read-back.  The packed results go where the feature planes
 // were: the pack kernel has consumed them, and 16 B of a pixel's 48 B there hold its float3 and
 // its RGBA.  Only d_aov and d_dn are written.
 int bdpt_denoise(bdpt_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out, unsigned char* rgba_out) {
@@ -283,8 +427,7 @@ int bdpt_denoise(bdpt_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out
     if (!p) return fail(c, BDPT_EINVAL, "bdpt_denoise: no parameters");
     if (!colors_out && !rgba_out) return fail(c, BDPT_EINVAL, "bdpt_denoise: no output buffer");
     if (int rc = filter_check(c, "bdpt_denoise", p->levels, 1, p->normal_power, p->sigma_color)) return rc;
-    if (p->materials != BDPT_DENOISE_DIFFUSE && p->materials != BDPT_DENOISE_ALL)
-        return fail(c, BDPT_EINVAL, "bdpt_denoise: materials %d", p->materials);
+    if (int rc = materials_check(c, "bdpt_denoise", p->materials)) return rc;
     if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_denoise: camera not set");
     if (c->cpu) {
         svc_cpu(c, kSvcDenoise, [&] { bdpt_cpu_denoise(c->cpu, p, colors_out, rgba_out); });
@@ -296,11 +439,12 @@ int bdpt_denoise(bdpt_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out
     if (int rc = dn_alloc(c, "bdpt_denoise", &d)) return rc;
     if (int rc = join_fold(c)) return rc;
     if (int rc = svc_begin(c, kSvcDenoise)) return rc;
-    bdpt_aov_args av;
-    if (int rc = aov_frame(c, c->cam, &av)) return rc;
-    hipLaunchKernelGGL(bdpt_denoise_pack_kernel, lane_grid(np), dim3(256), 0, c->stream, (const int*)av.id,
-                       (const bdpt_dev_vec*)av.normal, (const bdpt_dev_vec*)c->d_colors, (const bdpt_dev_sphere*)c->d_sph,
-                       (int)(p->materials == BDPT_DENOISE_ALL), d.guide, d.ping, (int)np);
+    const int* gid;
+    const bdpt_dev_vec* gnormal;
+    int all;
+    if (int rc = guide_frame(c, p->materials, &gid, &gnormal, &all)) return rc;
+    hipLaunchKernelGGL(bdpt_denoise_pack_kernel, lane_grid(np), dim3(256), 0, c->stream, gid, gnormal,
+                       (const bdpt_dev_vec*)c->d_colors, (const bdpt_dev_sphere*)c->d_sph, all, d.guide, d.ping, (int)np);
     HIPCHK(c, hipGetLastError());
     // 3 of a pixel's 12 words in d_aov, and the 4th
     const frame_outs want = wanted({(bdpt_dev_vec*)c->d_aov, nullptr, (uchar4*)(c->d_aov + 3 * c->aov_cap)}, colors_out,
@@ -331,8 +475,7 @@ int bdpt_denoise_noise(bdpt_ctx* c, const bdpt_denoise_noise_params* p, bdpt_vec
     if (!p) return fail(c, BDPT_EINVAL, "bdpt_denoise_noise: no parameters");
     if (!colors_out && !rgba_out) return fail(c, BDPT_EINVAL, "bdpt_denoise_noise: no output buffer");
     if (int rc = filter_check(c, "bdpt_denoise_noise", p->levels, 1, p->normal_power, p->sigma_color)) return rc;
-    if (p->materials != BDPT_DENOISE_DIFFUSE && p->materials != BDPT_DENOISE_ALL)
-        return fail(c, BDPT_EINVAL, "bdpt_denoise_noise: materials %d", p->materials);
+    if (int rc = materials_check(c, "bdpt_denoise_noise", p->materials)) return rc;
     if (!(p->noise_sigma > 0.f && p->noise_sigma < INFINITY))
         return fail(c, BDPT_EINVAL, "bdpt_denoise_noise: noise_sigma must be > 0 and finite");
     if (!c->cam_set) return fail(c, BDPT_ESTATE, "bdpt_denoise_noise: camera not set");
@@ -346,12 +489,14 @@ int bdpt_denoise_noise(bdpt_ctx* c, const bdpt_denoise_noise_params* p, bdpt_vec
     if (int rc = dn_alloc(c, "bdpt_denoise_noise", &d)) return rc;
     if (int rc = join_fold(c)) return rc;
     if (int rc = svc_begin(c, kSvcDenoiseNoise)) return rc;
-    bdpt_aov_args av;
-    if (int rc = aov_frame(c, c->cam, &av)) return rc;
-    hipLaunchKernelGGL(bdpt_dnoise_pack_kernel, lane_grid(np), dim3(256), 0, c->stream, (const int*)av.id,
-                       (const bdpt_dev_vec*)av.normal, (const bdpt_dev_vec*)c->d_colors, (const unsigned*)c->d_counter,
-                       (const uint4*)c->d_mark, (int)c->mark_live, (const bdpt_dev_sphere*)c->d_sph,
-                       (int)(p->materials == BDPT_DENOISE_ALL), d.guide, d.ping, (int)np);
+    const int* gid;
+    const bdpt_dev_vec* gnormal;
+    int all;
+    if (int rc = guide_frame(c, p->materials, &gid, &gnormal, &all)) return rc;
+    hipLaunchKernelGGL(bdpt_dnoise_pack_kernel, lane_grid(np), dim3(256), 0, c->stream, gid, gnormal,
+                       (const bdpt_dev_vec*)c->d_colors, (const unsigned*)c->d_counter,
+                       (const uint4*)c->d_mark, (int)c->mark_live, (const bdpt_dev_sphere*)c->d_sph, all, d.guide,
+                       d.ping, (int)np);
     HIPCHK(c, hipGetLastError());
     // (experiments: BDPT_DNOISE_PREFILTER=0 leaves the prefilter out -- the levels then read the raw
     // variances, which is not the definition -- so that scripts/denoise_noise_time.py can time its share)

@@ -165,7 +165,7 @@ static void release(bdpt_ctx* c) {
     void* bufs[] = {c->d_params, c->d_rand, c->d_rndp, c->d_scp, c->d_srec, c->d_lp, c->d_sph, c->d_lights, c->d_geom, c->d_lightrec, c->d_colors,
                     c->d_counter, c->d_pixels, c->d_thr, c->d_rbuf, c->d_rmask, c->d_poolctr, c->d_uflags, c->d_uerr, c->d_bvh_nodes,
                     c->d_bvh_geom, c->d_big_geom, c->d_mat, c->d_bvh_ids, c->d_big_ids,
-                    c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc, c->d_aov, c->d_dn, c->d_hist,
+                    c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc, c->d_aov, c->d_chain, c->d_dn, c->d_hist,
                     c->d_mark, c->d_noise, c->d_tiles};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -530,6 +530,7 @@ static int one_generate_rand(bdpt_ctx* c, unsigned seed) {
         bdpt_cpu_generate_rand(c->cpu, seed);
         c->rand_ready = true;
         c->rand_seed = seed;
+    c->rand_uploaded = false;
         return BDPT_OK;
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -548,6 +549,7 @@ static int one_generate_rand(bdpt_ctx* c, unsigned seed) {
     c->rand_ready = true;
     c->scp_ready = c->srec_ready = false;              // rebuilt by the next launch that reads them
     c->rand_seed = seed;
+    c->rand_uploaded = false;
     return BDPT_OK;
 }
 
@@ -589,6 +591,7 @@ static int one_light_pass(bdpt_ctx* c, int current_sample) {
         bdpt_cpu_light_pass(c->cpu, current_sample);
         c->rand_ready = true;
         c->rand_seed = (unsigned)(current_sample * 5);
+        c->rand_uploaded = false;
         return BDPT_OK;
     }
     // The reference regenerates the table per light with the same seed (smallpt_cpu.c:321-322):
@@ -1248,6 +1251,29 @@ int bdpt_read_rand(bdpt_ctx* c, float* t) {
     return BDPT_OK;
 }
 
+// The counterpart of bdpt_read_rand: the table from the host, and what one_generate_rand does after
+// the generator (the planar copy; the derived tables are rebuilt on their next use).
+int bdpt_write_rand(bdpt_ctx* c, const float* t) {
+    if (!c || !t) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_write_rand: multi-device contexts generate their tables");
+    if (c->cpu) {
+        bdpt_cpu_write_rand(c->cpu, t);
+    } else {
+        HIPCHK(c, hipSetDevice(c->device));
+        if (int rc = join_fold(c)) return rc;              // path kernels read the table
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_rand, t, sizeof(float) * BDPT_RAND_N, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(bdpt_rand_planar_kernel, dim3((BDPT_DEV_RANDP_PLANES * BDPT_DEV_RANDP_PL + 255) / 256),
+                           dim3(256), 0, c->stream, (const float*)c->d_rand, c->d_rndp);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->scp_ready = c->srec_ready = false;
+    }
+    c->rand_ready = true;
+    c->rand_uploaded = true;
+    return BDPT_OK;
+}
+
 int bdpt_read_sample_records(bdpt_ctx* c, float* rec) {
     if (!c || !rec) return BDPT_EINVAL;
     if (c->cpu) return fail(c, BDPT_EINVAL, "bdpt_read_sample_records: the CPU backend has no sample records");
@@ -1296,7 +1322,7 @@ static int one_write_lightpaths(bdpt_ctx* c, const bdpt_lightpath* lp) {
 
 int bdpt_rand_seed(const bdpt_ctx* c, unsigned* seed) {
     if (!c || !seed) return BDPT_EINVAL;
-    if (!c->rand_ready) return BDPT_ESTATE;
+    if (!c->rand_ready || c->rand_uploaded) return BDPT_ESTATE;
     *seed = c->rand_seed;
     return BDPT_OK;
 }

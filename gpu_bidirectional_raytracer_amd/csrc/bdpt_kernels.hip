@@ -1961,5 +1961,191 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_aov_kernel(bdpt_path_args
     v.dir[o] = ov;
 }
 
+// bdpt_aov_kernel's ray and closest hit as functions, for bdpt_chain_kernel's loop: the same operations
+// in the same order (the first-hit kernel above keeps its own text: its code is the measured one).
+namespace {
+// The camera ray (:562-600) of frame pixel (x, y), as the `fresh` branch of the path kernel forms
+// it; u0, u1 are the jitter randoms (+0: the unjittered ray).
+__device__ __forceinline__ void frame_camera_ray(const bdpt_path_args& a, int x, int y, float u0, float u1, f3& ro,
+                                                 f3& rd) {
+    const float kx = (float)(((double)((float)x * a.inv_w) - a.half_w) + (double)(u0 * a.inv_w));
+    const float ky = (float)(((double)((float)y * a.inv_h) - a.half_h) + (double)(u1 * a.inv_h));
+    f3 rdir = mk(0.f, 0.f, 0.f);
+    rdir = add(rdir, smul(kx, mk(a.ux[0], a.ux[1], a.ux[2])));
+    rdir = add(rdir, smul(ky, mk(a.uy[0], a.uy[1], a.uy[2])));
+    rdir = add(rdir, mk(10.0f * a.ud[0], 10.0f * a.ud[1], 10.0f * a.ud[2]));     // kz * ud
+    const float w = (a.tx * kx + a.ty * ky + a.tz * 10.0f) + 1;
+    rdir = smul(rcp_rn(w), rdir);
+    ro = add(rdir, mk(a.orig[0], a.orig[1], a.orig[2]));
+    rd = norm(rdir);
+}
+// The closest hit of a ray, scanning from the last sphere down (:106-124): t = 1e20f, id = -1 on a miss.
+__device__ __forceinline__ void frame_closest(const bdpt_path_args& a, int bvh, f3 ro, f3 rd, float& t, int& id) {
+    t = 1e20f;
+    id = -1;
+    if (bvh) {
+        // walls by brute force, then the BVH; equal distances go to the higher index, which is
+        // what the reference's downward scan with `d < t` yields
+        for (int q = a.big_n - 1; q >= 0; --q) {
+            const troots h = sphere_roots(ld_const(a.big_geom, q), ro, rd);
+            const float d = h.t1 > kEps ? h.t1 : h.t2;
+            const int s = a.big_ids[q] & kBvhIdMask;
+            if (h.t2 > kEps && (d < t || (d == t && s > id))) { t = d; id = s; }
+        }
+        const bvh_ray br = bvh_setup(a, ro, rd);
+        int node = 0;
+        while (true) {                                   // while-while, as in the path kernel
+            int info = -1;
+            while (node < a.bvh_nn) {
+                const float4 lo = a.bvh_nodes[2 * node], hi = a.bvh_nodes[2 * node + 1];
+                const int inf = __float_as_int(hi.w);
+                const bool in = bvh_box(lo, hi, br, t);
+                node = (in && inf < 0) ? node + 1 : __float_as_int(lo.w);
+                if (in && inf >= 0) { info = inf; break; }
+            }
+            if (info < 0) break;
+            const int first = info & 0xffffff, end = first + (info >> 24);
+            for (int k = first; k < end; k++) {
+                const troots h = sphere_roots(a.bvh_geom[k], ro, rd);
+                const float d = h.t1 > kEps ? h.t1 : h.t2;
+                const int s = a.bvh_ids[k] & kBvhIdMask;
+                if (h.t2 > kEps && (d < t || (d == t && s > id))) { t = d; id = s; }
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int s = (int)a.n - 1; s >= 0; --s) {
+            const troots q = sphere_roots(ld_const(a.geom, s), ro, rd);
+            const float r = q.t1 > kEps ? q.t1 : q.t2;
+            if (q.t2 > kEps && r < t) { t = r; id = s; }
+        }
+    }
+}
+__device__ __forceinline__ bdpt_dev_vec dev_vec(f3 v) {
+    bdpt_dev_vec o;
+    o.x = v.x; o.y = v.y; o.z = v.z;
+    return o;
+}
+}  // namespace
+
+// The eye path up to its first non-specular vertex (include/bdpt.h bdpt_render_chain; no reference
+// counterpart): bdpt_aov_kernel's ray and hit, then the integrator's mirror and glass branches
+// (device.cu:621-771) with the float operations of bdpt_path_kernel_t in its order, until a diffuse
+// surface, an emitter or a miss ends the chain, or the 7th segment does.  One lane per pixel of the
+// window; nothing but the ten output planes is written; no LDS, no cross-lane operation.
+//  * The loop is divergent: a lane leaves it where its chain ends (most at depth 0) and the wave
+//    goes on while any lane follows a mirror.  The scan indices stay wave-uniform among the lanes
+//    still in the loop, so the scene is read with scalar loads as in bdpt_aov_kernel; the hit
+//    sphere's material is one per-lane 48-B record (v.sph).
+//  * Wave tiles as bdpt_aov_kernel's, chosen by the host (v.rows).
+extern "C" __global__ __launch_bounds__(256) void bdpt_chain_kernel(bdpt_path_args a, bdpt_chain_args v) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lx = v.rows ? (int)blockIdx.x * BDPT_AOV_ROW_BTW + lane
+                          : (int)blockIdx.x * BDPT_AOV_BVH_BTW + wave * 8 + (lane & 7);
+    const int ly = v.rows ? (int)blockIdx.y * BDPT_AOV_ROW_BTH + wave
+                          : (int)blockIdx.y * BDPT_AOV_BVH_BTH + (lane >> 3);
+    if (lx >= v.w || ly >= v.h) return;                  // (no cross-lane operation below)
+    const int x = v.x0 + lx, y = v.y0 + ly;
+    const unsigned base = 26u + (unsigned)(y * a.W + x) * 25u;
+    float u0 = 0.f, u1 = 0.f;
+    if (v.jitter) {
+        const unsigned kk = (base + v.sid) % (kRandN - 5u);
+        u0 = a.rnd[kk];
+        u1 = a.rnd[kk + 1];
+    }
+    f3 ro, rd;
+    frame_camera_ray(a, x, y, u0, u1, ro, rd);
+
+    f3 thr = mk(1.f, 1.f, 1.f), hit = mk(0.f, 0.f, 0.f), normal = hit;
+    float len = 0.f, dp = 0.f;
+    int id = -1, first_id = -1, bounces = 0, kind = BDPT_DEV_CHAIN_EXHAUSTED;
+    for (unsigned depth = 0; depth <= 6u; ++depth) {
+        float t;
+        int s;
+        frame_closest(a, v.bvh, ro, rd, t, s);
+        if (depth == 0u) first_id = s;
+        if (s < 0) {
+            kind = BDPT_DEV_CHAIN_MISS;
+            break;
+        }
+        const bdpt_dev_sphere S = v.sph[s];
+        len = len + t;
+        hit = add(ro, smul(t, rd));                      // :635-637
+        normal = norm(sub(hit, mk(S.px, S.py, S.pz)));   // :639-641
+        dp = dot(normal, rd);                            // :643
+        if (!(S.ex == 0.f && S.ey == 0.f && S.ez == 0.f)) {   // :651, before the material
+            kind = BDPT_DEV_CHAIN_EMITTER;
+            id = s;
+            break;
+        }
+        if (S.refl == BDPT_DEV_DIFF) {
+            kind = BDPT_DEV_CHAIN_DIFFUSE;
+            id = s;
+            break;
+        }
+        bounces++;
+        const f3 cc = mk(S.cx, S.cy, S.cz);
+        const f3 refl = sub(rd, smul(2.f * dot(normal, rd), normal));
+        ro = hit;
+        if (S.refl == BDPT_DEV_SPEC) {                   // :704-714
+            thr = mul(thr, cc);
+            rd = refl;
+            continue;
+        }
+        // REFR / LITE (:715-770)
+        const f3 nl = dp > 0 ? mk(-normal.x, -normal.y, -normal.z) : normal;   // (-1*sign(dp))*n, exact
+        const float nc = 1.f, nt = 1.5f;
+        const bool into = dot(normal, nl) > 0;
+        const float nnt = into ? nc / nt : nt / nc;
+        const float ddn = dot(rd, nl);
+        const float cos2t = 1.f - nnt * nnt * (1.f - ddn * ddn);
+        if (cos2t < 0.f) {                               // total internal reflection
+            thr = mul(thr, cc);
+            rd = refl;
+            continue;
+        }
+        // cos2t = 1 - X is 0 or >= 2^-24: the core root is exact, as in the path kernel
+        const float kq = (float)(into ? 1 : -1) * (ddn * nnt + bdpt_sqrt_rn_core(cos2t));
+        const f3 td = norm(sub(smul(nnt, rd), smul(kq, normal)));
+        const float aa = nt - nc, bb = nt + nc;
+        const float R0 = aa * aa / (bb * bb);
+        const float c = 1 - (into ? -ddn : dot(td, normal));
+        const float Re = R0 + (1 - R0) * c * c * c * c * c;
+        const float Tr = 1.f - Re;
+        const float Pp = .25f + .5f * Re;
+        bool reflect = false;
+        if (v.pass) reflect = a.rnd[(base + depth * 5u + v.sid) % (kRandN - 5u) + 2u] < Pp;
+        const float k = div_rn_normal(reflect ? Re : Tr, reflect ? Pp : 1.f - Pp);
+        thr = mul(smul(k, thr), cc);
+        rd = reflect ? refl : td;
+    }
+    if (kind >= BDPT_DEV_CHAIN_MISS) {                   // MISS, EXHAUSTED: no end vertex
+        hit = mk(0.f, 0.f, 0.f);
+        normal = hit;
+        dp = 0.f;
+    }
+    const size_t o = (size_t)ly * (size_t)v.w + (size_t)lx;
+    if (v.key_n > 0) {
+        // the denoisers' guide key (include/bdpt.h BDPT_DENOISE_THROUGH); the host has checked that
+        // 6 n^2 + n fits an int
+        int key = -1;
+        if (kind == BDPT_DEV_CHAIN_DIFFUSE)
+            key = bounces == 0 ? id : v.key_n + ((bounces - 1) * v.key_n + first_id) * v.key_n + id;
+        v.id[o] = key;
+        v.normal[o] = dev_vec(normal);
+        return;
+    }
+    v.id[o] = id;
+    v.first_id[o] = first_id;
+    v.kind[o] = kind;
+    v.bounces[o] = bounces;
+    v.t[o] = len;
+    v.dp[o] = dp;
+    v.position[o] = dev_vec(hit);
+    v.normal[o] = dev_vec(normal);
+    v.dir[o] = dev_vec(rd);
+    v.throughput[o] = dev_vec(thr);
+}
+
 #include "bdpt_frame_kernels.h"    // the frame services' kernels (denoiser, reprojection, preview, noise)
 #endif  // BDPT_JIT, BDPT_TILES

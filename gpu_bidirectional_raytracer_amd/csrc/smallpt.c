@@ -24,7 +24,9 @@
  * the first light pass, so a run continues exactly where the saved one stopped.
  * --denoise writes --out from the denoised frame (bdpt_denoise: 4 levels, sigma 0.5, diffuse
  * surfaces only, unless --denoise-levels / --denoise-sigma / --denoise-all say otherwise) instead
- * of the raw pixels; one device (or the CPU, --device -1) only.
+ * of the raw pixels; one device (or the CPU, --device -1) only.  --denoise-through instead of
+ * --denoise-all guides the filter through mirrors and glass (BDPT_DENOISE_THROUGH: --denoise and
+ * --denoise-noise; not with --reproject, whose calls refuse it).
  * --reproject keeps the last view's frame across camera keys: every camera key of --keys captures
  * the frame before re-initialising (bdpt_history_capture), a sphere key clears the history, and
  * --out is written from the preview's pixels (bdpt_reproject: history weight capped at
@@ -99,6 +101,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[a], "--denoise-levels") && a + 1 < argc) dn.levels = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--denoise-sigma") && a + 1 < argc) dn.sigma_color = strtof(argv[++a], NULL);
         else if (!strcmp(argv[a], "--denoise-all")) dn.materials = BDPT_DENOISE_ALL;
+        else if (!strcmp(argv[a], "--denoise-through")) dn.materials = BDPT_DENOISE_THROUGH;
         else if (!strcmp(argv[a], "--denoise-count") && a + 1 < argc) count_ref = strtof(argv[++a], NULL);
         else if (!strcmp(argv[a], "--reproject")) h.reuse_history = 1;
         else if (!strcmp(argv[a], "--reproject-history") && a + 1 < argc) h.rp.max_history = strtof(argv[++a], NULL);

@@ -265,6 +265,11 @@ int  bdpt_device_timing(bdpt_ctx *ctx, int k, int *device, double *kernel_ms, do
 int  bdpt_read_radiance(bdpt_ctx *ctx, bdpt_vec *colors, unsigned *counter);
 int  bdpt_read_pixels(bdpt_ctx *ctx, unsigned char *rgba);
 int  bdpt_read_rand(bdpt_ctx *ctx, float *rand_table);          /* d_Rand, BDPT_RAND_N */
+/* Upload all BDPT_RAND_N entries of d_Rand (the counterpart of bdpt_read_rand; no reference
+ * counterpart): tests render on tables no seed produces -- all zeros, one constant.  Ordered after
+ * what is queued.  Such a table has no seed: until a table is generated again bdpt_rand_seed answers
+ * BDPT_ESTATE, and a checkpoint saved meanwhile holds no table.  One-device contexts only. */
+int  bdpt_write_rand(bdpt_ctx *ctx, const float *rand_table);
 int  bdpt_read_lightpaths(bdpt_ctx *ctx, bdpt_lightpath *lp);   /* dev_lp, 4096        */
 /* The sample records of the current table (BDPT_FEAT_SREC), built first if they are not current:
  * 8 floats per table position j < BDPT_RAND_N - 5, {A, B, C, u2, X, Y, Z, u0} of d_Rand[j..j+4]
@@ -324,6 +329,65 @@ int  bdpt_pick(bdpt_ctx *ctx, int x, int y, int jitter, unsigned sid, int *id, f
 int  bdpt_last_aov_traversal(const bdpt_ctx *ctx);
 int  bdpt_last_aov_ms(bdpt_ctx *ctx, float *ms);
 
+/* ---- chain buffers: the eye path up to its first non-specular vertex (no reference counterpart;
+ * DESIGN.md 4j) ----
+ * What a pixel shows through mirrors and glass: the integrator follows a mirror deterministically and
+ * glass by one random number, and stops being a chain at the first diffuse surface, emitter or miss
+ * (device.cu:621-771).  Window, `jitter`, `sid`, traversal, outputs packed [h][w], NULL = not wanted,
+ * "synchronous, ordered after what is queued, no side effects": all as bdpt_render_aov.  fp32, no
+ * contraction, correctly rounded sqrt and divide, denormals kept, in the order written; vnorm(v) =
+ * (1.f / sqrtf((v.x*v.x + v.y*v.y) + v.z*v.z)) * v; the GPU, the CPU backend and the tests' numpy
+ * statement form the same bits.
+ *   ray     bdpt_render_aov's: o, d.  thr = (1, 1, 1), len = +0, bounces = 0.
+ *   loop    depth = 0 .. 6 (:621), j = (26 + 25*i + 5*depth + sid) % (RAND_N-5) (:619, 32-bit unsigned).
+ *     hit     as bdpt_render_aov's (IntersectDevice :106-124); depth 0's sphere index is first_id
+ *             (-1 on a miss).  A miss: kind = MISS, stop.
+ *     vertex  len = len + t;  P = o + t*d (:635-637);  N = vnorm(P - p[s]) (:639-641);
+ *             dp = vdot(N, d) (:643);  nl = dp > 0 ? -N : N (:645-647).
+ *     stop    e[s] not all zero: kind = EMITTER, id = s, stop (:651, before the material).
+ *             refl[s] == DIFF: kind = DIFFUSE, id = s, stop (:663).
+ *     mirror  otherwise bounces += 1, R = d - (2.f * vdot(N, d)) * N, o = P.
+ *             refl[s] == SPEC (:704-714): thr = thr * c[s], d = R, next depth.
+ *     glass   any other refl (:715-770): into = vdot(N, nl) > 0;  nnt = into ? 1.f/1.5f : 1.5f/1.f;
+ *             ddn = vdot(d, nl);  cos2t = 1.f - nnt*nnt*(1.f - ddn*ddn).
+ *             cos2t < 0 (total internal reflection): thr = thr * c[s], d = R, next depth.
+ *             td = vnorm(nnt*d - ((into ? 1.f : -1.f) * (ddn*nnt + sqrtf(cos2t))) * N);
+ *             R0 = (0.5f*0.5f) / (2.5f*2.5f);  cc = 1 - (into ? -ddn : vdot(td, N));
+ *             Re = R0 + (1 - R0)*cc*cc*cc*cc*cc (left to right);  Tr = 1.f - Re;  P = .25f + .5f*Re;
+ *             RP = Re / P;  TP = Tr / (1.f - P).
+ *             BDPT_CHAIN_TRANSMIT: thr = (TP * thr) * c[s], d = td.
+ *             BDPT_CHAIN_PASS: d_Rand[j+2] < P ? (thr = (RP * thr) * c[s], d = R)
+ *                                              : (thr = (TP * thr) * c[s], d = td)  -- what pass `sid` does.
+ *     Leaving the loop after depth 6: kind = EXHAUSTED.
+ *   id        the end sphere (DIFFUSE, EMITTER), -1 for MISS and EXHAUSTED
+ *   first_id  bdpt_render_aov's id
+ *   kind      BDPT_CHAIN_KIND_*
+ *   bounces   mirror and glass vertices passed, 0..7
+ *   t         len: the summed distances of the segments that hit
+ *   dp, position, normal   of the end vertex (dp signed, the normal not flipped); +0.0f for MISS and
+ *             EXHAUSTED
+ *   dir       d when the loop is left: the direction of the segment that reached the end vertex or
+ *             missed; for EXHAUSTED the direction the 7th vertex sends the path on in
+ *   throughput  thr
+ * Where bounces == 0 the six planes shared with bdpt_render_aov equal its planes.  With probe emitters
+ * on the non-specular spheres and a zero light-path table, one path pass returns, per channel,
+ * throughput * (fabsf(dp) * e[id]) of the BDPT_CHAIN_PASS chain: the pin the tests hold it to.
+ * BDPT_EINVAL: an unknown `branch`, BDPT_CHAIN_PASS with jitter == 0 (the choice is a pass's), and
+ * what bdpt_render_aov refuses, the multi-device context included.  BDPT_ESTATE as bdpt_render_aov.
+ * bdpt_last_chain_ms: the device time of the last call's kernel alone (HIP events around the launch;
+ * wall time of the loop on the CPU backend), BDPT_ESTATE before the first call. */
+#define BDPT_CHAIN_TRANSMIT 0   /* glass: refract whenever refraction exists (no table needed) */
+#define BDPT_CHAIN_PASS     1   /* glass: the choice pass `sid` makes, rnd[j+2] < P (needs jitter != 0) */
+#define BDPT_CHAIN_KIND_DIFFUSE   0
+#define BDPT_CHAIN_KIND_EMITTER   1
+#define BDPT_CHAIN_KIND_MISS      2
+#define BDPT_CHAIN_KIND_EXHAUSTED 3
+typedef struct { int *id, *first_id, *kind, *bounces; float *t, *dp;
+                 bdpt_vec *position, *normal, *dir, *throughput; } bdpt_chain_buffers;
+int  bdpt_render_chain(bdpt_ctx *ctx, int x0, int y0, int w, int h, int jitter, unsigned sid,
+                       int branch, const bdpt_chain_buffers *out);
+int  bdpt_last_chain_ms(bdpt_ctx *ctx, float *ms);
+
 /* ---- edge-avoiding wavelet denoiser guided by the first-hit buffers (no reference counterpart:
  * the reference shows and saves only the raw running mean, smallpt_cpu.c:239-262) ----
  * An a-trous filter over the context's accumulated radiance (what bdpt_read_radiance returns) as
@@ -345,6 +409,15 @@ int  bdpt_last_aov_ms(bdpt_ctx *ctx, float *ms);
  *                sw = sw + w;  sc = sc + w*cur[q]
  *              and out = sc * (1/sw) (both divisions correctly rounded).  Level k+1 reads level k.
  *              Denormal intermediates are kept, not flushed; non-finite radiance is not special.
+ *   through    BDPT_DENOISE_THROUGH (bdpt_denoise and bdpt_denoise_noise only): the guides come from
+ *              bdpt_render_chain with jitter = 0, BDPT_CHAIN_TRANSMIT, whole frame, instead of the
+ *              first hit.  A pixel is eligible iff kind == DIFFUSE; its guide normal is the end
+ *              normal; its guide integer -- what "id" means in the level (and in bdpt_denoise_noise's
+ *              prefilter) -- is the key: id where bounces == 0, otherwise
+ *              n + ((bounces-1)*n + first_id)*n + id with n the sphere count, so two pixels match when
+ *              they show the same sphere through the same first sphere in as many bounces.  Nothing
+ *              else of the filter changes.  A scene with 6 n*n + n > 2^31 - 1 is BDPT_EINVAL for this
+ *              value only.  bdpt_reproject, bdpt_history_capture and bdpt_preview_denoise refuse it.
  *   levels 1..8, normal_power 0..6, sigma_color > 0 (+inf: no colour stopping).
  * colors_out: W*H denoised colours; rgba_out: 4*W*H bytes, the denoised frame through the toInt
  * thresholds and alpha of bdpt_read_pixels.  Either may be NULL, not both.  Synchronous; writes
@@ -355,6 +428,8 @@ int  bdpt_last_aov_ms(bdpt_ctx *ctx, float *ms);
  * (bdpt_create_multi).  BDPT_ESTATE: no camera set. */
 #define BDPT_DENOISE_DIFFUSE 0
 #define BDPT_DENOISE_ALL     1
+#define BDPT_DENOISE_THROUGH 3   /* guides through mirrors and glass (bdpt_render_chain); 2 is no
+                                    value: callers that probe the field with it keep their BDPT_EINVAL */
 typedef struct { int levels; int normal_power; float sigma_color; int materials; } bdpt_denoise_params;
 int  bdpt_denoise(bdpt_ctx *ctx, const bdpt_denoise_params *params, bdpt_vec *colors_out,
                   unsigned char *rgba_out);
