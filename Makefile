@@ -143,7 +143,7 @@ ASAN_FLAGS := -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize
 ASAN_DIR   := tests/native/_asan
 asan: $(ASAN_DIR)/smallpt_asan $(ASAN_DIR)/oracle_asan $(ASAN_DIR)/aov_asan $(ASAN_DIR)/denoise_asan $(ASAN_DIR)/reproject_asan \
       $(ASAN_DIR)/preview_asan $(ASAN_DIR)/noise_asan $(ASAN_DIR)/tiles_asan $(ASAN_DIR)/denoise_noise_asan \
-      $(ASAN_DIR)/chain_asan
+      $(ASAN_DIR)/chain_asan $(ASAN_DIR)/follow_asan
 
 $(ASAN_DIR):
 	mkdir -p $(ASAN_DIR)
@@ -158,9 +158,10 @@ $(ASAN_DIR)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h $(CSRC)/bdpt_fil
 # tests/native/asan_cpu_abi.cpp.  It used to be a chain of files, each including the one before and
 # adding a service's entry points, with asan_cpu_abi_noise.cpp on top; a tests/ tree that still has
 # the chain (the sanitizer tests as they stood before the layer became one file) builds its top.
-# asan_cpu_abi_denoise_noise.cpp is the top now: it includes asan_cpu_abi_noise.cpp and adds
-# bdpt_denoise_noise (smallpt --denoise-noise).
-ASAN_ABI_SRC := $(firstword $(wildcard tests/native/asan_cpu_abi_denoise_noise.cpp) $(wildcard tests/native/asan_cpu_abi_noise.cpp) tests/native/asan_cpu_abi.cpp)
+# asan_cpu_abi_denoise_noise.cpp includes asan_cpu_abi_noise.cpp and adds bdpt_denoise_noise (smallpt
+# --denoise-noise); asan_cpu_abi_follow.cpp is the top now: it includes that one and adds
+# bdpt_history_follow and bdpt_history_motion (smallpt --reproject-follow).
+ASAN_ABI_SRC := $(firstword $(wildcard tests/native/asan_cpu_abi_follow.cpp) $(wildcard tests/native/asan_cpu_abi_denoise_noise.cpp) $(wildcard tests/native/asan_cpu_abi_noise.cpp) tests/native/asan_cpu_abi.cpp)
 $(ASAN_DIR)/asan_cpu_abi.o: $(ASAN_ABI_SRC) $(wildcard tests/native/asan_cpu_abi*.cpp) $(CSRC)/bdpt_cpu.h include/bdpt.h | $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -std=c++17 -c $< -o $@
 
@@ -184,6 +185,10 @@ $(ASAN_DIR)/denoise_asan: tests/native/denoise_asan.cpp $(CSRC)/bdpt_cpu.h inclu
 
 # the CPU backend's history and reprojection driven directly; tests/test_reproject_asan.py
 $(ASAN_DIR)/reproject_asan: tests/native/reproject_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
+	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
+
+# the CPU backend's sphere-following history (bdpt_cpu_history_follow) driven directly; tests/test_follow_asan.py
+$(ASAN_DIR)/follow_asan: tests/native/follow_asan.cpp $(CSRC)/bdpt_cpu.h include/bdpt.h $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o
 	g++ $(ASAN_FLAGS) -std=c++17 -o $@ $< $(ASAN_DIR)/bdpt_cpu.o $(ASAN_DIR)/bdpt_util.o -lm -pthread
 
 # the CPU backend's denoised preview (bdpt_cpu_preview_denoise) driven directly; tests/test_preview_asan.py

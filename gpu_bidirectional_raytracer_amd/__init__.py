@@ -565,9 +565,28 @@ class Renderer:
     def history_clear(self) -> None:
         self._chk(lib.bdpt_history_clear(self._h))
 
+    def history_follow(self, on: bool = True) -> None:
+        """Opt in to (or out of) a history that follows moved spheres: one taken under spheres that
+        differ from the current ones only by translations of non-emitting spheres stays present,
+        and a pixel on a moved sphere fetches its history where that sphere was (include/bdpt.h
+        bdpt_history_follow).  Off by default; the switch survives set_scene, set_camera and
+        reset_accum."""
+        self._chk(lib.bdpt_history_follow(self._h, int(bool(on))))
+
+    def history_motion(self) -> Tuple[int, Optional[np.ndarray]]:
+        """(state, delta): the stored history against the current spheres, whether history_follow is
+        on or off -- 0 none stored, 1 the spheres are the same bytes, 2 followable, 3 not usable --
+        and in states 1 and 2 the spheres' offsets from the history's, [n, 3] float32 (else None)."""
+        n = lib.bdpt_get_scene(self._h, None, 0)
+        state = ctypes.c_int(-1)
+        delta = np.zeros((max(n, 0), 3), np.float32)
+        self._chk(lib.bdpt_history_motion(self._h, ctypes.byref(state), _ptr(delta), max(n, 0)))
+        return state.value, (delta if state.value in (1, 2) else None)
+
     def history_info(self) -> Tuple[bool, Optional[Camera]]:
         """(present, camera): whether a history is stored and the scene is still the one it was
-        taken under, and the camera of the stored history (None if none was ever stored)."""
+        taken under (with history_follow on: or one it can follow), and the camera of the stored
+        history (None if none was ever stored)."""
         present, cam = ctypes.c_int(-1), Camera()
         cam.orig.x = float("nan")
         self._chk(lib.bdpt_history_info(self._h, ctypes.byref(present), ctypes.byref(cam)))
@@ -768,10 +787,15 @@ class SmallPT:
 
     def __init__(self, width: Optional[int] = None, height: Optional[int] = None,
                  scene: Optional[str] = None, device: int = 0, dat_path: str = DEFAULT_DAT,
-                 reuse_history: bool = False):
+                 reuse_history: bool = False, follow_spheres: bool = False):
         # reuse_history: camera keys capture the frame before ReInit discards it, so that preview()
         # can reproject it into the new view (Renderer.reproject); the render path is unchanged
+        # follow_spheres (with reuse_history): sphere and selection keys capture the frame too instead
+        # of clearing the history, which then follows the moved sphere (Renderer.history_follow)
         self.reuse_history = bool(reuse_history)
+        self.follow_spheres = bool(follow_spheres)
+        if self.follow_spheres and not self.reuse_history:
+            raise ValueError("follow_spheres=True needs reuse_history=True")
         if scene is not None:
             self.camera, self.spheres = read_scene(scene)
             self.width, self.height = int(width), int(height)
@@ -798,6 +822,8 @@ class SmallPT:
         if self.renderer is None:
             self.renderer = Renderer(self.spheres, self.width, self.height, self.camera,
                                      self.dat_path, self.device)
+            if self.follow_spheres:
+                self.renderer.history_follow(True)
         else:                                                 # buffers persist (Appendix A.6)
             self.renderer.reset_accum()
             self.renderer.set_scene(self.spheres)
@@ -927,7 +953,9 @@ class SmallPT:
         self.UpdateRendering(1)
 
     def ReInitScene(self) -> None:                           # smallpt_cpu.c:365-371
-        if self.reuse_history:                                # a moved sphere changes the lighting everywhere
+        if self.follow_spheres:                               # the context still holds the old spheres
+            self.renderer.history_capture()
+        elif self.reuse_history:                              # a moved sphere changes the lighting everywhere
             self.renderer.history_clear()
         self.current_sample = 0
         self.sched.state.flag = 1

@@ -188,6 +188,8 @@ _SIGS = [
     ("bdpt_last_denoise_ms", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("bdpt_history_capture", ctypes.c_int, [_P, ctypes.POINTER(ReprojectParams)]),
     ("bdpt_history_clear", ctypes.c_int, [_P]),
+    ("bdpt_history_follow", ctypes.c_int, [_P, ctypes.c_int]),
+    ("bdpt_history_motion", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), _P, ctypes.c_uint]),
     ("bdpt_history_info", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(Camera)]),
     ("bdpt_history_read", ctypes.c_int, [_P, _P, _P]),
     ("bdpt_history_write", ctypes.c_int, [_P, ctypes.POINTER(Camera), _P, _P]),

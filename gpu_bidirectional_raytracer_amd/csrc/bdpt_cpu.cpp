@@ -177,8 +177,8 @@ struct bdpt_cpu_ctx {
     int shard = 0, nshards = 1, band_rows = 8;
     int threads = 1;
     // history of bdpt_reproject (include/bdpt.h): colour, weight and guides per pixel under hcam
-    // and the spheres hsph; has_hist says that one is stored
-    bool has_hist = false;
+    // and the spheres hsph; has_hist says that one is stored; follow: bdpt_history_follow's switch
+    bool has_hist = false, follow = false;
     bdpt_camera hcam{};
     std::vector<bdpt_sphere> hsph;
     std::vector<bdpt_vec> hc, gpos;
@@ -771,9 +771,40 @@ void bdpt_cpu_denoise(const bdpt_cpu_ctx* c, const bdpt_denoise_params* p, bdpt_
 // Temporal reprojection (include/bdpt.h bdpt_reproject): the current camera's
 // unjittered first hit, its point projected into the history's camera, four validated bilinear
 // taps, the blend by sample count -- bdpt_filter.h's rp_project, rp_tap, rp_history and rp_blend.
+// The state of a history taken under s0[n0] against the spheres s[n] (include/bdpt.h
+// bdpt_history_motion: the followable rule and the offsets), host code shared by both backends.
+// delta (n entries, may be nullptr) is written in the states SAME and MOVED only.
+int bdpt_history_state(bool stored, const bdpt_sphere* s0, size_t n0, const bdpt_sphere* s, size_t n, bdpt_vec* delta) {
+    if (!stored) return BDPT_HISTORY_NONE;
+    if (n0 != n) return BDPT_HISTORY_UNUSABLE;
+    if (n == 0 || memcmp(s0, s, sizeof(bdpt_sphere) * n) == 0) {
+        if (delta)
+            for (size_t k = 0; k < n; k++) delta[k] = {0.f, 0.f, 0.f};
+        return BDPT_HISTORY_SAME;
+    }
+    for (size_t k = 0; k < n; k++) {
+        const bdpt_sphere &a = s0[k], &b = s[k];
+        if (memcmp(&a.rad, &b.rad, sizeof a.rad) || memcmp(&a.e, &b.e, sizeof a.e) || memcmp(&a.c, &b.c, sizeof a.c) ||
+            memcmp(&a.refl, &b.refl, sizeof a.refl))
+            return BDPT_HISTORY_UNUSABLE;
+        const bool emits = !(b.e.x == 0.f && b.e.y == 0.f && b.e.z == 0.f);
+        if (emits && memcmp(&a.p, &b.p, sizeof a.p)) return BDPT_HISTORY_UNUSABLE;
+    }
+    if (delta)
+        for (size_t k = 0; k < n; k++) {
+            const bdpt_vec &a = s0[k].p, &b = s[k].p;
+            delta[k] = {b.x == a.x ? 0.f : b.x - a.x, b.y == a.y ? 0.f : b.y - a.y, b.z == a.z ? 0.f : b.z - a.z};
+        }
+    return BDPT_HISTORY_MOVED;
+}
+
+void bdpt_cpu_history_follow(bdpt_cpu_ctx* c, int on) { c->follow = on != 0; }
+int bdpt_cpu_history_motion(const bdpt_cpu_ctx* c, bdpt_vec* delta) {
+    return bdpt_history_state(c->has_hist, c->hsph.data(), c->hsph.size(), c->scene.s.data(), c->scene.s.size(), delta);
+}
 bool bdpt_cpu_history_present(const bdpt_cpu_ctx* c) {
-    return c->has_hist && c->hsph.size() == c->scene.s.size() &&
-           memcmp(c->hsph.data(), c->scene.s.data(), sizeof(bdpt_sphere) * c->hsph.size()) == 0;
+    const int state = bdpt_cpu_history_motion(c, nullptr);
+    return state == BDPT_HISTORY_SAME || (c->follow && state == BDPT_HISTORY_MOVED);
 }
 bool bdpt_cpu_history_stored(const bdpt_cpu_ctx* c, bdpt_camera* cam) {
     if (c->has_hist && cam) *cam = c->hcam;
@@ -790,7 +821,11 @@ namespace {
 void reproject_frame(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, const FirstHit& f,
                      std::vector<bdpt_vec>& out, std::vector<float>& wout) {
     const int W = c->W, H = c->H;
-    const bool present = bdpt_cpu_history_present(c);
+    // "follow": the offsets of a history whose spheres have moved (empty: P stands as it is)
+    std::vector<bdpt_vec> delta(c->follow ? c->scene.s.size() : 0);
+    const int state = bdpt_cpu_history_motion(c, delta.empty() ? nullptr : delta.data());
+    const bool present = state == BDPT_HISTORY_SAME || (c->follow && state == BDPT_HISTORY_MOVED);
+    if (state != BDPT_HISTORY_MOVED) delta.clear();
     const bool all_materials = p->materials == BDPT_DENOISE_ALL;
     const bdpt_camera& c0 = c->hcam;
     const f3 ux = of3(unit(of(c0.x))), uy = of3(unit(of(c0.y))), ud = of3(unit(of(c0.dir))), o = of3(c0.orig);
@@ -804,7 +839,8 @@ void reproject_frame(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, cons
             float m = 0.f;
             f3 h = mk(0.f, 0.f, 0.f);
             if (present && guide_id(id1, all_materials, c->scene.s.data()) >= 0) {
-                const f3 P = of3(f.pos[i]), N = of3(f.nrm[i]);
+                const f3 N = of3(f.nrm[i]);
+                const f3 P = delta.empty() ? of3(f.pos[i]) : rp_follow(of3(f.pos[i]), of3(delta[id1]));
                 float fx, fy;
                 if (rp_project(P, o, ux, uy, ud, hw, hh, sx, sy, W, H, fx, fy)) {
                     const float xf = floorf(fx), yf = floorf(fy);

@@ -3,6 +3,7 @@
 #ifndef BDPT_CPU_H
 #define BDPT_CPU_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/bdpt.h"
@@ -36,7 +37,14 @@ inline bool bdpt_chain_keys_fit(unsigned n) {
 void bdpt_cpu_denoise(const bdpt_cpu_ctx* c, const bdpt_denoise_params* p, bdpt_vec* colors_out,
                       unsigned char* rgba_out);
 // temporal reprojection (include/bdpt.h bdpt_reproject); the caller has checked parameters and camera
-bool bdpt_cpu_history_present(const bdpt_cpu_ctx* c);                       // stored and the scene unchanged
+bool bdpt_cpu_history_present(const bdpt_cpu_ctx* c);                       // stored and usable (state 1, or 2 with follow on)
+// "follow" (include/bdpt.h bdpt_history_follow / bdpt_history_motion): the switch, and the state
+// BDPT_HISTORY_* with the offsets (delta: one per sphere of the context, or nullptr)
+void bdpt_cpu_history_follow(bdpt_cpu_ctx* c, int on);
+int bdpt_cpu_history_motion(const bdpt_cpu_ctx* c, bdpt_vec* delta);
+// the state of a history (`stored`) taken under s0[n0] against the spheres s[n], and the offsets in
+// the states SAME and MOVED: host code shared by both backends
+int bdpt_history_state(bool stored, const bdpt_sphere* s0, size_t n0, const bdpt_sphere* s, size_t n, bdpt_vec* delta);
 bool bdpt_cpu_history_stored(const bdpt_cpu_ctx* c, bdpt_camera* cam);     // stored at all; *cam = C0 then
 void bdpt_cpu_history_clear(bdpt_cpu_ctx* c);
 void bdpt_cpu_history_read(const bdpt_cpu_ctx* c, bdpt_vec* colors, float* weight);

@@ -196,6 +196,12 @@ struct bdpt_ctx {
     bool has_hist = false;              // a history is stored (under hist_cam / hist_spheres)
     bdpt_camera hist_cam{};
     std::vector<bdpt_sphere> hist_spheres;
+    // "follow" (bdpt_history_follow): the switch, and the spheres' offsets from hist_spheres as one
+    // float4 per sphere on the device, made on first use; hdelta_up is what d_hdelta holds, so the
+    // table is uploaded when the offsets change, not per call
+    bool hist_follow = false;
+    float4* d_hdelta = nullptr;
+    std::vector<float4> hdelta_up;
     // (the denoised preview, bdpt_preview_denoise, works in d_dn and d_hist's result buffers)
     // noise estimate (bdpt_noise_estimate): the mark's 16-byte records and the results of a call
     // (the per-pixel plane, then S, E, c and the pending count per tile), each made on first use.

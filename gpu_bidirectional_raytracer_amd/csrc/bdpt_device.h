@@ -24,6 +24,8 @@
 //             pong colours; made on the first call                                  48 B/pixel
 //   d_hist    float4[4][W*H] + 20 B/pixel  reprojection (bdpt_reproject): two sets of history records
 //             {gpos, gid}, {hc, hm} and the packed results; made on first use        84 B/pixel
+//   d_hdelta  float4[n]             "follow" (bdpt_history_follow): the spheres' offsets from the
+//             history's, written when a sphere has moved; made on first use          16 B/sphere
 //   bdpt_preview_denoise works in d_dn (the count in the colour records' .w) and d_hist's results;
 //   bdpt_denoise_noise works in d_dn (the variance in .w) and reads d_mark, the noise estimate's
 //   uint4[W*H] records {mc, mn}; its packed results and variance plane go into d_aov
@@ -296,7 +298,10 @@ struct bdpt_reproject_args {
     const unsigned* counter;
     const float4* hguide;           // nullptr: no history present (out = colors, weight = counter)
     const float4* hcol;
-    float4* next;                   // capture: the next history's {colour, weight} records
+    // "follow" (bdpt_history_follow): {delta[k], 0} per sphere, the offsets of the context's spheres
+    // from the history's; nullptr unless follow is on and some sphere has moved (BDPT_HISTORY_MOVED)
+    const float4* hdelta;
+    float4* next;                  // capture: the next history's {colour, weight} records
     bdpt_dev_vec* out3;             // any of these may be nullptr
     float* weight;
     uchar4* rgba;

@@ -242,6 +242,11 @@ BDPT_FLT bool rp_project(f3 P, f3 o, f3 ux, f3 uy, f3 ud, float hw, float hh, fl
     return fx >= -1.f && fx < (float)W && fy >= -1.f && fy < (float)H;
 }
 
+// "Follow" (bdpt_history_follow): the first-hit point where its sphere was when the history was
+// taken, P' = P - delta[id1].  It replaces P in rp_project and in rp_tap's plane test and nowhere
+// else.  x - (+0) == x for every x, -0 included, so an unmoved sphere's pixel keeps P's bits.
+BDPT_FLT f3 rp_follow(f3 P, f3 delta) { return sub(P, delta); }
+
 // Bilinear tap k (dx = k & 1, dy = k >> 1; dy outer, dx inner, as defined) with the fractions
 // (wx, wy).  in: the tap is inside the frame; where it is not, the caller passes any record.  The
 // tap counts where its weight is positive, it shows the pixel's sphere id1, has a count m_q > 0

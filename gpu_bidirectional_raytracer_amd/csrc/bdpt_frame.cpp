@@ -530,10 +530,53 @@ int bdpt_last_denoise_noise_ms(bdpt_ctx* c, float* ms) {
 // bdpt_history_pack_kernel writing the next history's guide records from its planes, then
 // bdpt_reproject_kernel, which reads the history's records and writes the packed results or the
 // next history's colour records; then the read-back.  Only d_aov and d_hist are written.
-static bool hist_present(const bdpt_ctx* c) {
-    if (c->cpu) return bdpt_cpu_history_present(c->cpu);
-    return c->has_hist && c->hist_spheres.size() == c->spheres.size() &&
-           memcmp(c->hist_spheres.data(), c->spheres.data(), sizeof(bdpt_sphere) * c->spheres.size()) == 0;
+// The state of the stored history against the context's spheres (BDPT_HISTORY_*; delta: one offset
+// per sphere in the states SAME and MOVED, or nullptr), and whether a history in that state is present.
+static int hist_state(const bdpt_ctx* c, bdpt_vec* delta) {
+    if (c->cpu) return bdpt_cpu_history_motion(c->cpu, delta);
+    return bdpt_history_state(c->has_hist, c->hist_spheres.data(), c->hist_spheres.size(), c->spheres.data(),
+                              c->spheres.size(), delta);
+}
+static bool hist_present(const bdpt_ctx* c, int state) {
+    return state == BDPT_HISTORY_SAME || (c->hist_follow && state == BDPT_HISTORY_MOVED);
+}
+static bool hist_present(const bdpt_ctx* c) { return hist_present(c, hist_state(c, nullptr)); }
+
+// What a call finds of the history: whether one is present, and ("follow", some sphere moved) the
+// table of offsets in d_hdelta, one float4 per sphere.  The table is written here, with the state,
+// when the offsets are not the ones it holds -- once per sphere move, before the service's clock
+// starts.  The copy's source is hdelta_up, which stands until the next move.
+struct hist_use {
+    bool present;
+    const float4* hdelta;
+};
+static int hist_eval(bdpt_ctx* c, hist_use* u) {
+    const size_t n = c->spheres.size();
+    std::vector<bdpt_vec> delta(c->hist_follow ? n : 0);
+    const int state = hist_state(c, delta.empty() ? nullptr : delta.data());
+    u->present = hist_present(c, state);
+    u->hdelta = nullptr;
+    if (!c->hist_follow || state != BDPT_HISTORY_MOVED) return BDPT_OK;
+    std::vector<float4> table(n);
+    for (size_t k = 0; k < n; k++) table[k] = make_float4(delta[k].x, delta[k].y, delta[k].z, 0.f);
+    const bool held = c->d_hdelta && c->hdelta_up.size() == n &&
+                      memcmp(c->hdelta_up.data(), table.data(), sizeof(float4) * n) == 0;
+    if (!held) {
+        if (c->hdelta_up.size() != n || !c->d_hdelta) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));           // an earlier call's kernels are done anyway
+            if (c->d_hdelta) HIPCHK(c, hipFree(c->d_hdelta));
+            c->d_hdelta = nullptr;
+            c->hdelta_up.clear();
+            if (hipMalloc(&c->d_hdelta, sizeof(float4) * n) != hipSuccess) {
+                c->d_hdelta = nullptr;
+                return fail(c, BDPT_ENOMEM, "bdpt_reproject: the followed spheres' offsets (%zu B)", sizeof(float4) * n);
+            }
+        }
+        c->hdelta_up.swap(table);
+        HIPCHK(c, hipMemcpyAsync(c->d_hdelta, c->hdelta_up.data(), sizeof(float4) * n, hipMemcpyHostToDevice, c->stream));
+    }
+    u->hdelta = c->d_hdelta;
+    return BDPT_OK;
 }
 
 static int rp_check(bdpt_ctx* c, const bdpt_reproject_params* p, const char* who) {
@@ -568,9 +611,9 @@ static int hist_alloc(bdpt_ctx* c, hist_bufs* b) {
 }
 
 // bdpt_reproject_kernel's arguments but for its outputs: the current view's first hit (av), the
-// frame, and the history present, if any
+// frame, and the history present, if any (hist_eval's answer)
 static bdpt_reproject_args rp_args(bdpt_ctx* c, const bdpt_reproject_params* p, const bdpt_aov_args& av,
-                                   const hist_bufs& b) {
+                                   const hist_bufs& b, const hist_use& u) {
     bdpt_reproject_args v;
     memset(&v, 0, sizeof(v));
     v.W = c->W; v.H = c->H;
@@ -582,7 +625,7 @@ static bdpt_reproject_args rp_args(bdpt_ctx* c, const bdpt_reproject_params* p, 
     v.colors = c->d_colors;
     v.counter = c->d_counter;
     v.gamma_thr = c->d_thr;
-    if (hist_present(c)) {
+    if (u.present) {
         bdpt_path_args ha;                                    // C0 as the kernels' camera constants
         memset(&ha, 0, sizeof(ha));
         camera_args(c, c->hist_cam, ha);
@@ -592,6 +635,7 @@ static bdpt_reproject_args rp_args(bdpt_ctx* c, const bdpt_reproject_params* p, 
         v.sx = 1.f / ha.inv_w; v.sy = 1.f / ha.inv_h;
         v.hguide = b.guide[c->hist_cur];
         v.hcol = b.col[c->hist_cur];
+        v.hdelta = u.hdelta;
     }
     // wave tile: the measured choice; BDPT_REPROJECT_TILE = 8 / 64 overrides it
     v.rows = 1;
@@ -627,12 +671,14 @@ static int rp_run(bdpt_ctx* c, const bdpt_reproject_params* p, bool capture, con
     dn_bufs d{};
     if (pv)
         if (int rc = dn_alloc(c, "bdpt_preview_denoise", &d)) return rc;
+    hist_use use;
+    if (int rc = hist_eval(c, &use)) return rc;
     if (int rc = join_fold(c)) return rc;
     if (int rc = svc_begin(c, svc)) return rc;
     bdpt_aov_args av;
     if (int rc = aov_frame(c, c->cam, &av)) return rc;
     const int nxt = c->hist_cur ^ 1;
-    bdpt_reproject_args v = rp_args(c, p, av, b);
+    bdpt_reproject_args v = rp_args(c, p, av, b, use);
     const frame_outs want = wanted(b.res, colors_out, weight_out, rgba_out);   // a capture wants none
     if (capture) {
         hipLaunchKernelGGL(bdpt_history_pack_kernel, lane_grid(np), dim3(256), 0, c->stream, (const int*)av.id,
@@ -698,6 +744,22 @@ int bdpt_history_clear(bdpt_ctx* c) {
     if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_history_clear: multi-device contexts keep no history");
     if (c->cpu) bdpt_cpu_history_clear(c->cpu);
     c->has_hist = false;
+    return BDPT_OK;
+}
+
+int bdpt_history_follow(bdpt_ctx* c, int on) {
+    if (!c) return BDPT_EINVAL;
+    if (c->multi) return fail(c, BDPT_EINVAL, "bdpt_history_follow: multi-device contexts keep no history");
+    if (c->cpu) bdpt_cpu_history_follow(c->cpu, on);
+    c->hist_follow = on != 0;
+    return BDPT_OK;
+}
+
+int bdpt_history_motion(const bdpt_ctx* c, int* state, bdpt_vec* delta, unsigned n) {
+    if (!c || c->multi) return BDPT_EINVAL;
+    if (delta && n != c->spheres.size()) return BDPT_EINVAL;
+    const int s = hist_state(c, delta);
+    if (state) *state = s;
     return BDPT_OK;
 }
 

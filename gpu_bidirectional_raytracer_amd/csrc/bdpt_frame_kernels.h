@@ -313,7 +313,10 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_history_pack_kernel(
 // One lane per pixel: the projection of the pixel's first-hit point into the history's camera,
 // four validated taps of two 16-byte loads each (issued together; a tap outside the frame reads the
 // lane's own record, always a valid address, and is not used), the blend, and the stores the call
-// asked for.  Wave tiles 8 x 8 or 64 x 1 (v.rows), as in bdpt_aov_kernel.
+// asked for.  Wave tiles 8 x 8 or 64 x 1 (v.rows), as in bdpt_aov_kernel.  With "follow"
+// (v.hdelta: some sphere has moved since the history was taken) the lane first gathers its sphere's
+// offset, one 16-byte load from a table the L1 holds, and projects and plane-tests
+// the point shifted back by it (rp_follow).
 extern "C" __global__ __launch_bounds__(256) void bdpt_reproject_kernel(bdpt_reproject_args v) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = v.rows ? (int)blockIdx.x * BDPT_RP_ROW_BTW + lane
@@ -331,7 +334,12 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_reproject_kernel(bdpt_rep
     f3 h = mk(0.f, 0.f, 0.f);
     if (v.hguide != nullptr && g1 >= 0) {
         const bdpt_dev_vec p3 = v.position[i], n3 = v.normal[i];
-        const f3 P = mk(p3.x, p3.y, p3.z), N = mk(n3.x, n3.y, n3.z);
+        const f3 N = mk(n3.x, n3.y, n3.z);
+        f3 P = mk(p3.x, p3.y, p3.z);
+        if (v.hdelta != nullptr) {                        // "follow": where the pixel's sphere was (uniform branch)
+            const float4 d = v.hdelta[id1];
+            P = rp_follow(P, mk(d.x, d.y, d.z));
+        }
         float fx, fy;
         if (rp_project(P, mk(v.o[0], v.o[1], v.o[2]), mk(v.ux[0], v.ux[1], v.ux[2]), mk(v.uy[0], v.uy[1], v.uy[2]),
                        mk(v.ud[0], v.ud[1], v.ud[2]), v.hw, v.hh, v.sx, v.sy, v.W, v.H, fx, fy)) {

@@ -166,7 +166,7 @@ static void release(bdpt_ctx* c) {
                     c->d_counter, c->d_pixels, c->d_thr, c->d_rbuf, c->d_rmask, c->d_poolctr, c->d_uflags, c->d_uerr, c->d_bvh_nodes,
                     c->d_bvh_geom, c->d_big_geom, c->d_mat, c->d_bvh_ids, c->d_big_ids,
                     c->d_fcolors, c->d_fcounter, c->d_fpixels, c->d_ftmp, c->d_ftmpc, c->d_aov, c->d_chain, c->d_dn, c->d_hist,
-                    c->d_mark, c->d_noise, c->d_tiles};
+                    c->d_hdelta, c->d_mark, c->d_noise, c->d_tiles};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (const bdpt_svc_clock& k : c->svc)

@@ -6,7 +6,7 @@
  *   smallpt [<width> <height> <scene.scn>] [--spp N] [--batch B] [--keys KEYS] [--out F.ppm]
  *           [--device D | --gpus N | --devices D0,D1,...] [--tile ROWS] [--seed S] [--dat PATH]
  *           [--denoise [--denoise-levels N] [--denoise-sigma S] [--denoise-all] [--denoise-count N]]
- *           [--reproject [--reproject-history N] [--reproject-tol T]]
+ *           [--reproject [--reproject-history N] [--reproject-tol T] [--reproject-follow]]
  *           [--until E [--max-spp N] [--adaptive [--min-spp N]]] [--denoise-noise [S]]
  *
  * Without positional arguments the built-in CornellSpheres scene is used (smallpt_cpu.c:400).
@@ -31,7 +31,10 @@
  * the frame before re-initialising (bdpt_history_capture), a sphere key clears the history, and
  * --out is written from the preview's pixels (bdpt_reproject: history weight capped at
  * --reproject-history, default 64; plane test --reproject-tol, default 0.01); one device (or the
- * CPU) only.  The accumulation itself is unchanged.
+ * CPU) only.  The accumulation itself is unchanged.  --reproject-follow (with --reproject) keeps
+ * the history across sphere and selection keys as well: they capture the frame instead of clearing
+ * the history, and a pixel on a moved sphere fetches its history where the sphere was
+ * (bdpt_history_follow).
  * --reproject --denoise together write --out from the denoised preview (bdpt_preview_denoise: the
  * reprojected frame filtered with per-pixel sample counts; the --denoise-* options apply,
  * --denoise-all to both stages of that call, and --denoise-count N sets count_ref, default 8).
@@ -106,6 +109,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[a], "--reproject")) h.reuse_history = 1;
         else if (!strcmp(argv[a], "--reproject-history") && a + 1 < argc) h.rp.max_history = strtof(argv[++a], NULL);
         else if (!strcmp(argv[a], "--reproject-tol") && a + 1 < argc) h.rp.plane_tol = strtof(argv[++a], NULL);
+        else if (!strcmp(argv[a], "--reproject-follow")) h.follow_spheres = 1;
         else if (!strcmp(argv[a], "--until") && a + 1 < argc) { until = 1; nz.threshold = strtof(argv[++a], NULL); }
         else if (!strcmp(argv[a], "--max-spp") && a + 1 < argc) max_spp = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--adaptive")) adaptive = 1;
@@ -127,6 +131,10 @@ int main(int argc, char **argv)
     }
     if (h.reuse_history && ndev) {
         fprintf(stderr, "--reproject needs one device (--device D, or -1 for the CPU)\n");
+        return 1;
+    }
+    if (h.follow_spheres && !h.reuse_history) {
+        fprintf(stderr, "--reproject-follow goes with --reproject\n");
         return 1;
     }
     if (until && ndev) {
@@ -173,6 +181,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "Devices: %d, frame reduce: %s\n", bdpt_num_devices(h.ctx), bdpt_reduce_backend(h.ctx));
     }
     report(&h, bdpt_set_camera(h.ctx, &h.camera), "camera");
+    if (h.follow_spheres) report(&h, bdpt_history_follow(h.ctx, 1), "history follow");
 
     /* IdleFunc display_func.c:192-217: frame 1 = light pass then path pass; then path passes */
     update_rendering2(&h);

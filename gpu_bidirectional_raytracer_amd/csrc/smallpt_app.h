@@ -31,6 +31,7 @@ typedef struct {
     float total_time;
     bdpt_pass_state ps;
     int reuse_history;                 /* --reproject: camera keys capture the frame before ReInit */
+    int follow_spheres;                /* --reproject-follow: sphere and selection keys capture it too */
     bdpt_reproject_params rp;
 } host;
 
@@ -89,7 +90,10 @@ static void reinit(host *h)
 /* ReInitScene smallpt_cpu.c:365-371 */
 static void reinit_scene(host *h)
 {
-    if (h->reuse_history) report(h, bdpt_history_clear(h->ctx), "ReInitScene history");
+    /* the context still holds the old spheres: with --reproject-follow the frame becomes the history,
+     * which then follows the moved sphere (bdpt_history_follow) */
+    if (h->follow_spheres) report(h, bdpt_history_capture(h->ctx, &h->rp), "ReInitScene history capture");
+    else if (h->reuse_history) report(h, bdpt_history_clear(h->ctx), "ReInitScene history");
     h->current_sample = 0;
     report(h, bdpt_reset_accum(h->ctx), "ReInitScene");
     report(h, bdpt_set_scene(h->ctx, h->spheres, h->n), "ReInitScene upload");

@@ -449,7 +449,8 @@ int  bdpt_last_denoise_ms(bdpt_ctx *ctx, float *ms);
  *             behind the colour) and the guides gid[q], gpos[q] = id and position of
  *             bdpt_render_aov with jitter = 0 under C0, whole frame, rendered once when the history
  *             is taken.  While the context's spheres differ from the remembered array byte for
- *             byte the history counts as absent (a moved sphere changes the lighting everywhere).
+ *             byte the history counts as absent (a moved sphere changes the lighting everywhere;
+ *             "follow" below is the opt-in exception).
  *   C0        as the kernels' camera constants: ux, uy, ud = vnorm of C0.x, C0.y, C0.dir
  *             (l = 1.f / sqrtf((x*x + y*y) + z*z), each component times l); o = C0.orig;
  *             inv_w = (float)(14./W), inv_h = (float)(10.5/H);
@@ -502,6 +503,50 @@ int  bdpt_history_write(bdpt_ctx *ctx, const bdpt_camera *camera, const bdpt_vec
 int  bdpt_reproject(bdpt_ctx *ctx, const bdpt_reproject_params *params, bdpt_vec *colors_out,
                     float *weight_out, unsigned char *rgba_out);
 int  bdpt_last_reproject_ms(bdpt_ctx *ctx, float *ms);
+
+/* ---- "follow": the history stays usable when a sphere is moved (no reference counterpart: every
+ * sphere key goes through ReInitScene, smallpt_cpu.c:365-371, which discards the frame;
+ * DESIGN.md 4k) ----
+ * Opt-in.  A moved sphere does change the lighting everywhere, but at preview sample counts the
+ * noise of a fresh frame is far larger than the bias of the stale shadows, and nearly all of the
+ * old frame is still the same surface: with follow on, a history taken under the spheres S0 stays
+ * present under the spheres S when S differs from S0 only by translations of non-emitting spheres,
+ * and a pixel that shows a moved sphere fetches its history where that sphere was.
+ *   state     of the stored history against the context's spheres (bdpt_history_motion):
+ *               BDPT_HISTORY_NONE     0  no history stored
+ *               BDPT_HISTORY_SAME     1  stored, and the spheres are equal byte for byte
+ *               BDPT_HISTORY_MOVED    2  stored and followable
+ *               BDPT_HISTORY_UNUSABLE 3  stored and not usable
+ *   followable  the sphere count is the same; for every k rad, e, c and refl are byte-equal; p may
+ *             differ only where all three components of e compare == 0.f (the rule by which the
+ *             path kernel's light list is filled).  A moved emitter, a changed radius, colour or
+ *             material and a changed count make the history absent, as without follow.
+ *   delta[k]  = S[k].p - S0[k].p, per component, in fp32, formed on the host; +0 where the
+ *             components compare equal.
+ *   bdpt_reproject with follow on: in state 1 as defined above; in state 2 as defined above with
+ *             one change: P' = P - delta[id1] (per component, fp32) replaces P in step 2 (v = P' - o)
+ *             and in the plane test of step 3 (fabsf(dot(gpos[q] - P', N)) <= plane_tol * t1).
+ *             id1, t1, N, the eligibility rule, the tap order, the cap and the blend are untouched;
+ *             the id test already refuses taps on what the sphere used to hide.  x - (+0) == x for
+ *             every x, -0 included (-0 - (+0) = -0), so a pixel on an unmoved sphere forms the bits
+ *             of the definition above.  bdpt_history_info reports present = 1 in state 2 while
+ *             follow is on.
+ *   bdpt_history_capture in state 2 with follow on forms (out, weight_out) as just defined and
+ *             stores them with the current camera as C0 and the current spheres as the key: the
+ *             state becomes 1, and captures chain across sphere moves as they do across camera
+ *             moves (a camera move and a sphere move between two captures need nothing more: C0
+ *             and delta are independent).  bdpt_preview_denoise takes bdpt_reproject's output
+ *             exactly as defined there, so it follows without a parameter of its own.
+ * bdpt_history_follow: the switch, off by default; it belongs to the context and survives
+ * bdpt_set_scene, bdpt_set_camera and bdpt_reset_accum.  While it is off every call answers as
+ * without this section: the same bits, the same `present`, the same errors.  bdpt_history_motion:
+ * *state as above, whether follow is on or off; in states 1 and 2 delta[0..n) takes the offsets (all
+ * +0 in state 1), otherwise it is left alone.  delta may be NULL; otherwise n must equal the
+ * context's sphere count.  state may be NULL.
+ * BDPT_EINVAL: a NULL or multi-device context, delta with n other than the sphere count. */
+enum { BDPT_HISTORY_NONE = 0, BDPT_HISTORY_SAME = 1, BDPT_HISTORY_MOVED = 2, BDPT_HISTORY_UNUSABLE = 3 };
+int  bdpt_history_follow(bdpt_ctx *ctx, int on);
+int  bdpt_history_motion(const bdpt_ctx *ctx, int *state, bdpt_vec *delta, unsigned n);
 
 /* ---- the reprojected preview, denoised with per-pixel sample counts (no reference counterpart;
  * DESIGN.md 4f) ----
