@@ -45,12 +45,15 @@ tests/native/plan_tiles_check: tests/native/plan_tiles_check.cpp $(CSRC)/bdpt_pl
 $(BUILD):
 	mkdir -p $(BUILD)
 
-$(BUILD)/bdpt_kernels.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h $(CSRC)/bdpt_frame_kernels.h $(CSRC)/bdpt_filter.h | $(BUILD)
+# the arithmetic stated once for the HIP kernels and the CPU backend, and what each side brings
+EYE_DEPS := $(CSRC)/bdpt_sides.h $(CSRC)/bdpt_eye.h $(CSRC)/bdpt_filter.h
+
+$(BUILD)/bdpt_kernels.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h $(CSRC)/bdpt_frame_kernels.h $(EYE_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the same file once more for launches over a tile list (BDPT_TILES: only the generic and the BVH
 # instance of the path kernel with the tile-list code, bdpt_path_tiles_kernel_table)
-$(BUILD)/bdpt_kernels_tiles.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h | $(BUILD)
+$(BUILD)/bdpt_kernels_tiles.o: $(CSRC)/bdpt_kernels.hip $(CSRC)/bdpt_device.h $(CSRC)/bdpt_math.h $(CSRC)/bdpt_sincos_table.h $(CSRC)/bdpt_leaf.h $(EYE_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -DBDPT_TILES=1 -c $< -o $@
 
 # the path kernel's sources as strings, for scene-specialised kernels compiled at run time
@@ -58,7 +61,7 @@ $(CSRC)/bdpt_jit_src.h: tools/embed_jit_sources.py $(CSRC)/bdpt_kernels.hip $(CS
 	python3 tools/embed_jit_sources.py $@
 
 CTX_DEPS := $(CSRC)/bdpt_ctx.h $(CSRC)/bdpt_device.h $(CSRC)/bdpt_plan.h $(CSRC)/bdpt_jit_plan.h $(CSRC)/bdpt_cpu.h include/bdpt.h
-$(BUILD)/bdpt_host.o: $(CSRC)/bdpt_host.cpp $(CTX_DEPS) $(CSRC)/bdpt_bvh.h | $(BUILD)
+$(BUILD)/bdpt_host.o: $(CSRC)/bdpt_host.cpp $(CTX_DEPS) $(CSRC)/bdpt_bvh.h $(EYE_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/bdpt_jit.o: $(CSRC)/bdpt_jit.cpp $(CTX_DEPS) $(CSRC)/bdpt_jit_src.h | $(BUILD)
@@ -70,7 +73,7 @@ $(BUILD)/bdpt_frame.o: $(CSRC)/bdpt_frame.cpp $(CTX_DEPS) | $(BUILD)
 $(BUILD)/bdpt_bvh.o: $(CSRC)/bdpt_bvh.cpp $(CSRC)/bdpt_bvh.h include/bdpt.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BUILD)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h $(CSRC)/bdpt_filter.h include/bdpt.h | $(BUILD)
+$(BUILD)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h $(EYE_DEPS) include/bdpt.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/bdpt_util.o: $(CSRC)/bdpt_util.c include/bdpt.h | $(BUILD)
@@ -151,7 +154,7 @@ $(ASAN_DIR):
 $(ASAN_DIR)/%.o: $(CSRC)/%.c include/bdpt.h | $(ASAN_DIR)
 	$(CC) $(ASAN_FLAGS) -std=gnu11 -c $< -o $@
 
-$(ASAN_DIR)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h $(CSRC)/bdpt_filter.h include/bdpt.h | $(ASAN_DIR)
+$(ASAN_DIR)/bdpt_cpu.o: $(CSRC)/bdpt_cpu.cpp $(CSRC)/bdpt_cpu.h $(EYE_DEPS) include/bdpt.h | $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -std=c++17 -c $< -o $@
 
 # the HIP-free context layer: every entry point smallpt calls, the frame services included, in

@@ -11,7 +11,9 @@
 //
 // The frame services (denoisers, reprojection, noise estimate) take what a pixel or a tap computes
 // from bdpt_filter.h, the one statement of it that the HIP kernels run too; this file is the host's
-// driver of it: rows over threads, plain arrays instead of packed records.
+// driver of it: rows over threads, plain arrays instead of packed records.  The eye path's vertices
+// (camera ray, hit point and normal, mirror and glass) are bdpt_eye.h's in the same way, between
+// this file's own traversal (Scene).
 #include "bdpt_cpu.h"
 
 #include <math.h>
@@ -23,27 +25,22 @@
 #include <thread>
 #include <vector>
 
+#include "bdpt_eye.h"
 #include "bdpt_filter.h"
 
 namespace {
 
 constexpr float kEps = 0.01f;                              // geom.h:6 EPSILON
 constexpr float kPi = 3.14159265358979323846f;             // geom.h:7 FLOAT_PI
-constexpr unsigned kRandN = BDPT_RAND_N;
 
-struct V3 {
-    float x, y, z;
-};
-inline V3 v3(float a, float b, float c) { return V3{a, b, c}; }
-inline V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-inline V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-inline V3 operator*(V3 a, V3 b) { return v3(a.x * b.x, a.y * b.y, a.z * b.z); }
-inline V3 operator*(float k, V3 b) { return v3(k * b.x, k * b.y, k * b.z); }
-inline float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-inline V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-inline V3 unit(V3 v) { return (1.f / sqrtf(dot(v, v))) * v; }   // vnorm (vec.h:22), fp32 on the device
-inline bool zero(V3 v) { return v.x == 0.f && v.y == 0.f && v.z == 0.f; }
-inline V3 of(const bdpt_vec& v) { return v3(v.x, v.y, v.z); }
+// the operator spelling of bdpt_sides.h's f3 operations, for the traversal and the light sampling
+inline f3 operator+(f3 a, f3 b) { return add(a, b); }
+inline f3 operator-(f3 a, f3 b) { return sub(a, b); }
+inline f3 operator*(f3 a, f3 b) { return mul(a, b); }
+inline f3 operator*(float k, f3 b) { return smul(k, b); }
+inline f3 cross(f3 a, f3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+inline bool zero(f3 v) { return v.x == 0.f && v.y == 0.f && v.z == 0.f; }
+inline f3 of(const bdpt_vec& v) { return mk(v.x, v.y, v.z); }
 inline float fsin(float x) { return (float)sin((double)x); }
 inline float fcos(float x) { return (float)cos((double)x); }
 
@@ -63,8 +60,8 @@ struct Scene {
         }
     }
     // SphereIntersectDevice device.cu:80-104: 0 = miss
-    float hit(unsigned i, V3 o, V3 d) const {
-        const V3 op = v3(px[i], py[i], pz[i]) - o;
+    float hit(unsigned i, f3 o, f3 d) const {
+        const f3 op = mk(px[i], py[i], pz[i]) - o;
         const float b = dot(op, d);
         float det = b * b - dot(op, op) + rad[i] * rad[i];
         if (det < 0.f) return 0.f;
@@ -75,7 +72,7 @@ struct Scene {
         return t2 > kEps ? t2 : 0.f;
     }
     // IntersectDevice device.cu:106-124: scan from the last sphere down, `<` keeps ties
-    bool closest(V3 o, V3 d, float* t, unsigned* id) const {
+    bool closest(f3 o, f3 d, float* t, unsigned* id) const {
         *t = 1e20f;
         for (unsigned i = n; i--;) {
             const float h = hit(i, o, d);
@@ -84,7 +81,7 @@ struct Scene {
         return *t < 1e20f;
     }
     // IntersectPDevice / IntersectPVacuumDevice device.cu:126-154
-    bool occluded(V3 o, V3 d, float maxt, bool vacuum) const {
+    bool occluded(f3 o, f3 d, float maxt, bool vacuum) const {
         for (unsigned i = n; i--;) {
             const float h = hit(i, o, d);
             if (h != 0.f && h < maxt && !(vacuum && emissive[i])) return true;
@@ -94,21 +91,21 @@ struct Scene {
 };
 
 // UniformSampleSphereDevice device.cu:157-165
-V3 sphere_point(float u1, float u2) {
+f3 sphere_point(float u1, float u2) {
     const float zz = 1.f - 2.f * u1;
     const float q = 1.f - zz * zz;
     const float r = sqrtf(0.f > q ? 0.f : q);
     const float phi = 2.f * kPi * u2;
-    return v3(r * fcos(phi), r * fsin(phi), zz);
+    return mk(r * fcos(phi), r * fsin(phi), zz);
 }
 
 // cosine-weighted direction about w (device.cu:190-212, 357-380, 676-699)
-V3 cosine_dir(V3 w, float u_phi, float r2) {
+f3 cosine_dir(f3 w, float u_phi, float r2) {
     const float r1 = 2.f * kPi * u_phi;
     const float r2s = sqrtf(r2);
-    const V3 a = fabsf(w.x) > .1f ? v3(0.f, 1.f, 0.f) : v3(1.f, 0.f, 0.f);
-    V3 u = unit(cross(a, w));
-    V3 v = cross(w, u);
+    const f3 a = fabsf(w.x) > .1f ? mk(0.f, 1.f, 0.f) : mk(1.f, 0.f, 0.f);
+    f3 u = norm(cross(a, w));
+    f3 v = cross(w, u);
     u = (fcos(r1) * r2s) * u;
     v = (fsin(r1) * r2s) * v;
     return (u + v) + sqrtf(1 - r2) * w;
@@ -131,9 +128,6 @@ void to_rgba(const float* thr, const bdpt_vec* col, size_t n, unsigned char* rgb
     }
 }
 
-// bdpt_filter.h's vector from the ABI's and from the path tracer's, and back
-inline f3 of3(const bdpt_vec& v) { return mk(v.x, v.y, v.z); }
-inline f3 of3(V3 v) { return mk(v.x, v.y, v.z); }
 inline bdpt_vec to_vec(f3 v) { return {v.x, v.y, v.z}; }
 
 int worker_count() {
@@ -269,23 +263,21 @@ void bdpt_cpu_light_pass(bdpt_cpu_ctx* c, int current_sample) {
         parallel_rows(0, BDPT_LIGHT_POINTS / 64, c->threads, [&](int blk) {
             for (int ind = blk * 64; ind < blk * 64 + 64; ind++) {
                 const unsigned i = (unsigned)(current_sample * 5 + ind * 4) % (kRandN - 4u), j = i + 2;
-                const V3 spt = L.rad * sphere_point(rnd[j], rnd[i]) + of(L.p);
-                const V3 o = spt, d = cosine_dir(unit(spt - of(L.p)), rnd[i + 1], rnd[j + 1]);
-                V3 thr = 0.25f * of(L.e);
+                const f3 spt = L.rad * sphere_point(rnd[j], rnd[i]) + of(L.p);
+                const f3 o = spt, d = cosine_dir(norm(spt - of(L.p)), rnd[i + 1], rnd[j + 1]);
+                f3 thr = 0.25f * of(L.e);
                 float t;
                 unsigned id = 0;
                 bdpt_lightpath& out = c->lp[ind];
                 if (!sc.closest(o, d, &t, &id)) {                      // escaped (:279-292)
-                    const V3 nor = (float)(-1. / (double)L.rad) * (o - of(L.p)), hr = 0.5f * of(L.e);
+                    const f3 nor = (float)(-1. / (double)L.rad) * (o - of(L.p)), hr = 0.5f * of(L.e);
                     out.hp = {o.x, o.y, o.z}; out.rad = {hr.x, hr.y, hr.z}; out.nl = {nor.x, nor.y, nor.z};
                     continue;
                 }
                 const bdpt_sphere& O = sc.s[id];
                 if (sc.emissive[id]) continue;                          // :296-298
-                const V3 h = o + t * d;
-                const V3 nrm = unit(h - of(O.p));
-                const float dp = dot(nrm, d);
-                const V3 nl = (-1.f * (float)(dp > 0 ? 1 : -1)) * nrm;
+                const eye_vertex p = eye_vertex_at(o, d, t, of(O.p));
+                const f3 h = p.hit, nl = eye_nl(p.normal, p.dp);
                 if (O.refl != BDPT_DIFF) continue;                      // DEPTH = 1: no store
                 const float tol = (float)0.0001;                         // VecMultiply :10-42
                 float* tv[3] = {&thr.x, &thr.y, &thr.z};
@@ -310,31 +302,21 @@ struct PathTracer {
     const Scene& sc;
     const float* rnd;
     const bdpt_lightpath* lp;
-    V3 ux, uy, ud, orig;
-    float tx, ty, tz, inv_w, inv_h;
-    double half_w, half_h;
+    eye_camera cam;
 
     PathTracer(const bdpt_cpu_ctx* c) : PathTracer(c, c->cam) {}
     // under a camera other than the context's (the history's, bdpt_cpu_history_write)
-    PathTracer(const bdpt_cpu_ctx* c, const bdpt_camera& cm) : sc(c->scene), rnd(c->rnd.data()), lp(c->lp.data()) {
-        ux = unit(of(cm.x)); uy = unit(of(cm.y)); ud = unit(of(cm.dir)); orig = of(cm.orig);
-        tx = dot(unit(-1.f * of(cm.x)), orig);
-        ty = dot(unit(-1.f * of(cm.y)), orig);
-        tz = dot(-1.f * of(cm.dir), orig);                      // :591-592, no vnorm
-        inv_w = (float)(14. / c->W);                            // smallpt_cpu.c:411-412
-        inv_h = (float)(10.5 / c->H);
-        half_w = (double)(inv_w * (float)c->W) / 2.;
-        half_h = (double)(inv_h * (float)c->H) / 2.;
-    }
+    PathTracer(const bdpt_cpu_ctx* c, const bdpt_camera& cm)
+        : sc(c->scene), rnd(c->rnd.data()), lp(c->lp.data()), cam(eye_camera_terms(cm, c->W, c->H)) {}
 
     // SampleLightsDevice device.cu:457-542: NEE to every emitter + one VLP, blended 1/2
-    V3 lights(V3 h, V3 nl, unsigned j, const bdpt_lightpath& v) const {
-        V3 res = v3(0.f, 0.f, 0.f);
+    f3 lights(f3 h, f3 nl, unsigned j, const bdpt_lightpath& v) const {
+        f3 res = mk(0.f, 0.f, 0.f);
         for (unsigned i = 0; i < sc.n; i++) {
             if (!sc.emissive[i]) continue;
             const bdpt_sphere& L = sc.s[i];
-            const V3 usp = sphere_point(rnd[j + 3], rnd[j + 4]);
-            V3 sd = (L.rad * usp + of(L.p)) - h;
+            const f3 usp = sphere_point(rnd[j + 3], rnd[j + 4]);
+            f3 sd = (L.rad * usp + of(L.p)) - h;
             const float len = sqrtf(dot(sd, sd));
             sd = (1.f / len) * sd;
             float wo = dot(sd, usp);
@@ -344,8 +326,8 @@ struct PathTracer {
             if (wi > 0.f && !sc.occluded(h, sd, len - kEps, false))
                 res = res + ((4.f * kPi * L.rad * L.rad) * wi * wo / (len * len)) * of(L.e);
         }
-        V3 vres = v3(0.f, 0.f, 0.f);
-        V3 vd = of(v.hp) - h;
+        f3 vres = mk(0.f, 0.f, 0.f);
+        f3 vd = of(v.hp) - h;
         const float len = sqrtf(dot(vd, vd));
         vd = (1.f / len) * vd;
         float wo = dot(vd, of(v.nl));
@@ -359,166 +341,96 @@ struct PathTracer {
         return 0.5f * res;
     }
 
-    // the camera ray of device.cu:562-600 for pixel (x, y) with the jitter randoms u0, u1
-    void camera_ray(int x, int y, float u0, float u1, V3* o, V3* d) const {
-        const float kx = (float)(((double)((float)x * inv_w) - half_w) + (double)(u0 * inv_w));
-        const float ky = (float)(((double)((float)y * inv_h) - half_h) + (double)(u1 * inv_h));
-        const float kz = 10.0f;
-        V3 rdir = v3(0.f, 0.f, 0.f);
-        rdir = rdir + kx * ux;
-        rdir = rdir + ky * uy;
-        rdir = rdir + kz * ud;
-        const float w = (tx * kx + ty * ky + tz * kz) + 1;
-        rdir = (float)(1. / w) * rdir;
-        *o = rdir + orig;
-        *d = unit(rdir);
+    // The camera ray of pixel (x, y): jittered with pass sid's randoms, or (+0, +0).
+    eye_ray camera_ray(int x, int y, int W, bool jitter, unsigned sid) const {
+        float u0 = 0.f, u1 = 0.f;
+        if (jitter) {
+            const unsigned kk = eye_rand_index((unsigned)(y * W + x), 0u, sid);
+            u0 = rnd[kk];
+            u1 = rnd[kk + 1];
+        }
+        return eye_camera_ray(cam, x, y, u0, u1);
     }
 
-    V3 sample(int x, int y, int W, unsigned sid, int vlp) const {
-        const unsigned base = 26u + (unsigned)(y * W + x) * 25u;
-        const unsigned kk = (base + sid) % (kRandN - 5u);
-        V3 o, d;
-        camera_ray(x, y, rnd[kk], rnd[kk + 1], &o, &d);
-        V3 rad = v3(0.f, 0.f, 0.f), thr = v3(1.f, 1.f, 1.f);
+    // The vertices are bdpt_eye.h's; Scene::closest is the traversal between them.
+    f3 sample(int x, int y, int W, unsigned sid, int vlp) const {
+        eye_ray r = camera_ray(x, y, W, true, sid);
+        f3 rad = mk(0.f, 0.f, 0.f), thr = mk(1.f, 1.f, 1.f);
         bool specular = true;
         const bdpt_lightpath& v = lp[vlp & (BDPT_LIGHT_POINTS - 1)];
         for (unsigned depth = 0; depth <= 6; ++depth) {
-            const unsigned j = (base + depth * 5u + sid) % (kRandN - 5u);
+            const unsigned j = eye_rand_index((unsigned)(y * W + x), depth, sid);
             float t;
             unsigned id = 0;
-            if (!sc.closest(o, d, &t, &id)) break;
+            if (!sc.closest(r.o, r.d, &t, &id)) break;
             const bdpt_sphere& S = sc.s[id];
-            const V3 h = o + t * d;
-            const V3 normal = unit(h - of(S.p));
-            const float dp = dot(normal, d);
-            const V3 nl = (-1.f * (float)(dp > 0 ? 1 : -1)) * normal;
+            const eye_vertex p = eye_vertex_at(r.o, r.d, t, of(S.p));
             if (sc.emissive[id]) {                                   // :651-661
-                if (specular) rad = rad + thr * (fabsf(dp) * of(S.e));
+                if (specular) rad = rad + thr * (fabsf(p.dp) * of(S.e));
                 break;
             }
-            if (S.refl == BDPT_DIFF) {                               // :663-703
-                specular = false;
+            r.o = p.hit;
+            specular = S.refl != BDPT_DIFF;
+            if (!specular) {                                         // :663-703
+                const f3 nl = eye_nl(p.normal, p.dp);
                 thr = thr * of(S.c);
-                rad = rad + lights(h, nl, j, v) * thr;
-                o = h;
-                d = cosine_dir(nl, rnd[j], rnd[j + 1]);
+                rad = rad + lights(p.hit, nl, j, v) * thr;
+                r.d = cosine_dir(nl, rnd[j], rnd[j + 1]);
                 continue;
             }
-            specular = true;
-            const V3 refl = d - (2.f * dot(normal, d)) * normal;
-            if (S.refl == BDPT_SPEC) {                               // :704-714
-                thr = thr * of(S.c);
-                o = h; d = refl;
-                continue;
-            }
-            const bool into = dot(normal, nl) > 0;                   // REFR / LITE :715-770
-            const float nc = 1.f, nt = 1.5f, nnt = into ? nc / nt : nt / nc;
-            const float ddn = dot(d, nl);
-            const float cos2t = 1.f - nnt * nnt * (1.f - ddn * ddn);
-            if (cos2t < 0.f) {
-                thr = thr * of(S.c);
-                o = h; d = refl;
-                continue;
-            }
-            const float kq = (float)(into ? 1 : -1) * (ddn * nnt + sqrtf(cos2t));
-            const V3 td = unit(nnt * d - kq * normal);
-            const float a = nt - nc, b = nt + nc, R0 = a * a / (b * b);
-            const float cc = 1 - (into ? -ddn : dot(td, normal));
-            const float Re = R0 + (1 - R0) * cc * cc * cc * cc * cc, Tr = 1.f - Re, P = .25f + .5f * Re;
-            if (rnd[j + 2] < P) {
-                thr = (Re / P) * thr * of(S.c);
-                d = refl;
-            } else {
-                thr = (Tr / (1.f - P)) * thr * of(S.c);
-                d = td;
-            }
-            o = h;
+            eye_specular(S.refl == BDPT_SPEC, p.normal, p.dp, of(S.c), [&](float P) { return rnd[j + 2] < P; }, r.d,
+                         thr);
         }
         return rad;
     }
 
     // The eye path of sample() up to its first non-specular vertex (include/bdpt.h bdpt_render_chain):
-    // the same vertex arithmetic, stopped at the first emitter, diffuse surface or miss.  pass: glass
-    // takes pass sid's choice (rnd[j + 2] < P), else it transmits whenever refraction exists.
+    // the same vertices, stopped at the first emitter, diffuse surface or miss.  pass: glass takes
+    // pass sid's choice (rnd[j + 2] < P), else it transmits whenever refraction exists.
     struct Chain {
         int id = -1, first_id = -1, kind = BDPT_CHAIN_KIND_EXHAUSTED, bounces = 0;
         float t = 0.f, dp = 0.f;
-        V3 pos = v3(0.f, 0.f, 0.f), nrm = v3(0.f, 0.f, 0.f), dir, thr = v3(1.f, 1.f, 1.f);
+        f3 pos = mk(0.f, 0.f, 0.f), nrm = mk(0.f, 0.f, 0.f), dir, thr = mk(1.f, 1.f, 1.f);
     };
     Chain chain(int x, int y, int W, bool jitter, unsigned sid, bool pass) const {
-        const unsigned base = 26u + (unsigned)(y * W + x) * 25u;
-        float u0 = 0.f, u1 = 0.f;                                // no jitter: both randoms +0
-        if (jitter) {
-            const unsigned kk = (base + sid) % (kRandN - 5u);
-            u0 = rnd[kk];
-            u1 = rnd[kk + 1];
-        }
-        V3 o, d;
-        camera_ray(x, y, u0, u1, &o, &d);
-        Chain r;
-        float len = 0.f, dp = 0.f;
-        V3 h = r.pos, normal = r.nrm;
+        eye_ray r = camera_ray(x, y, W, jitter, sid);
+        Chain c;
+        float len = 0.f;                                     // sums in locals, the result assembled after
+        eye_vertex p = {c.pos, c.nrm, c.dp};                 // the loop: the shape that was timed
         for (unsigned depth = 0; depth <= 6; ++depth) {
             float t;
             unsigned id = 0;
-            const bool hit = sc.closest(o, d, &t, &id);
-            if (depth == 0) r.first_id = hit ? (int)id : -1;
+            const bool hit = sc.closest(r.o, r.d, &t, &id);
+            if (depth == 0) c.first_id = hit ? (int)id : -1;
             if (!hit) {
-                r.kind = BDPT_CHAIN_KIND_MISS;
+                c.kind = BDPT_CHAIN_KIND_MISS;
                 break;
             }
             const bdpt_sphere& S = sc.s[id];
             len = len + t;
-            h = o + t * d;
-            normal = unit(h - of(S.p));
-            dp = dot(normal, d);
-            const V3 nl = (-1.f * (float)(dp > 0 ? 1 : -1)) * normal;
+            p = eye_vertex_at(r.o, r.d, t, of(S.p));
             if (sc.emissive[id]) {                                   // :651, before the material
-                r.kind = BDPT_CHAIN_KIND_EMITTER;
-                r.id = (int)id;
+                c.kind = BDPT_CHAIN_KIND_EMITTER;
+                c.id = (int)id;
                 break;
             }
             if (S.refl == BDPT_DIFF) {
-                r.kind = BDPT_CHAIN_KIND_DIFFUSE;
-                r.id = (int)id;
+                c.kind = BDPT_CHAIN_KIND_DIFFUSE;
+                c.id = (int)id;
                 break;
             }
-            r.bounces++;
-            const V3 refl = d - (2.f * dot(normal, d)) * normal;
-            o = h;
-            if (S.refl == BDPT_SPEC) {                               // :704-714
-                r.thr = r.thr * of(S.c);
-                d = refl;
-                continue;
-            }
-            const bool into = dot(normal, nl) > 0;                   // REFR / LITE :715-770
-            const float nc = 1.f, nt = 1.5f, nnt = into ? nc / nt : nt / nc;
-            const float ddn = dot(d, nl);
-            const float cos2t = 1.f - nnt * nnt * (1.f - ddn * ddn);
-            if (cos2t < 0.f) {
-                r.thr = r.thr * of(S.c);
-                d = refl;
-                continue;
-            }
-            const float kq = (float)(into ? 1 : -1) * (ddn * nnt + sqrtf(cos2t));
-            const V3 td = unit(nnt * d - kq * normal);
-            const float a = nt - nc, b = nt + nc, R0 = a * a / (b * b);
-            const float cc = 1 - (into ? -ddn : dot(td, normal));
-            const float Re = R0 + (1 - R0) * cc * cc * cc * cc * cc, Tr = 1.f - Re, P = .25f + .5f * Re;
-            if (pass && rnd[(base + depth * 5u + sid) % (kRandN - 5u) + 2] < P) {
-                r.thr = (Re / P) * r.thr * of(S.c);
-                d = refl;
-            } else {
-                r.thr = (Tr / (1.f - P)) * r.thr * of(S.c);
-                d = td;
-            }
+            c.bounces++;
+            r.o = p.hit;
+            eye_specular(S.refl == BDPT_SPEC, p.normal, p.dp, of(S.c), [&](float P) {
+                return pass && rnd[eye_rand_index((unsigned)(y * W + x), depth, sid) + 2] < P;
+            }, r.d, c.thr);
         }
-        r.t = len;
-        r.dir = d;
-        if (r.kind == BDPT_CHAIN_KIND_DIFFUSE || r.kind == BDPT_CHAIN_KIND_EMITTER) {
-            r.dp = dp; r.pos = h; r.nrm = normal;
+        c.t = len;
+        c.dir = r.d;
+        if (c.kind == BDPT_CHAIN_KIND_DIFFUSE || c.kind == BDPT_CHAIN_KIND_EMITTER) {
+            c.dp = p.dp; c.pos = p.hit; c.nrm = p.normal;
         }
-        return r;
+        return c;
     }
 };
 }  // namespace
@@ -544,7 +456,7 @@ void bdpt_cpu_path_passes(bdpt_cpu_ctx* c, const unsigned* sid, const int* vlp, 
             unsigned cnt = c->counter[i];
             const unsigned cnt0 = cnt;
             for (int p = 0; p < npass && cnt < BDPT_COUNTER_CAP; p++, cnt++) {
-                const V3 r = pt.sample(x, y, W, sid[p], vlp[p]);
+                const f3 r = pt.sample(x, y, W, sid[p], vlp[p]);
                 if (cnt == 0) {
                     col = {r.x, r.y, r.z};
                 } else {
@@ -567,42 +479,33 @@ void bdpt_cpu_path_passes(bdpt_cpu_ctx* c, const unsigned* sid, const int* vlp, 
 }
 
 // First-hit feature buffers (include/bdpt.h bdpt_render_aov): the first segment of the eye path of
-// sample() above on its own -- the camera ray (device.cu:562-600), IntersectDevice (:106-124) and
-// hitPoint / normal / dp (:635-643) -- for the window's pixels, packed [h][w].  The caller has
-// checked the window, the camera and (jitter) the table.
+// sample() on its own -- bdpt_eye.h's camera ray, IntersectDevice (:106-124) and bdpt_eye.h's vertex
+// -- for the window's pixels, packed [h][w].  The caller has checked the window, the camera and
+// (jitter) the table.
 static void render_aov_cam(const bdpt_cpu_ctx* c, const bdpt_camera& cam, int x0, int y0, int w, int h, int jitter,
                            unsigned sid, const bdpt_aov_buffers* out) {
     const PathTracer pt(c, cam);
     const int W = c->W;
     parallel_rows(y0, y0 + h, c->threads, [&](int y) {
         for (int x = x0; x < x0 + w; x++) {
-            float u0 = 0.f, u1 = 0.f;                              // no jitter: both randoms +0
-            if (jitter) {
-                const unsigned kk = (26u + (unsigned)(y * W + x) * 25u + sid) % (kRandN - 5u);   // :562
-                u0 = pt.rnd[kk];
-                u1 = pt.rnd[kk + 1];
-            }
-            V3 o, d;
-            pt.camera_ray(x, y, u0, u1, &o, &d);
-            float t = 0.f, dp = 0.f;
+            const eye_ray r = pt.camera_ray(x, y, W, jitter != 0, sid);
+            float t = 0.f;
             unsigned s = 0;
             int id = -1;
-            V3 hp = v3(0.f, 0.f, 0.f), nrm = hp;
-            if (pt.sc.closest(o, d, &t, &s)) {
+            eye_vertex p = {mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f), 0.f};      // a miss: +0 everywhere but dir
+            if (pt.sc.closest(r.o, r.d, &t, &s)) {
                 id = (int)s;
-                hp = o + t * d;
-                nrm = unit(hp - of(pt.sc.s[s].p));
-                dp = dot(nrm, d);
+                p = eye_vertex_at(r.o, r.d, t, of(pt.sc.s[s].p));
             } else {
                 t = 0.f;
             }
             const size_t k = (size_t)(y - y0) * w + (x - x0);
             if (out->id) out->id[k] = id;
             if (out->t) out->t[k] = t;
-            if (out->dp) out->dp[k] = dp;
-            if (out->position) out->position[k] = {hp.x, hp.y, hp.z};
-            if (out->normal) out->normal[k] = {nrm.x, nrm.y, nrm.z};
-            if (out->dir) out->dir[k] = {d.x, d.y, d.z};
+            if (out->dp) out->dp[k] = p.dp;
+            if (out->position) out->position[k] = to_vec(p.hit);
+            if (out->normal) out->normal[k] = to_vec(p.normal);
+            if (out->dir) out->dir[k] = to_vec(r.d);
         }
     });
 }
@@ -678,12 +581,8 @@ struct FirstHit {
         g.normal = nrm.data();
         bdpt_cpu_render_chain(c, 0, 0, c->W, c->H, 0, 0u, BDPT_CHAIN_TRANSMIT, &g);
         const int n = (int)c->scene.n;
-        for (size_t i = 0; i < np; i++) {
-            int key = -1;
-            if (kind[i] == BDPT_CHAIN_KIND_DIFFUSE)
-                key = bounces[i] == 0 ? id[i] : n + ((bounces[i] - 1) * n + first[i]) * n + id[i];
-            id[i] = key;
-        }
+        for (size_t i = 0; i < np; i++)
+            id[i] = through_key(kind[i] == BDPT_CHAIN_KIND_DIFFUSE, n, bounces[i], first[i], id[i]);
     }
 };
 
@@ -710,13 +609,13 @@ void atrous_levels(const bdpt_cpu_ctx* c, const FirstHit& g, int levels, int nor
         parallel_rows(0, H, c->threads, [&](int y) {
             for (int x = 0; x < W; x++) {
                 const size_t i = (size_t)y * W + x;
-                const f3 c_p = of3(cur[i]);
+                const f3 c_p = of(cur[i]);
                 float a_p = 0.f;
                 if constexpr (MODE != kLvPlain) a_p = acur[i];
                 f3 o = c_p;
                 float a = a_p;
                 if (g.id[i] >= 0) {
-                    const f3 n_p = of3(g.nrm[i]);
+                    const f3 n_p = of(g.nrm[i]);
                     float su = 0.f, sw = 0.f;
                     f3 sc = mk(0.f, 0.f, 0.f);
                     bool used = false;
@@ -730,8 +629,8 @@ void atrous_levels(const bdpt_cpu_ctx* c, const FirstHit& g, int levels, int nor
                             if (g.id[q] != g.id[i]) continue;
                             float a_q = 0.f;
                             if constexpr (MODE != kLvPlain) a_q = acur[q];
-                            lv_tap<MODE>(b3_weight(j, t), normal_power, isc, kk, n_p, c_p, a_p, of3(g.nrm[q]),
-                                         of3(cur[q]), a_q, su, sw, sc, used);
+                            lv_tap<MODE>(b3_weight(j, t), normal_power, isc, kk, n_p, c_p, a_p, of(g.nrm[q]),
+                                         of(cur[q]), a_q, su, sw, sc, used);
                         }
                     }
                     o = lv_finish<MODE>(used, c_p, a_p, su, sw, sc, a);
@@ -827,11 +726,10 @@ void reproject_frame(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, cons
     const bool present = state == BDPT_HISTORY_SAME || (c->follow && state == BDPT_HISTORY_MOVED);
     if (state != BDPT_HISTORY_MOVED) delta.clear();
     const bool all_materials = p->materials == BDPT_DENOISE_ALL;
-    const bdpt_camera& c0 = c->hcam;
-    const f3 ux = of3(unit(of(c0.x))), uy = of3(unit(of(c0.y))), ud = of3(unit(of(c0.dir))), o = of3(c0.orig);
-    const float inv_w = (float)(14. / W), inv_h = (float)(10.5 / H);
-    const float hw = (float)((double)(inv_w * (float)W) / 2.), hh = (float)((double)(inv_h * (float)H) / 2.);
-    const float sx = 1.f / inv_w, sy = 1.f / inv_h;
+    const eye_camera c0 = eye_camera_terms(c->hcam, W, H);
+    const f3 ux = c0.ux, uy = c0.uy, ud = c0.ud, o = c0.orig;
+    const float hw = (float)c0.half_w, hh = (float)c0.half_h;
+    const float sx = 1.f / c0.inv_w, sy = 1.f / c0.inv_h;
     parallel_rows(0, H, c->threads, [&](int y) {
         for (int x = 0; x < W; x++) {
             const size_t i = (size_t)y * W + x;
@@ -839,8 +737,8 @@ void reproject_frame(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, cons
             float m = 0.f;
             f3 h = mk(0.f, 0.f, 0.f);
             if (present && guide_id(id1, all_materials, c->scene.s.data()) >= 0) {
-                const f3 N = of3(f.nrm[i]);
-                const f3 P = delta.empty() ? of3(f.pos[i]) : rp_follow(of3(f.pos[i]), of3(delta[id1]));
+                const f3 N = of(f.nrm[i]);
+                const f3 P = delta.empty() ? of(f.pos[i]) : rp_follow(of(f.pos[i]), of(delta[id1]));
                 float fx, fy;
                 if (rp_project(P, o, ux, uy, ud, hw, hh, sx, sy, W, H, fx, fy)) {
                     const float xf = floorf(fx), yf = floorf(fy);
@@ -854,13 +752,13 @@ void reproject_frame(const bdpt_cpu_ctx* c, const bdpt_reproject_params* p, cons
                         const int qx = qx0 + (k & 1), qy = qy0 + (k >> 1);
                         const bool in = qx >= 0 && qx < W && qy >= 0 && qy < H;
                         const size_t q = in ? (size_t)qy * W + qx : i;   // outside: the pixel's own, not used
-                        rp_tap(k, wx, wy, in, c->gid[q], of3(c->gpos[q]), of3(c->hc[q]), c->hm[q], id1, P, N, lim,
+                        rp_tap(k, wx, wy, in, c->gid[q], of(c->gpos[q]), of(c->hc[q]), c->hm[q], id1, P, N, lim,
                                p->max_history, sw, sm, sc, used);
                     }
                     rp_history(used, sw, sm, sc, h, m);
                 }
             }
-            out[i] = to_vec(rp_blend(of3(c->colors[i]), (float)c->counter[i], h, m, wout[i]));
+            out[i] = to_vec(rp_blend(of(c->colors[i]), (float)c->counter[i], h, m, wout[i]));
         }
     });
 }
@@ -994,7 +892,7 @@ void bdpt_cpu_noise_estimate(bdpt_cpu_ctx* c, const bdpt_noise_params* p, float*
                 const unsigned cnt = c->counter[i], mn = stored ? c->mark[i].n : 0u;
                 float e = -1.0f;
                 if (mark_valid(cnt, mn)) {
-                    e = pixel_error(of3(B), of3(c->mark[i].c), cnt, mn, p->dark);
+                    e = pixel_error(of(B), of(c->mark[i].c), cnt, mn, p->dark);
                     v[k] = e;
                     valid++;
                 } else if (mark_growing(cnt)) {
@@ -1031,7 +929,7 @@ void bdpt_cpu_denoise_noise(const bdpt_cpu_ctx* c, const bdpt_denoise_noise_para
     std::vector<float> v0(np, -1.0f), var(np);
     for (size_t i = 0; i < np; i++) {                     // the raw variance
         const unsigned cnt = c->counter[i], mn = stored ? c->mark[i].n : 0u;
-        if (mark_valid(cnt, mn)) v0[i] = raw_variance(of3(c->colors[i]), of3(c->mark[i].c), cnt, mn);
+        if (mark_valid(cnt, mn)) v0[i] = raw_variance(of(c->colors[i]), of(c->mark[i].c), cnt, mn);
     }
     parallel_rows(0, H, c->threads, [&](int y) {          // the prefilter
         for (int x = 0; x < W; x++) {

@@ -8,55 +8,18 @@
 // (-ffp-contract=off), dot() as (x*x' + y*y') + z*z', every reciprocal, division and root correctly
 // rounded, denormals kept.  A tap that is not used adds nothing: it is skipped, not weighted by 0.
 //
-// The one place with two definitions is the block below: what a translation unit brings with it.
-// A kernel file says so by defining BDPT_FILTER_KERNELS before the include: it has bdpt_device.h
-// and bdpt_leaf.h first, so f3 and its operations, the BDPT_DEV_* constants and the fast correctly
-// rounded sequences exist, in its device pass and in its host pass alike (which is why the choice
-// cannot be __HIP_DEVICE_COMPILE__ alone: the host pass of a kernel file would define f3 twice, and
-// hipcc compiles bdpt_cpu.cpp with a device pass that has none of these).  Host code (after
-// <math.h> and include/bdpt.h; hipcc or g++) gets the same names here, with 1.f / x and sqrtf
-// (equal bits: tests/native/hw_exact_check.hip).  Everything is inlined on both sides.
+// What a translation unit brings with it (f3 and its operations, the constants, the reciprocals
+// and the root) is bdpt_sides.h's, the one block with two definitions.
 #pragma once
+#include "bdpt_sides.h"
 
 namespace {
-
-#if defined(BDPT_FILTER_KERNELS)
-#define BDPT_FLT __device__ __forceinline__
-constexpr int kFltDiff = BDPT_DEV_DIFF;
-constexpr unsigned kFltCounterCap = BDPT_DEV_COUNTER_CAP;
-constexpr float kFltNoiseEps = BDPT_DEV_DNOISE_EPS;
-BDPT_FLT float flt_rcp(float x) { return rcp_rn(x); }
-// x in [2^-125, 2^125) proven by the caller
-BDPT_FLT float flt_rcp_inrange(float x) { return rcp_rn_inrange(x); }
-// x >= 1 or NaN (1 + a product that is non-negative or NaN): one compare decides between the
-// in-range sequence and the library division (+inf, NaN, >= 2^125)
-BDPT_FLT float flt_rcp_ge1(float x) {
-    if (__builtin_expect(!(x < 0x1p125f), 0)) return 1.f / x;
-    return rcp_rn_inrange(x);
-}
-BDPT_FLT float flt_sqrt(float x) { return bdpt_sqrt_rn(x); }
-#else
-#define BDPT_FLT static inline __attribute__((always_inline))
-constexpr int kFltDiff = BDPT_DIFF;
-constexpr unsigned kFltCounterCap = BDPT_COUNTER_CAP;
-constexpr float kFltNoiseEps = BDPT_DENOISE_NOISE_EPS;
-struct f3 { float x, y, z; };
-BDPT_FLT f3 mk(float a, float b, float c) { f3 v; v.x = a; v.y = b; v.z = c; return v; }
-BDPT_FLT f3 add(f3 a, f3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
-BDPT_FLT f3 sub(f3 a, f3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-BDPT_FLT f3 smul(float k, f3 b) { return mk(k * b.x, k * b.y, k * b.z); }
-BDPT_FLT float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-BDPT_FLT float flt_rcp(float x) { return 1.f / x; }
-BDPT_FLT float flt_rcp_inrange(float x) { return 1.f / x; }
-BDPT_FLT float flt_rcp_ge1(float x) { return 1.f / x; }
-BDPT_FLT float flt_sqrt(float x) { return sqrtf(x); }
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // Small constants and rules
 
 // the 5 x 5 B3-spline weight of tap (j, t): h[j] * h[t], an exact constant
-BDPT_FLT float b3_weight(int j, int t) {
+BDPT_BOTH float b3_weight(int j, int t) {
     constexpr float hk[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
     return hk[j] * hk[t];
 }
@@ -65,14 +28,22 @@ BDPT_FLT float b3_weight(int j, int t) {
 // miss; unless all_materials, any sphere that is not DIFF).  Eligibility is a function of the
 // sphere, so "same sphere as an eligible centre" implies an eligible tap.
 template <class Sphere>
-BDPT_FLT int guide_id(int id, bool all_materials, const Sphere* sph) {
+BDPT_BOTH int guide_id(int id, bool all_materials, const Sphere* sph) {
     int g = id;
     if (g >= 0 && !all_materials && sph[g].refl != kFltDiff) g = -1;
     return g;
 }
+// The guide key of a pixel whose unjittered TRANSMIT chain ends on a diffuse surface (include/bdpt.h
+// BDPT_DENOISE_THROUGH; -1: it does not): the end sphere itself after no bounce, else a key of the
+// bounce count, the first sphere and the end sphere, above the n sphere ids.  The caller has checked
+// that 6 n^2 + n fits an int.
+BDPT_BOTH int through_key(bool diffuse, int n, int bounces, int first_id, int id) {
+    if (!diffuse) return -1;
+    return bounces == 0 ? id : n + ((bounces - 1) * n + first_id) * n + id;
+}
 
 // clampc of bdpt_preview_denoise: a record's count, 0 or inside [2^-20, 2^40]
-BDPT_FLT float clampc(float w) { return w == 0.f ? 0.f : fminf(fmaxf(w, 0x1p-20f), 0x1p40f); }
+BDPT_BOTH float clampc(float w) { return w == 0.f ? 0.f : fminf(fmaxf(w, 0x1p-20f), 0x1p40f); }
 
 // ---------------------------------------------------------------------------------------------
 // The a-trous level of the three filters: taps and finishes.  What a pixel carries next to its
@@ -81,20 +52,20 @@ BDPT_FLT float clampc(float w) { return w == 0.f ? 0.f : fminf(fmaxf(w, 0x1p-20f
 constexpr int kLvPlain = 0, kLvCounts = 1, kLvNoise = 2;
 
 // the normal weight of a tap: the cosine, clamped at 0, squared np = normal_power times
-BDPT_FLT float tap_wn(f3 n_p, f3 n_q, int np) {
+BDPT_BOTH float tap_wn(f3 n_p, f3 n_q, int np) {
     const float d = dot(n_p, n_q);
     float wn = d > 0.f ? d : 0.f;
     for (int r = 0; r < np; r++) wn = wn * wn;
     return wn;
 }
 
-BDPT_FLT float tap_e2(f3 c_p, f3 q) {
+BDPT_BOTH float tap_e2(f3 c_p, f3 q) {
     const f3 dc = sub(q, c_p);
     return dot(dc, dc);
 }
 
 // one used tap of bdpt_denoise: hw = b3_weight(j, t), q the tap's colour
-BDPT_FLT void dn_tap(float hw, int np, float isc, f3 n_p, f3 c_p, f3 n_q, f3 q, float& sw, f3& sc) {
+BDPT_BOTH void dn_tap(float hw, int np, float isc, f3 n_p, f3 c_p, f3 n_q, f3 q, float& sw, f3& sc) {
     const float wn = tap_wn(n_p, n_q, np);
     const float e2 = tap_e2(c_p, q);
     const float wc = flt_rcp_ge1(1.f + e2 * isc);        // e2 >= 0 and isc >= 0, or their product is NaN
@@ -105,7 +76,7 @@ BDPT_FLT void dn_tap(float hw, int np, float isc, f3 n_p, f3 c_p, f3 n_q, f3 q, 
 
 // one used tap with counts (a_q > 0); a centre without a count (a_p == 0) stops nothing: wc = 1.f.
 // a_p + a_q lies in [2^-20, 2^41] (clampc), inside the fast reciprocal's range
-BDPT_FLT void pv_tap(float hw, int np, float isc, float c2, f3 n_p, f3 c_p, float a_p, f3 n_q, f3 q, float a_q,
+BDPT_BOTH void pv_tap(float hw, int np, float isc, float c2, f3 n_p, f3 c_p, float a_p, f3 n_q, f3 q, float a_q,
                      float& su, float& sw, f3& sc) {
     const float wn = tap_wn(n_p, n_q, np);
     const float e2 = tap_e2(c_p, q);
@@ -123,7 +94,7 @@ BDPT_FLT void pv_tap(float hw, int np, float isc, float c2, f3 n_p, f3 c_p, floa
 
 // one used tap of bdpt_denoise_noise: the colour stop from the two variances where both pixels
 // have one (v < 0: none), else the denoiser's; the centre's variance is carried as sum w^2 v
-BDPT_FLT void nz_tap(float hw, int np, float isc, float s2, f3 n_p, f3 c_p, float v_p, f3 n_q, f3 q, float v_q,
+BDPT_BOTH void nz_tap(float hw, int np, float isc, float s2, f3 n_p, f3 c_p, float v_p, f3 n_q, f3 q, float v_q,
                      float& sv, float& sw, f3& sc) {
     const float wn = tap_wn(n_p, n_q, np);
     const float e2 = tap_e2(c_p, q);
@@ -145,7 +116,7 @@ BDPT_FLT void nz_tap(float hw, int np, float isc, float s2, f3 n_p, f3 c_p, floa
 // tap's count or variance; k: c2 = 2 / count_ref (counts) or s2 = noise_sigma^2 (noise); su: the
 // second sum (counts: of u; noise: of w^2 v); used (counts): the tap had a count.
 template <int MODE>
-BDPT_FLT void lv_tap(float hw, int np, float isc, float k, f3 n_p, f3 c_p, float a_p, f3 n_q, f3 q, float a_q,
+BDPT_BOTH void lv_tap(float hw, int np, float isc, float k, f3 n_p, f3 c_p, float a_p, f3 n_q, f3 q, float a_q,
                      float& su, float& sw, f3& sc, bool& used) {
     if constexpr (MODE == kLvCounts) {
         if (!(a_q > 0.f)) return;
@@ -162,7 +133,7 @@ BDPT_FLT void lv_tap(float hw, int np, float isc, float k, f3 n_p, f3 c_p, float
 // the centre is copied through, else the count is clampc(sw / su).  Noise: the variance of the
 // weighted mean, (sum w^2 v) / (sum w)^2 as (su * r) * r, where the centre had one.
 template <int MODE>
-BDPT_FLT f3 lv_finish(bool used, f3 c_p, float a_p, float su, float sw, f3 sc, float& a) {
+BDPT_BOTH f3 lv_finish(bool used, f3 c_p, float a_p, float su, float sw, f3 sc, float& a) {
     if constexpr (MODE == kLvCounts) {
         if (!used) {
             a = a_p;
@@ -184,35 +155,35 @@ BDPT_FLT f3 lv_finish(bool used, f3 c_p, float a_p, float su, float sw, f3 sc, f
 // ---------------------------------------------------------------------------------------------
 // The variance prefilter of bdpt_denoise_noise: one tap inside the frame (used where it shows the
 // centre's sphere and has a variance), and the centre's result
-BDPT_FLT void pf_tap(float hw, bool same_sphere, float v_q, float& sv, float& sh, bool& used) {
+BDPT_BOTH void pf_tap(float hw, bool same_sphere, float v_q, float& sv, float& sh, bool& used) {
     if (!same_sphere || v_q < 0.f) return;
     sv = sv + hw * v_q;
     sh = sh + hw;
     used = true;
 }
-BDPT_FLT float pf_finish(bool used, float sv, float sh) { return used ? sv / sh : -1.0f; }
+BDPT_BOTH float pf_finish(bool used, float sv, float sh) { return used ? sv / sh : -1.0f; }
 
 // ---------------------------------------------------------------------------------------------
 // The mark of bdpt_noise_estimate: a pixel's colour A at count mn, against its colour B at cnt now
 
 // the mark is usable: mn > 0, cnt > mn and 2 * (cnt - mn) >= mn, the last as
 // cnt - mn >= ceil(mn / 2) so that 32 bits cannot wrap
-BDPT_FLT bool mark_valid(unsigned cnt, unsigned mn) {
+BDPT_BOTH bool mark_valid(unsigned cnt, unsigned mn) {
     return mn > 0u && cnt > mn && cnt - mn >= (mn >> 1) + (mn & 1u);
 }
-BDPT_FLT bool mark_growing(unsigned cnt) { return cnt > 0u && cnt < kFltCounterCap; }
+BDPT_BOTH bool mark_growing(unsigned cnt) { return cnt > 0u && cnt < kFltCounterCap; }
 // a re-marking call takes the pixel: it still grows and cnt >= 2 * mn, as (cnt >> 1) >= mn
-BDPT_FLT bool mark_take(unsigned cnt, unsigned mn) { return mark_growing(cnt) && (cnt >> 1) >= mn; }
+BDPT_BOTH bool mark_take(unsigned cnt, unsigned mn) { return mark_growing(cnt) && (cnt >> 1) >= mn; }
 
 // the raw variance v0 of a pixel with a valid mark (bdpt_denoise_noise)
-BDPT_FLT float raw_variance(f3 B, f3 A, unsigned cnt, unsigned mn) {
+BDPT_BOTH float raw_variance(f3 B, f3 A, unsigned cnt, unsigned mn) {
     const f3 d = sub(B, A);
     const float a = (float)mn, n = (float)cnt;
     return dot(d, d) * (a / (n - a));
 }
 
 // the per-pixel error of a pixel with a valid mark (bdpt_noise_estimate)
-BDPT_FLT float pixel_error(f3 B, f3 A, unsigned cnt, unsigned mn, float dark) {
+BDPT_BOTH float pixel_error(f3 B, f3 A, unsigned cnt, unsigned mn, float dark) {
     const float a = (float)mn, n = (float)cnt;
     const float dx = B.x - A.x, dy = B.y - A.y, dz = B.z - A.z;
     const float e1 = (fabsf(dx) + fabsf(dy)) + fabsf(dz);
@@ -229,7 +200,7 @@ BDPT_FLT float pixel_error(f3 B, f3 A, unsigned cnt, unsigned mn, float dark) {
 // The first-hit point P in the history's camera (origin o, unit axes ux, uy, ud; hw, hh the film's
 // half extent, sx, sy pixels per film unit): its continuous pixel position, and whether the four
 // taps around it can touch the frame (a NaN fails).  cz = 0 takes the library division.
-BDPT_FLT bool rp_project(f3 P, f3 o, f3 ux, f3 uy, f3 ud, float hw, float hh, float sx, float sy, int W, int H,
+BDPT_BOTH bool rp_project(f3 P, f3 o, f3 ux, f3 uy, f3 ud, float hw, float hh, float sx, float sy, int W, int H,
                          float& fx, float& fy) {
     const f3 d = sub(P, o);
     const float a = dot(d, ux);
@@ -245,13 +216,13 @@ BDPT_FLT bool rp_project(f3 P, f3 o, f3 ux, f3 uy, f3 ud, float hw, float hh, fl
 // "Follow" (bdpt_history_follow): the first-hit point where its sphere was when the history was
 // taken, P' = P - delta[id1].  It replaces P in rp_project and in rp_tap's plane test and nowhere
 // else.  x - (+0) == x for every x, -0 included, so an unmoved sphere's pixel keeps P's bits.
-BDPT_FLT f3 rp_follow(f3 P, f3 delta) { return sub(P, delta); }
+BDPT_BOTH f3 rp_follow(f3 P, f3 delta) { return sub(P, delta); }
 
 // Bilinear tap k (dx = k & 1, dy = k >> 1; dy outer, dx inner, as defined) with the fractions
 // (wx, wy).  in: the tap is inside the frame; where it is not, the caller passes any record.  The
 // tap counts where its weight is positive, it shows the pixel's sphere id1, has a count m_q > 0
 // and its point p_q lies within lim of the plane (P, N).
-BDPT_FLT void rp_tap(int k, float wx, float wy, bool in, int id_q, f3 p_q, f3 c_q, float m_q, int id1, f3 P, f3 N,
+BDPT_BOTH void rp_tap(int k, float wx, float wy, bool in, int id_q, f3 p_q, f3 c_q, float m_q, int id1, f3 P, f3 N,
                      float lim, float max_history, float& sw, float& sm, f3& sc, bool& used) {
     const float bx = (k & 1) ? wx : 1.f - wx, by = (k >> 1) ? wy : 1.f - wy;
     const float bw = bx * by;
@@ -264,7 +235,7 @@ BDPT_FLT void rp_tap(int k, float wx, float wy, bool in, int id_q, f3 p_q, f3 c_
 }
 
 // the history (h, m) from the taps' sums; a denormal sw takes the library division
-BDPT_FLT void rp_history(bool used, float sw, float sm, f3 sc, f3& h, float& m) {
+BDPT_BOTH void rp_history(bool used, float sw, float sm, f3 sc, f3& h, float& m) {
     if (used) {
         h = smul(flt_rcp(sw), sc);
         m = sm;
@@ -272,7 +243,7 @@ BDPT_FLT void rp_history(bool used, float sw, float sm, f3 sc, f3& h, float& m) 
 }
 
 // the blend of the frame's (c, n) with the history's (h, m); tot = n + m
-BDPT_FLT f3 rp_blend(f3 c, float n, f3 h, float m, float& tot) {
+BDPT_BOTH f3 rp_blend(f3 c, float n, f3 h, float m, float& tot) {
     tot = n + m;
     f3 o = c;
     if (m == 0.f) {
@@ -285,6 +256,6 @@ BDPT_FLT f3 rp_blend(f3 c, float n, f3 h, float m, float& tot) {
     return o;
 }
 
-#undef BDPT_FLT
-
 }  // namespace
+
+#undef BDPT_BOTH

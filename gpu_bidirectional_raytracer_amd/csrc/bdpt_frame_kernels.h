@@ -1,14 +1,12 @@
 // bdpt_frame_kernels.h -- the kernels of the frame services (bdpt_frame.cpp): denoiser, temporal
 // reprojection, denoised preview and noise estimate.  Part of bdpt_kernels.hip, which includes this
 // file in its precompiled build only (never under BDPT_JIT), after the helpers used here: f3 and
-// its operations, rcp_rn, bdpt_sqrt_rn, bdpt_dev_to_rgba.  bdpt_aov_kernel, whose planes these
-// kernels read, stays there with the path kernel's traversal.
+// its operations, rcp_rn, bdpt_sqrt_rn, bdpt_dev_to_rgba, and bdpt_filter.h on the kernel side.
+// bdpt_aov_kernel, whose planes these kernels read, stays there with the path kernel's traversal.
 //
 // What a pixel or a tap computes is stated once, in bdpt_filter.h, for these kernels and for the
 // CPU backend (bdpt_cpu.cpp); this file is the device's driver of it: tiles, LDS staging, a row's
 // loads batched before its taps, the wave reduction, and the launch tables.
-#define BDPT_FILTER_KERNELS 1    // f3, rcp_rn, bdpt_sqrt_rn and the BDPT_DEV_* constants are in scope
-#include "bdpt_filter.h"
 
 // ---------------------------------------------------------------------------------------------
 // Edge-avoiding wavelet denoiser (include/bdpt.h bdpt_denoise; no reference

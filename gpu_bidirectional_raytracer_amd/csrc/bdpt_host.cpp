@@ -28,6 +28,7 @@
 
 #include "bdpt_ctx.h"
 #include "bdpt_bvh.h"
+#include "bdpt_eye.h"                   // host side: the camera terms
 #include <chrono>
 
 using namespace bdpt_host;
@@ -609,32 +610,17 @@ static int one_light_pass(bdpt_ctx* c, int current_sample) {
     return BDPT_OK;
 }
 
-// camera terms of device.cu:572-592, with the kernel's float operation order
-static void vnorm3(float v[3]) {
-    float l = 1.f / sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    v[0] = l * v[0]; v[1] = l * v[1]; v[2] = l * v[2];
-}
-
 // The frame and camera constants of a launch (the by-value Camera of device.cu:548, as the kernels
-// take it): shared by the path passes and the feature-buffer kernel.
+// take it): shared by the path passes and the frame kernels.  The terms are bdpt_eye.h's, the one
+// statement of them, which the CPU backend uses too.
 extern "C++" void bdpt_host::camera_args(const bdpt_ctx* c, const bdpt_camera& cam, bdpt_path_args& a) {
+    const eye_camera e = eye_camera_terms(cam, c->W, c->H);
+    static_assert(sizeof(f3) == sizeof(a.ux), "f3 is three packed floats");
     a.W = c->W; a.H = c->H;
-    a.inv_w = (float)(14. / c->W);                       // smallpt_cpu.c:411-412
-    a.inv_h = (float)(10.5 / c->H);
-    a.half_w = (double)(a.inv_w * (float)c->W) / 2.;      // device.cu:565 inv_width*width/2.
-    a.half_h = (double)(a.inv_h * (float)c->H) / 2.;
-    float ux[3] = {cam.x.x, cam.x.y, cam.x.z}, uy[3] = {cam.y.x, cam.y.y, cam.y.z};
-    float ud[3] = {cam.dir.x, cam.dir.y, cam.dir.z};
-    vnorm3(ux); vnorm3(uy); vnorm3(ud);
-    float nx[3] = {-1.f * cam.x.x, -1.f * cam.x.y, -1.f * cam.x.z};
-    float ny[3] = {-1.f * cam.y.x, -1.f * cam.y.y, -1.f * cam.y.z};
-    float nd[3] = {-1.f * cam.dir.x, -1.f * cam.dir.y, -1.f * cam.dir.z};
-    vnorm3(nx); vnorm3(ny);                               // :584-590 (no vnorm on -dir, :591)
-    a.tx = nx[0] * cam.orig.x + nx[1] * cam.orig.y + nx[2] * cam.orig.z;
-    a.ty = ny[0] * cam.orig.x + ny[1] * cam.orig.y + ny[2] * cam.orig.z;
-    a.tz = nd[0] * cam.orig.x + nd[1] * cam.orig.y + nd[2] * cam.orig.z;
-    memcpy(a.ux, ux, sizeof(ux)); memcpy(a.uy, uy, sizeof(uy)); memcpy(a.ud, ud, sizeof(ud));
-    a.orig[0] = cam.orig.x; a.orig[1] = cam.orig.y; a.orig[2] = cam.orig.z;
+    a.inv_w = e.inv_w; a.inv_h = e.inv_h; a.half_w = e.half_w; a.half_h = e.half_h;
+    memcpy(a.ux, &e.ux, sizeof(a.ux)); memcpy(a.uy, &e.uy, sizeof(a.uy)); memcpy(a.ud, &e.ud, sizeof(a.ud));
+    memcpy(a.orig, &e.orig, sizeof(a.orig));
+    a.tx = e.tx; a.ty = e.ty; a.tz = e.tz;
 }
 static void camera_args(const bdpt_ctx* c, bdpt_path_args& a) { camera_args(c, c->cam, a); }
 

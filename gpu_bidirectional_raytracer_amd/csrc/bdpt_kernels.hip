@@ -1857,132 +1857,46 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_pixels_kernel(const bdpt_
     pixels[i] = bdpt_dev_to_rgba(c.x, c.y, c.z, thr);
 }
 
-// First-hit feature buffers (include/bdpt.h bdpt_render_aov; no reference counterpart): the first
-// segment of the eye path on its own, one lane per pixel of the window -- the camera ray
-// (device.cu:562-600), the closest hit (:106-124) and hitPoint / normal / dp (:635-643), with the
-// float operations of bdpt_path_kernel_t in its order, so the planes equal what the path kernel
-// forms inside.  Nothing but the six output planes is written.
+// The arithmetic the two frame kernels below and the frame services' kernels share with the CPU
+// backend, stated once: the eye path's vertices (bdpt_eye.h) and the filters (bdpt_filter.h).
+#define BDPT_KERNEL_SIDE 1       // f3, rcp_rn, bdpt_sqrt_rn and the BDPT_DEV_* constants are in scope
+#include "bdpt_eye.h"
+#include "bdpt_filter.h"
+
+// The device's driver of bdpt_eye.h for both frame kernels: a launch's window and camera, and the
+// closest hit.
 //  * Sphere data is wave-uniform: the brute scan and the walls of a BVH scene read {p, rad^2}
 //    through the constant address space at a uniform index (scalar loads, ld_const); only the hit
-//    sphere's centre is a per-lane load.  The tree is read through L1/L2 as in the path kernel.
-//  * Wave tiles (v.rows, bdpt_device.h): 8 x 8 pixels when the BVH is traversed, so that a wave's
+//    sphere's record is a per-lane load.  The tree is read through L1/L2 as in the path kernel.
+//  * Wave tiles (rows, bdpt_device.h): 8 x 8 pixels when the BVH is traversed, so that a wave's
 //    rays walk the same nodes; 64 x 1 for the brute scan, whose loop is branch-free and the same
 //    for every lane -- there a wave's stores are whole contiguous rows of each plane (256 B of a
 //    scalar plane, 768 B of a float3 plane, instead of 8 runs of 32 / 96 B).
 //  * Tiles are anchored at the window's corner; a pixel's values depend on its frame index alone.
-extern "C" __global__ __launch_bounds__(256) void bdpt_aov_kernel(bdpt_path_args a, bdpt_aov_args v) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lx = v.rows ? (int)blockIdx.x * BDPT_AOV_ROW_BTW + lane
-                          : (int)blockIdx.x * BDPT_AOV_BVH_BTW + wave * 8 + (lane & 7);
-    const int ly = v.rows ? (int)blockIdx.y * BDPT_AOV_ROW_BTH + wave
-                          : (int)blockIdx.y * BDPT_AOV_BVH_BTH + (lane >> 3);
-    if (lx >= v.w || ly >= v.h) return;                  // (no cross-lane operation below)
-    const int x = v.x0 + lx, y = v.y0 + ly;
-    const unsigned i = (unsigned)(y * a.W + x);
+namespace {
+__device__ __forceinline__ eye_camera frame_camera(const bdpt_path_args& a) {
+    eye_camera c;
+    c.ux = mk(a.ux[0], a.ux[1], a.ux[2]); c.uy = mk(a.uy[0], a.uy[1], a.uy[2]); c.ud = mk(a.ud[0], a.ud[1], a.ud[2]);
+    c.orig = mk(a.orig[0], a.orig[1], a.orig[2]);
+    c.tx = a.tx; c.ty = a.ty; c.tz = a.tz;
+    c.inv_w = a.inv_w; c.inv_h = a.inv_h; c.half_w = a.half_w; c.half_h = a.half_h;
+    return c;
+}
+// The camera ray of frame pixel (x, y): jittered with pass sid's randoms, or (+0, +0) and a.rnd not read.
+__device__ __forceinline__ eye_ray frame_camera_ray(const bdpt_path_args& a, int x, int y, int jitter, unsigned sid) {
     float u0 = 0.f, u1 = 0.f;
-    if (v.jitter) {
-        const unsigned kk = (26u + i * 25u + v.sid) % (kRandN - 5u);     // kk + 1 <= RAND_N - 5
+    if (jitter) {
+        const unsigned kk = eye_rand_index((unsigned)(y * a.W + x), 0u, sid);
         u0 = a.rnd[kk];
         u1 = a.rnd[kk + 1];
     }
-    // camera ray (:562-600), as the `fresh` branch of the path kernel forms it
-    const float kx = (float)(((double)((float)x * a.inv_w) - a.half_w) + (double)(u0 * a.inv_w));
-    const float ky = (float)(((double)((float)y * a.inv_h) - a.half_h) + (double)(u1 * a.inv_h));
-    f3 rdir = mk(0.f, 0.f, 0.f);
-    rdir = add(rdir, smul(kx, mk(a.ux[0], a.ux[1], a.ux[2])));
-    rdir = add(rdir, smul(ky, mk(a.uy[0], a.uy[1], a.uy[2])));
-    rdir = add(rdir, mk(10.0f * a.ud[0], 10.0f * a.ud[1], 10.0f * a.ud[2]));     // kz * ud
-    const float w = (a.tx * kx + a.ty * ky + a.tz * 10.0f) + 1;
-    rdir = smul(rcp_rn(w), rdir);
-    const f3 ro = add(rdir, mk(a.orig[0], a.orig[1], a.orig[2]));
-    const f3 rd = norm(rdir);
-
-    // closest hit, scanning from the last sphere down (:106-124)
-    float t = 1e20f;
-    int id = -1;
-    if (v.bvh) {
-        // walls by brute force, then the BVH; equal distances go to the higher index, which is
-        // what the reference's downward scan with `d < t` yields
-        for (int q = a.big_n - 1; q >= 0; --q) {
-            const troots h = sphere_roots(ld_const(a.big_geom, q), ro, rd);
-            const float d = h.t1 > kEps ? h.t1 : h.t2;
-            const int s = a.big_ids[q] & kBvhIdMask;
-            if (h.t2 > kEps && (d < t || (d == t && s > id))) { t = d; id = s; }
-        }
-        const bvh_ray br = bvh_setup(a, ro, rd);
-        int node = 0;
-        while (true) {                                   // while-while, as in the path kernel
-            int info = -1;
-            while (node < a.bvh_nn) {
-                const float4 lo = a.bvh_nodes[2 * node], hi = a.bvh_nodes[2 * node + 1];
-                const int inf = __float_as_int(hi.w);
-                const bool in = bvh_box(lo, hi, br, t);
-                node = (in && inf < 0) ? node + 1 : __float_as_int(lo.w);
-                if (in && inf >= 0) { info = inf; break; }
-            }
-            if (info < 0) break;
-            const int first = info & 0xffffff, end = first + (info >> 24);
-            for (int k = first; k < end; k++) {
-                const troots h = sphere_roots(a.bvh_geom[k], ro, rd);
-                const float d = h.t1 > kEps ? h.t1 : h.t2;
-                const int s = a.bvh_ids[k] & kBvhIdMask;
-                if (h.t2 > kEps && (d < t || (d == t && s > id))) { t = d; id = s; }
-            }
-        }
-    } else {
-#pragma unroll 4
-        for (int s = (int)a.n - 1; s >= 0; --s) {
-            const troots q = sphere_roots(ld_const(a.geom, s), ro, rd);
-            const float r = q.t1 > kEps ? q.t1 : q.t2;
-            if (q.t2 > kEps && r < t) { t = r; id = s; }
-        }
-    }
-
-    f3 hit = mk(0.f, 0.f, 0.f), normal = hit;            // a miss: +0 everywhere but dir
-    float dp = 0.f;
-    if (id >= 0) {
-        const float4 pc = a.geom[id];
-        hit = add(ro, smul(t, rd));                      // :635-637
-        normal = norm(sub(hit, mk(pc.x, pc.y, pc.z)));   // :639-641
-        dp = dot(normal, rd);                            // :643
-    } else {
-        t = 0.f;
-    }
-    const size_t o = (size_t)ly * (size_t)v.w + (size_t)lx;
-    v.id[o] = id;
-    v.t[o] = t;
-    v.dp[o] = dp;
-    bdpt_dev_vec ov;
-    ov.x = hit.x; ov.y = hit.y; ov.z = hit.z;
-    v.position[o] = ov;
-    ov.x = normal.x; ov.y = normal.y; ov.z = normal.z;
-    v.normal[o] = ov;
-    ov.x = rd.x; ov.y = rd.y; ov.z = rd.z;
-    v.dir[o] = ov;
-}
-
-// bdpt_aov_kernel's ray and closest hit as functions, for bdpt_chain_kernel's loop: the same operations
-// in the same order (the first-hit kernel above keeps its own text: its code is the measured one).
-namespace {
-// The camera ray (:562-600) of frame pixel (x, y), as the `fresh` branch of the path kernel forms
-// it; u0, u1 are the jitter randoms (+0: the unjittered ray).
-__device__ __forceinline__ void frame_camera_ray(const bdpt_path_args& a, int x, int y, float u0, float u1, f3& ro,
-                                                 f3& rd) {
-    const float kx = (float)(((double)((float)x * a.inv_w) - a.half_w) + (double)(u0 * a.inv_w));
-    const float ky = (float)(((double)((float)y * a.inv_h) - a.half_h) + (double)(u1 * a.inv_h));
-    f3 rdir = mk(0.f, 0.f, 0.f);
-    rdir = add(rdir, smul(kx, mk(a.ux[0], a.ux[1], a.ux[2])));
-    rdir = add(rdir, smul(ky, mk(a.uy[0], a.uy[1], a.uy[2])));
-    rdir = add(rdir, mk(10.0f * a.ud[0], 10.0f * a.ud[1], 10.0f * a.ud[2]));     // kz * ud
-    const float w = (a.tx * kx + a.ty * ky + a.tz * 10.0f) + 1;
-    rdir = smul(rcp_rn(w), rdir);
-    ro = add(rdir, mk(a.orig[0], a.orig[1], a.orig[2]));
-    rd = norm(rdir);
+    return eye_camera_ray(frame_camera(a), x, y, u0, u1);
 }
 // The closest hit of a ray, scanning from the last sphere down (:106-124): t = 1e20f, id = -1 on a miss.
-__device__ __forceinline__ void frame_closest(const bdpt_path_args& a, int bvh, f3 ro, f3 rd, float& t, int& id) {
-    t = 1e20f;
-    id = -1;
+struct frame_hit { float t; int id; };
+__device__ __forceinline__ frame_hit frame_closest(const bdpt_path_args& a, int bvh, f3 ro, f3 rd) {
+    float t = 1e20f;
+    int id = -1;
     if (bvh) {
         // walls by brute force, then the BVH; equal distances go to the higher index, which is
         // what the reference's downward scan with `d < t` yields
@@ -2020,6 +1934,7 @@ __device__ __forceinline__ void frame_closest(const bdpt_path_args& a, int bvh, 
             if (q.t2 > kEps && r < t) { t = r; id = s; }
         }
     }
+    return {t, id};
 }
 __device__ __forceinline__ bdpt_dev_vec dev_vec(f3 v) {
     bdpt_dev_vec o;
@@ -2028,11 +1943,42 @@ __device__ __forceinline__ bdpt_dev_vec dev_vec(f3 v) {
 }
 }  // namespace
 
+// First-hit feature buffers (include/bdpt.h bdpt_render_aov; no reference counterpart): the first
+// segment of the eye path on its own, one lane per pixel of the window -- the camera ray
+// (device.cu:562-600), the closest hit (:106-124) and hitPoint / normal / dp (:635-643), with the
+// float operations of bdpt_path_kernel_t in its order, so the planes equal what the path kernel
+// forms inside.  Nothing but the six output planes is written.
+extern "C" __global__ __launch_bounds__(256) void bdpt_aov_kernel(bdpt_path_args a, bdpt_aov_args v) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lx = v.rows ? (int)blockIdx.x * BDPT_AOV_ROW_BTW + lane
+                          : (int)blockIdx.x * BDPT_AOV_BVH_BTW + wave * 8 + (lane & 7);
+    const int ly = v.rows ? (int)blockIdx.y * BDPT_AOV_ROW_BTH + wave
+                          : (int)blockIdx.y * BDPT_AOV_BVH_BTH + (lane >> 3);
+    if (lx >= v.w || ly >= v.h) return;                  // (no cross-lane operation below)
+    const eye_ray r = frame_camera_ray(a, v.x0 + lx, v.y0 + ly, v.jitter, v.sid);
+    frame_hit h = frame_closest(a, v.bvh, r.o, r.d);
+    eye_vertex p = {mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f), 0.f};       // a miss: +0 everywhere but dir
+    if (h.id >= 0) {
+        const float4 pc = a.geom[h.id];
+        p = eye_vertex_at(r.o, r.d, h.t, mk(pc.x, pc.y, pc.z));
+    } else {
+        h.t = 0.f;
+    }
+    const size_t o = (size_t)ly * (size_t)v.w + (size_t)lx;
+    v.id[o] = h.id;
+    v.t[o] = h.t;
+    v.dp[o] = p.dp;
+    v.position[o] = dev_vec(p.hit);
+    v.normal[o] = dev_vec(p.normal);
+    v.dir[o] = dev_vec(r.d);
+}
+
 // The eye path up to its first non-specular vertex (include/bdpt.h bdpt_render_chain; no reference
 // counterpart): bdpt_aov_kernel's ray and hit, then the integrator's mirror and glass branches
-// (device.cu:621-771) with the float operations of bdpt_path_kernel_t in its order, until a diffuse
-// surface, an emitter or a miss ends the chain, or the 7th segment does.  One lane per pixel of the
-// window; nothing but the ten output planes is written; no LDS, no cross-lane operation.
+// (device.cu:621-771; bdpt_eye.h eye_specular) with the float operations of bdpt_path_kernel_t in
+// its order, until a diffuse surface, an emitter or a miss ends the chain, or the 7th segment
+// does.  One lane per pixel of the window; nothing but the ten output planes is written; no LDS,
+// no cross-lane operation.
 //  * The loop is divergent: a lane leaves it where its chain ends (most at depth 0) and the wave
 //    goes on while any lane follows a mirror.  The scan indices stay wave-uniform among the lanes
 //    still in the loop, so the scene is read with scalar loads as in bdpt_aov_kernel; the hit
@@ -2046,93 +1992,43 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_chain_kernel(bdpt_path_ar
                           : (int)blockIdx.y * BDPT_AOV_BVH_BTH + (lane >> 3);
     if (lx >= v.w || ly >= v.h) return;                  // (no cross-lane operation below)
     const int x = v.x0 + lx, y = v.y0 + ly;
-    const unsigned base = 26u + (unsigned)(y * a.W + x) * 25u;
-    float u0 = 0.f, u1 = 0.f;
-    if (v.jitter) {
-        const unsigned kk = (base + v.sid) % (kRandN - 5u);
-        u0 = a.rnd[kk];
-        u1 = a.rnd[kk + 1];
-    }
-    f3 ro, rd;
-    frame_camera_ray(a, x, y, u0, u1, ro, rd);
+    eye_ray r = frame_camera_ray(a, x, y, v.jitter, v.sid);
 
-    f3 thr = mk(1.f, 1.f, 1.f), hit = mk(0.f, 0.f, 0.f), normal = hit;
-    float len = 0.f, dp = 0.f;
+    f3 thr = mk(1.f, 1.f, 1.f);
+    eye_vertex p = {mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f), 0.f};
+    float len = 0.f;
     int id = -1, first_id = -1, bounces = 0, kind = BDPT_DEV_CHAIN_EXHAUSTED;
     for (unsigned depth = 0; depth <= 6u; ++depth) {
-        float t;
-        int s;
-        frame_closest(a, v.bvh, ro, rd, t, s);
-        if (depth == 0u) first_id = s;
-        if (s < 0) {
+        const frame_hit h = frame_closest(a, v.bvh, r.o, r.d);
+        if (depth == 0u) first_id = h.id;
+        if (h.id < 0) {
             kind = BDPT_DEV_CHAIN_MISS;
             break;
         }
-        const bdpt_dev_sphere S = v.sph[s];
-        len = len + t;
-        hit = add(ro, smul(t, rd));                      // :635-637
-        normal = norm(sub(hit, mk(S.px, S.py, S.pz)));   // :639-641
-        dp = dot(normal, rd);                            // :643
+        const bdpt_dev_sphere S = v.sph[h.id];
+        len = len + h.t;
+        p = eye_vertex_at(r.o, r.d, h.t, mk(S.px, S.py, S.pz));
         if (!(S.ex == 0.f && S.ey == 0.f && S.ez == 0.f)) {   // :651, before the material
             kind = BDPT_DEV_CHAIN_EMITTER;
-            id = s;
+            id = h.id;
             break;
         }
         if (S.refl == BDPT_DEV_DIFF) {
             kind = BDPT_DEV_CHAIN_DIFFUSE;
-            id = s;
+            id = h.id;
             break;
         }
         bounces++;
-        const f3 cc = mk(S.cx, S.cy, S.cz);
-        const f3 refl = sub(rd, smul(2.f * dot(normal, rd), normal));
-        ro = hit;
-        if (S.refl == BDPT_DEV_SPEC) {                   // :704-714
-            thr = mul(thr, cc);
-            rd = refl;
-            continue;
-        }
-        // REFR / LITE (:715-770)
-        const f3 nl = dp > 0 ? mk(-normal.x, -normal.y, -normal.z) : normal;   // (-1*sign(dp))*n, exact
-        const float nc = 1.f, nt = 1.5f;
-        const bool into = dot(normal, nl) > 0;
-        const float nnt = into ? nc / nt : nt / nc;
-        const float ddn = dot(rd, nl);
-        const float cos2t = 1.f - nnt * nnt * (1.f - ddn * ddn);
-        if (cos2t < 0.f) {                               // total internal reflection
-            thr = mul(thr, cc);
-            rd = refl;
-            continue;
-        }
-        // cos2t = 1 - X is 0 or >= 2^-24: the core root is exact, as in the path kernel
-        const float kq = (float)(into ? 1 : -1) * (ddn * nnt + bdpt_sqrt_rn_core(cos2t));
-        const f3 td = norm(sub(smul(nnt, rd), smul(kq, normal)));
-        const float aa = nt - nc, bb = nt + nc;
-        const float R0 = aa * aa / (bb * bb);
-        const float c = 1 - (into ? -ddn : dot(td, normal));
-        const float Re = R0 + (1 - R0) * c * c * c * c * c;
-        const float Tr = 1.f - Re;
-        const float Pp = .25f + .5f * Re;
-        bool reflect = false;
-        if (v.pass) reflect = a.rnd[(base + depth * 5u + v.sid) % (kRandN - 5u) + 2u] < Pp;
-        const float k = div_rn_normal(reflect ? Re : Tr, reflect ? Pp : 1.f - Pp);
-        thr = mul(smul(k, thr), cc);
-        rd = reflect ? refl : td;
+        r.o = p.hit;
+        eye_specular(S.refl == BDPT_DEV_SPEC, p.normal, p.dp, mk(S.cx, S.cy, S.cz), [&](float P) {
+            return v.pass && a.rnd[eye_rand_index((unsigned)(y * a.W + x), depth, v.sid) + 2u] < P;
+        }, r.d, thr);
     }
-    if (kind >= BDPT_DEV_CHAIN_MISS) {                   // MISS, EXHAUSTED: no end vertex
-        hit = mk(0.f, 0.f, 0.f);
-        normal = hit;
-        dp = 0.f;
-    }
+    if (kind >= BDPT_DEV_CHAIN_MISS) p = {mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f), 0.f};   // MISS, EXHAUSTED: no end vertex
     const size_t o = (size_t)ly * (size_t)v.w + (size_t)lx;
-    if (v.key_n > 0) {
-        // the denoisers' guide key (include/bdpt.h BDPT_DENOISE_THROUGH); the host has checked that
-        // 6 n^2 + n fits an int
-        int key = -1;
-        if (kind == BDPT_DEV_CHAIN_DIFFUSE)
-            key = bounces == 0 ? id : v.key_n + ((bounces - 1) * v.key_n + first_id) * v.key_n + id;
-        v.id[o] = key;
-        v.normal[o] = dev_vec(normal);
+    if (v.key_n > 0) {                                   // the denoisers' guides alone
+        v.id[o] = through_key(kind == BDPT_DEV_CHAIN_DIFFUSE, v.key_n, bounces, first_id, id);
+        v.normal[o] = dev_vec(p.normal);
         return;
     }
     v.id[o] = id;
@@ -2140,10 +2036,10 @@ extern "C" __global__ __launch_bounds__(256) void bdpt_chain_kernel(bdpt_path_ar
     v.kind[o] = kind;
     v.bounces[o] = bounces;
     v.t[o] = len;
-    v.dp[o] = dp;
-    v.position[o] = dev_vec(hit);
-    v.normal[o] = dev_vec(normal);
-    v.dir[o] = dev_vec(rd);
+    v.dp[o] = p.dp;
+    v.position[o] = dev_vec(p.hit);
+    v.normal[o] = dev_vec(p.normal);
+    v.dir[o] = dev_vec(r.d);
     v.throughput[o] = dev_vec(thr);
 }
 
